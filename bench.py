@@ -8,9 +8,17 @@ closed-loop steps (after W warm-up steps of the same simulation) with all inputs
 value = instances * K / time over all ranks.
 
     python bench.py --gpus 1 --steps 200 --warmup 200
+    python bench.py --gpus 1 --steps 200 --warmup 200 --full
+    python bench.py --gpus 1 --steps 200 --warmup 200 --dump-outputs DIR
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-The `roofline` block states the bound that binds these fused kernels (primary definition):
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, ...).
+`--full` adds everything else the benchmark measures after the clock stopped: the closed loop's key figures and solver
+counts, the `roofline` and comparison blocks, the CPU baseline and (default single-GPU command) the `secondary` block.
+`--dump-outputs DIR` writes what the last timed step handed back to its caller as DIR/<name>.npy (float64; the inputs
+are seeded, so two builds can be compared output for output).
+
+The `roofline` block (--full) states the bound that binds these fused kernels (primary definition):
 fp64 vector issue.  HBM does not bind (about 0.2 KB of compulsory traffic per QP step) and there is no dense
 contraction for MFMA.  achieved = fp64 flops the kernel executes per QP step (PMC counters of the committed profile of
 this same command, profiles/r02_*_summary.json: SQ_INSTS_VALU_{ADD,MUL,FMA}_F64 x 64 lanes x active-lane fraction)
@@ -137,16 +145,58 @@ def build_parser():
                     help="abmpc: the headline (BASELINE.json configs[1]); fbmpc: configs[2]; blmpc: the baseline controller "
                          "(RunOpt_BLMPC, a handle with bl_mode = 1); same contract; nlp: BASELINE configs[4] -- RunOpt_NLP, "
                          "--batch routes per GPU (default there: 128 = 1024 / 8), one step = one cold-start solve of all of them")
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=200)
-    ap.add_argument("--batch", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 200; --workload nlp: 1)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed warm-up steps (default 200; --workload nlp: 0)")
+    ap.add_argument("--batch", type=int, default=None, help="instances per GPU (default 4096; --workload nlp: 128 routes)")
     ap.add_argument("--horizon", type=int, default=30)
     ap.add_argument("--chunk", type=int, default=0, help="steps per kernel launch (0 = all K in one launch)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also report what the headline does not need: key figures, solver counts, roofline and comparison "
+                         "blocks, the CPU baseline and the secondary measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary measurements (FBMPC, N=60, baseline controller, a few NLP routes) that the default "
-                         "single-GPU headline command appends under \"secondary\"")
+                    help="with --full: skip the secondary measurements (FBMPC, N=60, baseline controller, a few NLP routes) that "
+                         "the default single-GPU headline command appends under \"secondary\"")
     return ap
+
+
+def resolve_defaults(args):
+    """--steps / --warmup / --batch left unset take the workload's defaults; a value given is used as given."""
+    nlp = args.workload == "nlp"
+    for name, qp_default, nlp_default in (("steps", 200, 1), ("warmup", 200, 0), ("batch", 4096, 128)):
+        if getattr(args, name) is None:
+            setattr(args, name, nlp_default if nlp else qp_default)
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays, axis, rank=0, world=1):
+    """Write arrays (name -> tensor / ndarray, all sharing the instance count along `axis`) as float64 .npy files under
+    outdir; above DUMP_LIMIT_BYTES in all, a fixed seeded sample of instances is kept (its indices go to instances.npy).
+    Ranks other than 0 of a multi-rank job suffix their files with _rank<r>."""
+    import torch
+    out = {}
+    for name, x in arrays.items():
+        if x is None:
+            continue
+        if isinstance(x, torch.Tensor):
+            x = x.detach().cpu().numpy()
+        out[name] = np.asarray(x, dtype=np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = next(iter(out.values())).shape[axis]
+        keep = max(1, int(DUMP_LIMIT_BYTES // (total / n + 8)))          # 8: the instance's index in instances.npy
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        out = {k: np.take(a, idx, axis=axis) for k, a in out.items()}
+        out["instances"] = idx.astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    sfx = "_rank%d" % rank if world > 1 and rank > 0 else ""
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + sfx + ".npy"), np.ascontiguousarray(a))
 
 
 def dist_setup(device=None, backend=None):
@@ -230,15 +280,16 @@ def run_bench(args, make_engine=None, device=None, backend=None):
         return local_kpis(traj_all[:n], stat_all[:n], E, Ts, cutoff, OUT)
 
     # warm-up: W untimed steps of the simulation; also loads the code objects of every kernel the timed region
-    # launches (ours and torch's small reductions, which are loaded lazily) and runs the collectives once
+    # launches; with --full also those of the key-figure reduction after the clock (ours and torch's small reductions,
+    # which are loaded lazily) and runs its collectives once
     if W > 0:
         run(0, W, False, 0)
-        kw = kpis(W)
-    else:
-        traj_all[:1].zero_(); stat_all[:1].zero_()
-        kw = kpis(1)
-    kw = tuple(x if backend == "nccl" else x.cpu() for x in kw)
-    reduce_kpis(*kw, world)
+    if args.full:
+        if W == 0:
+            traj_all[:1].zero_(); stat_all[:1].zero_()
+        kw = kpis(max(W, 1))
+        kw = tuple(x if backend == "nccl" else x.cpu() for x in kw)
+        reduce_kpis(*kw, world)
     sync()
     if world > 1:
         dist.barrier()
@@ -265,6 +316,29 @@ def run_bench(args, make_engine=None, device=None, backend=None):
     dt = time.perf_counter() - t0                  # exactly the K steps, bracketed by barrier + synchronize
     kernel_ms = ev0.elapsed_time(ev1) if on_gpu else dt * 1e3
     dt = max_over_ranks(dt, world, d if backend == "nccl" else None)
+    if hasattr(eng, "synchronize"):
+        eng.synchronize()                       # raises if the closed-loop kernel flagged a device-side failure
+    if args.dump_outputs:
+        # what the closed loop handed back for its last timed step (W + K - 1): traj [OUT_N, B] and status [B]
+        dump_outputs(args.dump_outputs, {"traj": traj_all[K - 1], "status": stat_all[K - 1]}, axis=-1, rank=rank, world=world)
+
+    res = None
+    if rank == 0:
+        total_steps = world * B * K
+        res = {
+            "metric": "QP steps/sec (whole node), %s N=%d dense QP at batch %d" % ("FBMPC" if fb else ("BLMPC" if bl else "ABMPC"), N, B),
+            "value": total_steps / dt, "unit": "QP steps/s", "n_gpus": min(world, n_dev) if on_gpu else 0, "ranks": world, "steps": K,
+            "warmup": W, "ms_per_step": dt * 1e3 / K, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": "%s N=%d fp64, batch=%d synthetic S2 ego/lead scenarios per GPU, closed loop"
+                                   % ("FBMPC" if fb else ("BLMPC (baseline controller, LP)" if bl else "ABMPC"), N, B),
+                       "batch_per_gpu": B, "horizon": N, "steps_per_launch": int(K / launches),
+                       "parallelism": "instances sharded across %d GPU(s), no data-path collective" % world}}
+        if world > 1 and on_gpu and world > n_dev:
+            res["note"] = "rehearsal: %d ranks share %d device(s)" % (world, n_dev)
+    if not args.full:
+        return res
+
     # key-figure reduction of the job (the only collectives: SUM, MIN, MAX of three small tensors), after the clock
     # stopped: it is the job's final report, not part of the K steps
     t_k = time.perf_counter()
@@ -273,15 +347,10 @@ def run_bench(args, make_engine=None, device=None, backend=None):
     sums, mins, maxs = reduce_kpis(*kp, world)
     sync()
     kpi_ms = (time.perf_counter() - t_k) * 1e3
-    if hasattr(eng, "synchronize"):
-        eng.synchronize()                       # raises if the closed-loop kernel flagged a device-side failure
     iters = eng.last_iterations(B)
     neg_v = int((traj_all[:K, OUT["v"]] < -1e-11).sum().item())
 
-    res = None
     if rank == 0:
-        total_steps = world * B * K
-        value = total_steps / dt
         nV, nC = (6 * N, 26 * N + 2) if fb else ((2 * N, 13 * N + 2) if bl else (5 * N, 14 * N + 2))
         bytes_mat = 8 * (nV * nV + nC * nV + 3 * nV + 2 * nC) + 8 * (nV + 1)     # SURVEY 8d, R-materialised
         bytes_fused = 152                                                          # SURVEY 8d, R-fused (compulsory)
@@ -323,15 +392,7 @@ def run_bench(args, make_engine=None, device=None, backend=None):
                     "traffic": None, "definition": "no committed PMC profile for this workload (%s)" % prof_path,
                     "kernel": kname, "launches": launches, "launch_ms": launch_s * 1e3}
         it_step = float(iters.mean()) / max(K / launches, 1)
-        res = {
-            "metric": "QP steps/sec (whole node), %s N=%d dense QP at batch %d" % ("FBMPC" if fb else ("BLMPC" if bl else "ABMPC"), N, B),
-            "value": value, "unit": "QP steps/s", "n_gpus": min(world, n_dev) if on_gpu else 0, "ranks": world, "steps": K, "warmup": W,
-            "ms_per_step": dt * 1e3 / K, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "%s N=%d fp64, batch=%d synthetic S2 ego/lead scenarios per GPU, closed loop"
-                                   % ("FBMPC" if fb else ("BLMPC (baseline controller, LP)" if bl else "ABMPC"), N, B),
-                       "batch_per_gpu": B, "horizon": N, "steps_per_launch": int(K / launches),
-                       "parallelism": "instances sharded across %d GPU(s), no data-path collective" % world},
+        res.update({
             "roofline": roof,
             # comparison figures only: what the reference's dense-QP API would move per QP step, and the
             # compulsory traffic of the fused step
@@ -345,9 +406,7 @@ def run_bench(args, make_engine=None, device=None, backend=None):
                                "of the reference QP: that QP has no solution, the reference reports exitMessage = 1 as well"},
             "kpi": kpi_dict(sums, mins, maxs),
             "kpi_reduction_ms": kpi_ms,
-        }
-        if shared := (world > 1 and on_gpu and world > n_dev):
-            res["note"] = "rehearsal: %d ranks share %d device(s)" % (world, n_dev)
+        })
         if not args.no_cpu_baseline and world == 1 and on_gpu:      # reported at N = 1 only
             res["cpu_baseline"] = cpu_baseline(OPT, V, sc, "fb", 2, 60) if fb else cpu_baseline(OPT, V, sc)      # ~10-25 s of host work
             res["cpu_baseline"]["host_cores_available"] = os.cpu_count()
@@ -370,6 +429,8 @@ def secondary_measurements(args):
     (default command, one rank): short launches of the driver's own shape so the whole command stays within minutes."""
     import copy
     out = {}
+    args = copy.copy(args)
+    args.full, args.dump_outputs = True, None           # each entry keeps its roofline / solver blocks; only the headline dumps
     plan = [("fbmpc_N30_b4096", dict(workload="fbmpc", horizon=30, batch=4096)),                # BASELINE configs[2]
             ("abmpc_N60_b8192", dict(workload="abmpc", horizon=60, batch=8192)),                # configs[3]: 65536 / 8 per GPU
             ("blmpc_N30_b4096", dict(workload="blmpc", horizon=30, batch=4096)),
@@ -425,17 +486,15 @@ def nlp_traces(OPT, lead, rank, Rn):
 def run_nlp_bench(args, make_solver=None, device=None, backend=None):
     """BASELINE configs[4]: RunOpt_NLP for `--batch` routes per GPU (the reference's 435 s scenario with the lead vehicle's
     speed trace scaled per route), each solved from a cold start by the multi-start batch.  Routes shard across ranks with
-    no data-path collective; one all-reduce (SUM) of (routes at a KKT point, sum of objectives, iterations) at the end.
-    make_solver(OPT, V, dev) -> callable(traces) -> dict(status, J, iters) (torch tensors, one entry per route): default is
-    the HIP solver; the CPU test drives the same flow over gloo with a stand-in."""
+    no data-path collective; with --full one all-reduce (SUM) of (routes at a KKT point, sum of objectives, iterations) at
+    the end.  make_solver(OPT, V, dev) -> callable(traces) -> dict(status, J, iters) (torch tensors, one entry per route):
+    default is the HIP solver; the CPU test drives the same flow over gloo with a stand-in."""
     import torch
     import torch.distributed as dist
     from conftest import make_case
     from eepacc_mpc_casadi_matlab_amd.distributed import max_over_ranks
     rank, world, local_rank, backend, on_gpu, n_dev, dev, d = dist_setup(device, backend)
-    K = args.steps if args.steps != 200 else 1
-    W = args.warmup if args.warmup != 200 else 0
-    Rn = args.batch if args.batch != 4096 else 128
+    K, W, Rn = args.steps, args.warmup, args.batch
     OPT, V, _, _ = make_case("ABO")
     lead = np.load(os.path.join(ROOT, "tests", "golden", "lead_TO01_EAD.npz"))
     traces = nlp_traces(OPT, lead, rank, Rn)
@@ -464,29 +523,35 @@ def run_nlp_bench(args, make_solver=None, device=None, backend=None):
         dist.barrier()
     sync()
     dt = max_over_ranks(time.perf_counter() - t0, world, d if backend == "nccl" else None)
-    kp = torch.stack([(R["status"] == 0).sum().double(), R["J"].double().sum(), R["iters"].double().sum()])
-    kp = kp if (backend == "nccl" or not on_gpu) else kp.cpu()
-    if world > 1:
-        dist.all_reduce(kp, op=dist.ReduceOp.SUM)
+    if args.dump_outputs:
+        # what solve_routes handed back for the last timed solve: per-route solution, objective, status, iterations, ...
+        dump_outputs(args.dump_outputs, {k: v for k, v in R.items() if isinstance(v, torch.Tensor)}, axis=0, rank=rank, world=world)
+    if args.full:
+        kp = torch.stack([(R["status"] == 0).sum().double(), R["J"].double().sum(), R["iters"].double().sum()])
+        kp = kp if (backend == "nccl" or not on_gpu) else kp.cpu()
+        if world > 1:
+            dist.all_reduce(kp, op=dist.ReduceOp.SUM)
     if rank != 0:
         return None
     total = world * Rn * K
-    return {"metric": "RunOpt_NLP routes solved/s (whole node), 435 s route = 870 intervals, cold start", "value": total / dt,
-            "unit": "routes/s", "n_gpus": min(world, n_dev) if on_gpu else 0, "ranks": world, "steps": K, "warmup": W, "ms_per_step": dt * 1e3 / K,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "RunOpt_NLP, %d routes per GPU x %d starts, 870 intervals, lead trace scaled per route" % (Rn, len(NLP_STARTS)),
-                       "routes_per_gpu": Rn, "starts_per_route": len(NLP_STARTS)},
-            "solver": {"routes_at_kkt_point": int(kp[0].item()), "routes": world * Rn, "mean_iterations": float(kp[2].item()) / (world * Rn),
-                       "sum_objective": float(kp[1].item())},
-            "reference": {"ipopt_tSolve_s_one_route": 190.4754463, "source": "ABO/savedNLPsol.mat (NLPsol.tSolve), other hardware"}}
+    res = {"metric": "RunOpt_NLP routes solved/s (whole node), 435 s route = 870 intervals, cold start", "value": total / dt,
+           "unit": "routes/s", "n_gpus": min(world, n_dev) if on_gpu else 0, "ranks": world, "steps": K, "warmup": W, "ms_per_step": dt * 1e3 / K,
+           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+           "config": {"workload": "RunOpt_NLP, %d routes per GPU x %d starts, 870 intervals, lead trace scaled per route" % (Rn, len(NLP_STARTS)),
+                      "routes_per_gpu": Rn, "starts_per_route": len(NLP_STARTS)}}
+    if args.full:
+        res["solver"] = {"routes_at_kkt_point": int(kp[0].item()), "routes": world * Rn, "mean_iterations": float(kp[2].item()) / (world * Rn),
+                         "sum_objective": float(kp[1].item())}
+        res["reference"] = {"ipopt_tSolve_s_one_route": 190.4754463, "source": "ABO/savedNLPsol.mat (NLPsol.tSolve), other hardware"}
+    return res
 
 
 def main():
-    args = build_parser().parse_args()
+    args = resolve_defaults(build_parser().parse_args())
     import torch.distributed as dist
     res = run_nlp_bench(args) if args.workload == "nlp" else run_bench(args)
-    if (res is not None and args.workload == "abmpc" and not args.no_secondary and res.get("ranks") == 1 and res.get("n_gpus") == 1
-            and args.horizon == 30 and args.batch == 4096):
+    if (res is not None and args.full and args.workload == "abmpc" and not args.no_secondary and res.get("ranks") == 1
+            and res.get("n_gpus") == 1 and args.horizon == 30 and args.batch == 4096):
         res["secondary"] = secondary_measurements(args)
     if res is not None:
         print(json.dumps(res))

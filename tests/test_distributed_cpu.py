@@ -57,7 +57,7 @@ class OracleEngine:
 
 def _args(batch):
     return types.SimpleNamespace(workload="abmpc", steps=K, warmup=W, batch=batch, horizon=N_HOR, chunk=4,
-                                 no_cpu_baseline=True, gpus=1)
+                                 no_cpu_baseline=True, gpus=1, full=True, dump_outputs=None)
 
 
 def _worker(rank, world, port, outdir):
@@ -109,7 +109,8 @@ def _nlp_worker(rank, world, port, outdir):
     sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     import bench
-    args = types.SimpleNamespace(workload="nlp", steps=2, warmup=1, batch=3, horizon=30, chunk=0, no_cpu_baseline=True, gpus=world)
+    args = types.SimpleNamespace(workload="nlp", steps=2, warmup=1, batch=3, horizon=30, chunk=0, no_cpu_baseline=True, gpus=world,
+                                 full=True, dump_outputs=None)
     res = bench.run_nlp_bench(args, make_solver=_nlp_stand_in, device=torch.device("cpu"), backend="gloo")
     if rank == 0:
         json.dump(res, open(os.path.join(outdir, "nlp.json"), "w"))

@@ -468,7 +468,8 @@ def test_config5_at_its_per_gpu_size():
     (Determinism of the solver: test_native_solver_equals_the_host_loop.)"""
     import types
     import bench
-    args = types.SimpleNamespace(workload="nlp", steps=1, warmup=0, batch=128, horizon=30, chunk=0, no_cpu_baseline=True, gpus=1)
+    args = types.SimpleNamespace(workload="nlp", steps=1, warmup=0, batch=128, horizon=30, chunk=0, no_cpu_baseline=True, gpus=1,
+                                 full=True, dump_outputs=None)
     r1 = bench.run_nlp_bench(args)
     assert r1["solver"]["routes"] == 128 and r1["solver"]["routes_at_kkt_point"] >= 126, r1["solver"]
     assert np.isfinite(r1["solver"]["sum_objective"]) and r1["solver"]["mean_iterations"] > 10
