@@ -5,6 +5,7 @@
 // default path carries no register or instruction cost for the variants.
 namespace eepacc {
 namespace EEPACC_IMPL_NS {
+using namespace wv;
 
 constexpr bool kMoveBlocking = EEPACC_IMPL_MB;
 constexpr bool kBaseline = EEPACC_IMPL_BL;
@@ -17,7 +18,6 @@ constexpr bool kIce = false;
 
 #undef PTIC
 #undef PTOC
-#undef WSYNC
 #undef RTOC
 #ifdef EEPACC_AB_TIMING
 __device__ unsigned long long g_ab_prof[24];
@@ -27,7 +27,6 @@ __device__ unsigned long long g_ab_prof[24];
 #define PTIC(L)
 #define PTOC(L, slot)
 #endif
-#define WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
 
 constexpr double kInf = 1e300;
 constexpr double kTolViol = 1e-11;
@@ -35,85 +34,9 @@ constexpr double kTolViol = 1e-11;
 __device__ int g_trace_on = 0;       // event trace of single-instance launches (tools/gpu_bl_trace*.py, tools/gpu_ab_trace_one.py)
 #endif
 constexpr double kTolDual = 1e-12;
-#ifndef EEPACC_SINGLE_PASSES
-#define EEPACC_SINGLE_PASSES 14
-#endif
-constexpr int kSinglePasses = EEPACC_SINGLE_PASSES;
-#ifndef EEPACC_PF_ADDS
-#define EEPACC_PF_ADDS 4
-#endif
-constexpr int kPfAdds = EEPACC_PF_ADDS;        // rows a warm start may take in (primal first) before its negative multipliers are repaired
+constexpr int kSinglePasses = 14;
+constexpr int kPfAdds = 4;        // rows a warm start may take in (primal first) before its negative multipliers are repaired
 constexpr int kChunkStepsDefault = 16;      // MPC steps per work unit of the closed-loop kernel
-
-// ----------------------------------------------------------------------------------------------
-// wave primitives
-__device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
-
-// broadcast from a wave-uniform source lane (v_readlane)
-__device__ __forceinline__ double bcast(double x, int src) {
-    const int s = __builtin_amdgcn_readfirstlane(src);
-    int lo = __builtin_amdgcn_readlane(__double2loint(x), s);
-    int hi = __builtin_amdgcn_readlane(__double2hiint(x), s);
-    return __hiloint2double(hi, lo);
-}
-
-// DPP cross-lane moves (VALU data path, no LDS round trip).  ctrl: row_shr:n = 0x110+n,
-// row_bcast:15 = 0x142, row_bcast:31 = 0x143, wave_shr:1 = 0x138 (gfx9-family encodings).
-// dpp_zero: lanes without a valid source (or masked rows) read 0; dpp_keep: they keep their value.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_zero(double x) {
-    int lo = __double2loint(x), hi = __double2hiint(x);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, ROW_MASK, 0xf, true);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, ROW_MASK, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_keep(double x) {
-    int lo = __double2loint(x), hi = __double2hiint(x);
-    lo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xf, false);
-    hi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double read_lane63(double x) {
-    int lo = __builtin_amdgcn_readlane(__double2loint(x), 63);
-    int hi = __builtin_amdgcn_readlane(__double2hiint(x), 63);
-    return __hiloint2double(hi, lo);
-}
-// inclusive prefix sum over the 64 lanes (Hillis-Steele inside 16-lane rows, then row broadcasts)
-__device__ __forceinline__ double scan_incl(double x) {
-    x += dpp_zero<0x111, 0xf>(x);
-    x += dpp_zero<0x112, 0xf>(x);
-    x += dpp_zero<0x114, 0xf>(x);
-    x += dpp_zero<0x118, 0xf>(x);
-    x += dpp_zero<0x142, 0xa>(x);
-    x += dpp_zero<0x143, 0xc>(x);
-    return x;
-}
-__device__ __forceinline__ double wave_sum(double x) { return read_lane63(scan_incl(x)); }
-// exclusive prefix sum over lanes
-__device__ __forceinline__ double scan_excl(double x) { return dpp_zero<0x138, 0xf>(scan_incl(x)); }
-__device__ __forceinline__ double wave_max(double x) {
-    x = fmax(x, dpp_keep<0x111, 0xf>(x));
-    x = fmax(x, dpp_keep<0x112, 0xf>(x));
-    x = fmax(x, dpp_keep<0x114, 0xf>(x));
-    x = fmax(x, dpp_keep<0x118, 0xf>(x));
-    x = fmax(x, dpp_keep<0x142, 0xa>(x));
-    x = fmax(x, dpp_keep<0x143, 0xc>(x));
-    return read_lane63(x);
-}
-// arg-min / arg-max with integer payload; ties go to the lowest lane (deterministic)
-__device__ __forceinline__ void wave_argmax(double& v, int& p) {
-    const double best = wave_max(v);
-    const unsigned long long mask = __ballot(v == best);
-    const int src = mask ? (__ffsll((long long)mask) - 1) : 0;
-    p = __builtin_amdgcn_readlane(p, src);
-    v = best;
-}
-__device__ __forceinline__ void wave_argmin(double& v, int& p) {
-    double nv = -v;
-    wave_argmax(nv, p);
-    v = -nv;
-}
 
 // ----------------------------------------------------------------------------------------------
 // row catalogue
@@ -154,8 +77,6 @@ struct WaveMem {                 // one per wave, in LDS (followed by the wave's
     // (the pivot column of the factor updates lives in ws | wv | wa, which are free while the factor is rebuilt)
     int w_k[MMAX];
 };
-
-__device__ __forceinline__ int pidx(int i, int j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; }
 
 // per-lane (= per-stage) registers of the wave's QP
 struct Lane {
@@ -260,10 +181,7 @@ __device__ __forceinline__ void hom_traj(const Lane& L, double x, double& sh, do
 // offset.  NS = 64: packed lower triangle (entry (i,j), i >= j, at i(i+1)/2 + j): 16.6 KB instead of 32 KB, which is
 // what lets a third wave onto a CU at N = 60.  Lane k reads (i,k) for i >= k and (k,i) for i < k; the triangular
 // numbers are a permutation modulo 32, so both access patterns spread over the LDS banks.
-#ifndef EEPACC_PACK_SMALL
-#define EEPACC_PACK_SMALL 0
-#endif
-template <int NS> constexpr bool kPackedHe = NS > 32 || EEPACC_PACK_SMALL;
+template <int NS> constexpr bool kPackedHe = NS > 32;
 template <int NS> constexpr int kHeDoubles = kPackedHe<NS> ? NS * (NS + 1) / 2 : NS * NS;
 __device__ __forceinline__ int he_tri(int i) { return i * (i + 1) / 2; }
 
@@ -416,24 +334,6 @@ __device__ __forceinline__ void he_load_base(double* He, const double* __restric
             He[e] = (i < N && j < N) ? base[i * N + j] : 0.0;
         }
     }
-}
-
-// row/column of entry e of a packed lower triangle (e = r(r+1)/2 + c), one table per workgroup
-template <int MMAX>
-__device__ __forceinline__ unsigned short* rc_table() {
-    __shared__ unsigned short tab[MMAX * (MMAX + 1) / 2];
-    return tab;
-}
-template <int MMAX>
-__device__ __forceinline__ void rc_table_init() {      // every thread of the workgroup, before any returns
-    unsigned short* tab = rc_table<MMAX>();
-    for (int e = threadIdx.x; e < MMAX * (MMAX + 1) / 2; e += blockDim.x) {
-        int r = (int)((sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);
-        while (r * (r + 1) / 2 > e) --r;
-        while ((r + 1) * (r + 2) / 2 <= e) ++r;
-        tab[e] = (unsigned short)((r << 8) | (e - r * (r + 1) / 2));
-    }
-    __syncthreads();
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -1425,8 +1325,6 @@ __device__ void force_allocation(const DevCfg& C, double s_meas, double v_meas, 
     a_real = (Fm + Fb + F_r) / C.m / C.lambda;
 }
 
-struct StepOut { double out[EEPACC_OUT_N]; int status, iters; };
-
 // One ABMPC step for the wave's instance (ABO/RunOpt_ABMPC.m:193-329).  `code` carries the
 // working set between steps (already shifted by the caller).
 template <int MMAX, int NS>
@@ -1612,13 +1510,11 @@ __device__ __forceinline__ void ab_step(const DevCfg& C, WaveMem<MMAX, NS>& M, d
     // is slower than the incentive speed at the zero-acceleration trajectory starts off its bound.  The dual iteration would
     // reach that state one stage per iteration (measured: 29 of the 51 working-set changes of a first step); a stage where
     // it is wrong shows up as a violated slack bound, like any other wrong state.
-#ifndef EEPACC_NO_CRASH_START
     if constexpr (!kBaseline) {
         if (!__any(L.code != 0ull)) {
             if (lane < N && ((L.valid >> R_VINC) & 1u) && row_val(L, c, R_VINC, L.ba[R_VINC]) > L.lbV) set_code(L, R_VINC, 2);
         }
     }
-#endif
     // baseline controller: a solve that fails from a warm working set (a degenerate vertex of the LP can leave the
     // shifted set numerically dependent) is repeated once from the empty one before the step is reported as failed
     // (compiled into that variant only: the loop costs the ABMPC kernels registers, and their tests never need it)
@@ -1742,21 +1638,9 @@ __device__ __forceinline__ void ab_step(const DevCfg& C, WaveMem<MMAX, NS>& M, d
 #endif
 }
 
-// receding-horizon shift of the working set: stage k takes stage k+1's codes, the last stage and
-// the terminal rows keep theirs
-__device__ __forceinline__ unsigned long long shift_codes(unsigned long long code, int N) {
-    const int lane = lane_id();
-    unsigned lo = (unsigned)code, hi = (unsigned)(code >> 32);
-    unsigned nlo = __shfl_down(lo, 1, 64), nhi = __shfl_down(hi, 1, 64);
-    unsigned long long nxt = ((unsigned long long)nhi << 32) | nlo;
-    if (lane < N - 1) return nxt;
-    return code;
-}
-
-
 // LDS layout of a block: per wave [WaveMem][He: N x N doubles]
 __host__ __device__ inline size_t wave_bytes(size_t wm, int ns) {
-    const size_t he = (ns > 32 || EEPACC_PACK_SMALL) ? (size_t)ns * (ns + 1) / 2 : (size_t)ns * ns;      // kHeDoubles<NS>
+    const size_t he = ns > 32 ? (size_t)ns * (ns + 1) / 2 : (size_t)ns * ns;      // kHeDoubles<NS>
     return ((wm + he * sizeof(double)) + 15) & ~(size_t)15;
 }
 
@@ -1793,25 +1677,17 @@ k_ab_step(const DevCfg* __restrict__ Cp, int B,
                       kIce ? C.hb + ((size_t)blockIdx.x * WPB + (threadIdx.x >> 6)) * (NS * NS) : nullptr);
     if (C.paramEstSetting == 2 && lane <= C.N) { predp[lane] = sp; predp[64 + lane] = vp; }
     codes[(size_t)b * 64 + lane] = shift_codes(code, C.N);
-    if (lane < EEPACC_OUT_N) {
-        double val = 0.0;
-#pragma unroll
-        for (int f = 0; f < EEPACC_OUT_N; ++f) if (f == lane) val = so.out[f];
-        out[(size_t)lane * B + b] = val;
-    }
+    write_out(out, 0, B, b, so, lane);
     if (s_pred && lane <= C.N) s_pred[(size_t)lane * B + b] = sp;
     if (v_pred && lane <= C.N) v_pred[(size_t)lane * B + b] = vp;
     if (lane == 0) { status[b] = so.status; if (iters) iters[b] = so.iters; }
 }
 
-// B1: closed loop over n_steps for B instances (ABO/RunOpt_ABMPC.m:154-340).  k_start > 0
-// resumes from the carried per-instance state (carry [6][B]: s, v, Fm, Fb of the previous step,
-// previous lead speed, t_0; codes: shifted working set).
-#ifndef EEPACC_AB_OCC
-#define EEPACC_AB_OCC 2       // waves per SIMD the small-horizon kernel is compiled for (1: 512 registers, no scratch; measured slower)
-#endif
+// B1: closed loop over n_steps for B instances (ABO/RunOpt_ABMPC.m:154-340) in work units (run_units, eepacc_units.h).
+// k_start > 0 resumes from the carried per-instance state (carry [6][B], see Carry; codes: shifted working set).  The
+// small-horizon kernel is compiled for 2 waves per SIMD (1: 512 registers, no scratch; measured slower).
 template <int MMAX, int NS, int WPB>
-__global__ void __launch_bounds__(64 * WPB, ((NS <= 32 && WPB >= 4) ? (MMAX <= 32 ? 3 : EEPACC_AB_OCC) : 1))
+__global__ void __launch_bounds__(64 * WPB, ((NS <= 32 && WPB >= 4) ? 2 : 1))
 k_run_abmpc(const DevCfg* __restrict__ Cp, int B, int k_start, int n_steps,
             const double* __restrict__ s0, const double* __restrict__ v0, const double* __restrict__ a_m1,
             const double* __restrict__ s_tv, const double* __restrict__ v_tv,
@@ -1829,121 +1705,38 @@ k_run_abmpc(const DevCfg* __restrict__ Cp, int B, int k_start, int n_steps,
 #ifdef EEPACC_BL_TRACE
     if (B == 1) g_trace_on = 1;
 #endif
-    // Instances take very different numbers of working-set changes (per-instance run times spread
-    // 0.75x..1.7x around the mean), so the simulation is cut into work units (instance, chunk of
-    // kChunkSteps MPC steps) handed out through a device-wide counter in chunk-major order.  The loop
-    // state of an instance travels between units through `carry`/`codes` in HBM: the producer wave
-    // publishes done[b] = chunk+1 behind an agent-scope release, the consumer polls done[b] relaxed
-    // and then takes one agent-scope acquire (cdna_hip_programming.md, Guideline 16).  A unit is only
-    // handed out after its predecessor has been picked by a running wave, so the wait is bounded.
-    const int n_chunks = (n_steps + kChunkSteps - 1) / kChunkSteps;
-    const int n_units = n_chunks * B;
-    for (int fetch = 0; fetch <= n_units; ++fetch) {
-    int u = 0;
-    if (lane == 0) u = atomicAdd(work_counter, 1);
-    u = __builtin_amdgcn_readfirstlane(u);
-    if (u >= n_units || u < 0) break;
-    const int chunk = u / B, b = u - chunk * B;
-    const int kk0 = chunk * kChunkSteps;
-    const int kk1 = (kk0 + kChunkSteps < n_steps) ? kk0 + kChunkSteps : n_steps;
-    bool failed = false;
-    if (chunk > 0) {
-        int spins = 0;
-        while (__hip_atomic_load(&done[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < chunk) {
-            __builtin_amdgcn_s_sleep(32);
-            if (++spins > spin_limit) { failed = true; break; }   // never expected; keeps every wave finite
-            // an earlier time-out of this launch: do not wait the full limit again behind it
-            if ((spins & 63) == 0 && __hip_atomic_load(err_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
+    run_units(B, n_steps, kChunkSteps, work_counter, done, err_word, spin_limit, status, iters_total, [&](int b, int kk0, int kk1) {
+        unsigned long long code = 0ull;
+        Carry cs;
+        if (k_start + kk0 > 0) {
+            cs.load(carry, B, b);
+            code = codes[(size_t)b * 64 + lane];
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    // A predecessor that was never published (or any earlier failure of this launch) must not be continued
-    // from stale state: the unit's steps get status 3, the sticky error word of the handle is set (the host
-    // turns it into EEPACC_EDEVICE, eepacc_synchronize) and the unit is still published so that its
-    // successors terminate.
-    if (failed || __hip_atomic_load(err_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-        if (lane == 0) {
-            if (failed) atomicOr(err_word, 1);
-            for (int kk = kk0; kk < kk1; ++kk) status[(size_t)kk * B + b] = 3;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            __hip_atomic_fetch_max(&done[b], chunk + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        int it_total = 0;
+        double* predp = C.pred + (size_t)b * 128;
+        for (int kk = kk0; kk < kk1; ++kk) {
+            StepIn in;
+            measure(C, Ts, k_start + kk, kk, B, b, s0, v0, a_m1, s_tv, v_tv, cs, in);
+            StepOut so;
+            double sp, vp;
+            ab_step<MMAX, NS>(C, M, Hs, in, code, so, sp, vp, predp, kk > kk0,
+                              kIce ? C.hb + ((size_t)blockIdx.x * WPB + (threadIdx.x >> 6)) * (NS * NS) : nullptr);
+            if (C.paramEstSetting == 2) {
+                WSYNC();
+                if (lane <= C.N) { M.ws[lane] = sp; M.wv[lane] = vp; }
+                WSYNC();
+                if (kk == kk1 - 1 && lane <= C.N) { predp[lane] = sp; predp[64 + lane] = vp; }
+            }
+            code = shift_codes(code, C.N);
+            write_out(traj, (size_t)kk * EEPACC_OUT_N, B, b, so, lane);
+            if (lane == 0) status[(size_t)kk * B + b] = so.status;
+            it_total += so.iters;
+            cs.advance(so, Ts);
         }
-        continue;
-    }
-#ifdef EEPACC_DEBUG_TIMING
-    const long long t_begin = wall_clock64();
-#endif
-    unsigned long long code = 0ull;
-    double s_prev = 0, v_prev = 0, Fm_prev = 0, Fb_prev = 0, v_tv_measured = 0.0, t_0 = 0.0;
-    if (k_start + kk0 > 0) {
-        s_prev = carry[0 * (size_t)B + b]; v_prev = carry[1 * (size_t)B + b];
-        Fm_prev = carry[2 * (size_t)B + b]; Fb_prev = carry[3 * (size_t)B + b];
-        v_tv_measured = carry[4 * (size_t)B + b]; t_0 = carry[5 * (size_t)B + b];
-        code = codes[(size_t)b * 64 + lane];
-    }
-    int it_total = 0;
-    double* predp = C.pred + (size_t)b * 128;
-    for (int kk = kk0; kk < kk1; ++kk) {
-        StepIn in;
-        if (k_start + kk == 0) {                             // :159-172
-            in.s = s0[b]; in.v = v0[b]; in.a_prev = a_m1[b];
-            in.s_tv = s_tv[b]; in.v_tv = 0.0; in.a_tv_prev = 0.0;
-            v_tv_measured = 0.0;
-        } else {                                             // :173-191
-            double sm, vm;
-            plant_rk4(C, s_prev, v_prev, Fm_prev + Fb_prev, sm, vm);
-            in.s = sm; in.v = vm;
-            in.a_prev = (vm - v_prev) / Ts;
-            in.s_tv = s_tv[(size_t)kk * B + b];
-            double v_tv_prev = v_tv_measured;
-            v_tv_measured = v_tv[(size_t)kk * B + b];
-            in.v_tv = v_tv_measured;
-            in.a_tv_prev = (v_tv_measured - v_tv_prev) / Ts;
-        }
-        in.t0 = t_0;
-        StepOut so;
-        double sp, vp;
-        ab_step<MMAX, NS>(C, M, Hs, in, code, so, sp, vp, predp, kk > kk0,
-                          kIce ? C.hb + ((size_t)blockIdx.x * WPB + (threadIdx.x >> 6)) * (NS * NS) : nullptr);
-        if (C.paramEstSetting == 2) {
-            WSYNC();
-            if (lane <= C.N) { M.ws[lane] = sp; M.wv[lane] = vp; }
-            WSYNC();
-            if (kk == kk1 - 1 && lane <= C.N) { predp[lane] = sp; predp[64 + lane] = vp; }
-        }
-        code = shift_codes(code, C.N);
-        if (lane < EEPACC_OUT_N) {
-            double val = 0.0;
-#pragma unroll
-            for (int f = 0; f < EEPACC_OUT_N; ++f) if (f == lane) val = so.out[f];
-            traj[((size_t)kk * EEPACC_OUT_N + lane) * B + b] = val;
-        }
-        if (lane == 0) status[(size_t)kk * B + b] = so.status;
-        it_total += so.iters;
-        s_prev = so.out[EEPACC_OUT_S]; v_prev = so.out[EEPACC_OUT_V];
-        Fm_prev = so.out[EEPACC_OUT_FM]; Fb_prev = so.out[EEPACC_OUT_FB];
-        t_0 += Ts;                                           // :329
-    }
-    codes[(size_t)b * 64 + lane] = code;
-    if (lane == 0) {
-        carry[0 * (size_t)B + b] = s_prev; carry[1 * (size_t)B + b] = v_prev;
-        carry[2 * (size_t)B + b] = Fm_prev; carry[3 * (size_t)B + b] = Fb_prev;
-        carry[4 * (size_t)B + b] = v_tv_measured; carry[5 * (size_t)B + b] = t_0;
-#ifdef EEPACC_DEBUG_TIMING
-        if (iters_total) atomicAdd(&iters_total[b], (int)((wall_clock64() - t_begin) / 100));   // microseconds
-#else
-        if (iters_total) atomicAdd(&iters_total[b], it_total);
-#endif
-    }
-    // publish the unit: all of this wave's stores, then release, then the flag
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_fetch_max(&done[b], chunk + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    }
+        codes[(size_t)b * 64 + lane] = code;
+        if (lane == 0) cs.store(carry, B, b);
+        return it_total;
+    });
 }
 
 // A10: post-processing (ABO/RunOpt_ABMPC.m:343-349), one thread per instance, sequential in time

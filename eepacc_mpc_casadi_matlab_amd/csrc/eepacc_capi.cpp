@@ -48,7 +48,7 @@ struct eepacc_handle {
     double* d_pred = nullptr;                // [max_batch][2][64] previous predictions (paramEstSetting 2)
     unsigned long long* d_codes = nullptr;   // [max_batch][64]
     int32_t* d_iters = nullptr;              // [max_batch]
-    double* d_carry = nullptr;               // [6][B] closed-loop carry (see k_run_abmpc)
+    double* d_carry = nullptr;               // [6][B] closed-loop carry (see Carry, eepacc_units.h)
     int* d_counter = nullptr;                // work counter of the closed-loop kernel
     int* d_done = nullptr;                   // [max_batch] chunks finished per instance
     int* d_err = nullptr;                    // sticky device error word (bit 0: a closed-loop hand-off timed out)
@@ -641,8 +641,7 @@ extern "C" int eepacc_run_fbmpc(eepacc_handle* h, int B, int n_steps, const doub
         a.s0 = s0; a.v0 = v0; a.a_m1 = a_minus1; a.s_tv = s_tv; a.v_tv = v_tv;
         a.carry = h->fbs_carry; a.state = h->fbs_state; a.hb = h->fbs_hb; a.traj = traj; a.status = status;
         a.iters_total = h->d_iters; a.work_counter = h->d_counter; a.done = h->d_done; a.err_word = h->d_err;
-        a.chunk_steps = chunk_steps; a.spin_limit = 1 << 26;
-        if (const char* ev = getenv("EEPACC_DEBUG_SPIN_LIMIT")) a.spin_limit = atoi(ev);
+        a.chunk_steps = chunk_steps;
         a.cold = 0;
         if (const char* ev = getenv("EEPACC_DEBUG_FBS_COLD")) a.cold = atoi(ev) != 0;
         HIPCHK(eepacc::launch_fbs_run(a, h->cfg.N, h->num_cus, (hipStream_t)stream));

@@ -32,7 +32,7 @@ struct fbs_run_args {           // B1: closed loop (ABO/RunOpt_FBMPC.m:161-331)
     double* traj;
     int32_t *status, *iters_total;
     int *work_counter, *done, *err_word;
-    int chunk_steps, spin_limit;
+    int chunk_steps, spin_limit;    // spin_limit: set by launch_fbs_run
     int cold;                   // debug: 1 = no working-set warm start between MPC steps
 };
 
@@ -41,7 +41,7 @@ size_t fbs_smem_bytes(int N);
 size_t fbs_hb_doubles(int N, int B, int num_cus);   // scratch a launch for B instances needs
 hipError_t fbs_set_max_smem();
 hipError_t launch_fbs_step(const fbs_step_args& a, int N, hipStream_t stream);
-hipError_t launch_fbs_run(const fbs_run_args& a, int N, int num_cus, hipStream_t stream);
+hipError_t launch_fbs_run(fbs_run_args a, int N, int num_cus, hipStream_t stream);
 
 }  // namespace eepacc
 #endif

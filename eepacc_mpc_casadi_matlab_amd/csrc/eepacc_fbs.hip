@@ -26,15 +26,13 @@
 #include <stdlib.h>
 #include "eepacc_device.h"
 #include "eepacc_stage.h"
-#include "eepacc_wave.h"
+#include "eepacc_units.h"
 #include "eepacc_fbs.h"
 #include "../../include/eepacc.h"
 
 namespace eepacc {
 namespace fbs {
 using namespace wv;
-
-#define WSYNC() EEPACC_WSYNC()
 
 #ifdef EEPACC_FBS_TIMING
 __device__ unsigned long long g_fbs_prof[16];
@@ -140,8 +138,6 @@ struct FMem {                 // one per wave, in LDS (followed by the wave's NS
     double ba[kNumSlots * (NS + 1)];                  // right-hand sides, [slot of the type][lane]
     int w_k[MMAX];
 };
-
-__device__ __forceinline__ int pidx(int i, int j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; }
 
 struct Tup { double al, be, ga, de, c; };
 __device__ __forceinline__ Tup tup0() { return Tup{0.0, 0.0, 0.0, 0.0, 0.0}; }
@@ -438,24 +434,6 @@ __device__ __forceinline__ void he_sync(Lane& L, const RC& c, FMem<MMAX, NS>& M,
         L.wmask |= (1ull << k);
         if (L.lane == k) { L.fal = W.al; L.fbe = W.be; L.fga = W.ga; L.fde = W.de; }
     }
-}
-
-// row/column of entry e of a packed lower triangle (e = r(r+1)/2 + c), one table per workgroup
-template <int MMAX>
-__device__ __forceinline__ unsigned short* rc_table() {
-    __shared__ unsigned short tab[MMAX * (MMAX + 1) / 2];
-    return tab;
-}
-template <int MMAX>
-__device__ __forceinline__ void rc_table_init() {
-    unsigned short* tab = rc_table<MMAX>();
-    for (int e = threadIdx.x; e < MMAX * (MMAX + 1) / 2; e += blockDim.x) {
-        int r = (int)((sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);
-        while (r * (r + 1) / 2 > e) --r;
-        while ((r + 1) * (r + 2) / 2 <= e) ++r;
-        tab[e] = (unsigned short)((r << 8) | (e - r * (r + 1) / 2));
-    }
-    __syncthreads();
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -1224,7 +1202,6 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const RC& c, FMem<MMAX, 
 // per-step set-up and extraction (F4)
 
 struct StepIn { double s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, v_prev; int k_step, have_vprev; };
-struct StepOut { double out[EEPACC_OUT_N]; int status, iters; };
 
 // LDS layout of a block: per wave [FMem][He NS x NS]; the step's base inverse (needed again only by a cold restart)
 // is kept in a per-wave global scratch
@@ -1572,17 +1549,6 @@ __device__ __forceinline__ void fb_step(const DevCfg& C, FMem<MMAX, NS>& M, doub
 #endif
 }
 
-// receding-horizon shift of the working set: stage k takes stage k+1's codes, the last stage and the terminal rows
-// keep theirs
-__device__ __forceinline__ unsigned long long shift_codes(unsigned long long code, int N) {
-    const int lane = lane_id();
-    unsigned lo = (unsigned)code, hi = (unsigned)(code >> 32);
-    unsigned nlo = __shfl_down(lo, 1, 64), nhi = __shfl_down(hi, 1, 64);
-    unsigned long long nxt = ((unsigned long long)nhi << 32) | nlo;
-    if (lane < N - 1) return nxt;
-    return code;
-}
-
 template <int MMAX, int NS>
 __device__ FMem<MMAX, NS>* wave_mem(unsigned char* smem, double*& He) {
     unsigned char* base = smem + wave_bytes(sizeof(FMem<MMAX, NS>), NS) * (threadIdx.x >> 6);
@@ -1595,15 +1561,6 @@ __device__ __forceinline__ double* st_A22(double* s) { return s + 64; }
 __device__ __forceinline__ double* st_D2(double* s) { return s + 128; }
 __device__ __forceinline__ double* st_sp(double* s) { return s + 192; }
 __device__ __forceinline__ double* st_vp(double* s) { return s + 256; }
-
-__device__ __forceinline__ void write_out(double* dst, size_t stride_field, const StepOut& so, int lane) {
-    if (lane < EEPACC_OUT_N) {
-        double val = 0.0;
-#pragma unroll
-        for (int f = 0; f < EEPACC_OUT_N; ++f) if (f == lane) val = so.out[f];
-        dst[(size_t)lane * stride_field] = val;
-    }
-}
 
 // B2: one step for B instances
 template <int MMAX, int NS, int WPB>
@@ -1630,14 +1587,13 @@ k_fbs_step(fbs_step_args a) {
     st_A22(stt)[lane] = A22; st_D2(stt)[lane] = D2;
     if (lane <= N) { st_sp(stt)[lane] = sp; st_vp(stt)[lane] = vp; }
     reinterpret_cast<unsigned long long*>(stt)[lane] = shift_codes(code, N);
-    write_out(a.out + b, (size_t)a.B, so, lane);
+    write_out(a.out, 0, a.B, b, so, lane);
     if (a.s_pred && lane <= N) a.s_pred[(size_t)lane * a.B + b] = sp;
     if (a.v_pred && lane <= N) a.v_pred[(size_t)lane * a.B + b] = vp;
     if (lane == 0) { a.status[b] = so.status; if (a.iters) a.iters[b] = so.iters; }
 }
 
-// B1: closed loop over n_steps for B instances (ABO/RunOpt_FBMPC.m:161-331); work units (instance, chunk of MPC
-// steps) handed out through a device-wide counter as in the ABMPC kernel (eepacc_ab_impl.inc, k_run_abmpc)
+// B1: closed loop over n_steps for B instances (ABO/RunOpt_FBMPC.m:161-331) in work units (run_units, eepacc_units.h)
 template <int MMAX, int NS, int WPB>
 __global__ void __launch_bounds__(64 * WPB, ((NS <= 32 && WPB <= 2) ? 2 : 1))
 k_fbs_run(fbs_run_args a) {
@@ -1649,46 +1605,16 @@ k_fbs_run(fbs_run_args a) {
     double* Hb = a.hb + ((size_t)blockIdx.x * WPB + (threadIdx.x >> 6)) * (NS * NS);
     const int lane = lane_id(), N = C.N, B = a.B;
     const double Ts = C.Tvec[0];
-    const int n_chunks = (a.n_steps + a.chunk_steps - 1) / a.chunk_steps;
-    const int n_units = n_chunks * B;
-    for (int fetch = 0; fetch <= n_units; ++fetch) {
-        int u = 0;
-        if (lane == 0) u = atomicAdd(a.work_counter, 1);
-        u = __builtin_amdgcn_readfirstlane(u);
-        if (u >= n_units || u < 0) break;
-        const int chunk = u / B, b = u - chunk * B;
-        const int kk0 = chunk * a.chunk_steps;
-        const int kk1 = (kk0 + a.chunk_steps < a.n_steps) ? kk0 + a.chunk_steps : a.n_steps;
-        bool failed = false;
-        if (chunk > 0) {
-            int spins = 0;
-            while (__hip_atomic_load(&a.done[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < chunk) {
-                __builtin_amdgcn_s_sleep(32);
-                if (++spins > a.spin_limit) { failed = true; break; }
-                if ((spins & 63) == 0 && __hip_atomic_load(a.err_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        if (failed || __hip_atomic_load(a.err_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-            if (lane == 0) {
-                if (failed) atomicOr(a.err_word, 1);
-                for (int kk = kk0; kk < kk1; ++kk) a.status[(size_t)kk * B + b] = 3;
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-                __hip_atomic_fetch_max(&a.done[b], chunk + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            continue;
-        }
+    run_units(B, a.n_steps, a.chunk_steps, a.work_counter, a.done, a.err_word, a.spin_limit, a.status, a.iters_total,
+              [&](int b, int kk0, int kk1) {
         double* stt = a.state + (size_t)b * kFbsStateDoubles;
         unsigned long long code = 0ull;
         double A22 = 1.0, D2 = 0.0;
-        double s_prev = 0, v_prev = 0, Fm_prev = 0, Fb_prev = 0, v_tv_measured = 0.0, t_0 = 0.0;
+        Carry cs;
         const int idx = lane < N ? lane + 1 : N;
         double ps = 0.0, pv = 0.0;
         if (a.k_start + kk0 > 0) {
-            s_prev = a.carry[0 * (size_t)B + b]; v_prev = a.carry[1 * (size_t)B + b];
-            Fm_prev = a.carry[2 * (size_t)B + b]; Fb_prev = a.carry[3 * (size_t)B + b];
-            v_tv_measured = a.carry[4 * (size_t)B + b]; t_0 = a.carry[5 * (size_t)B + b];
+            cs.load(a.carry, B, b);
             code = reinterpret_cast<unsigned long long*>(stt)[lane];
             A22 = st_A22(stt)[lane]; D2 = st_D2(stt)[lane];
             ps = st_sp(stt)[idx]; pv = st_vp(stt)[idx];
@@ -1697,24 +1623,9 @@ k_fbs_run(fbs_run_args a) {
         for (int kk = kk0; kk < kk1; ++kk) {
             StepIn in;
             in.k_step = a.k_start + kk;
-            if (in.k_step == 0) {                                // :165-183
-                in.s = a.s0[b]; in.v = a.v0[b]; in.a_prev = a.a_m1[b];
-                in.s_tv = a.s_tv[b]; in.v_tv = 0.0; in.a_tv_prev = 0.0;
-                v_tv_measured = 0.0;
-                in.v_prev = 0.0; in.have_vprev = 0;
-            } else {                                             // :184-200
-                double sm, vm;
-                plant_rk4(C, s_prev, v_prev, Fm_prev + Fb_prev, sm, vm);
-                in.s = sm; in.v = vm;
-                in.a_prev = (vm - v_prev) / Ts;
-                in.s_tv = a.s_tv[(size_t)kk * B + b];
-                const double v_tv_prev = v_tv_measured;
-                v_tv_measured = a.v_tv[(size_t)kk * B + b];
-                in.v_tv = v_tv_measured;
-                in.a_tv_prev = (v_tv_measured - v_tv_prev) / Ts;
-                in.v_prev = v_prev; in.have_vprev = 1;
-            }
-            in.t0 = t_0;
+            in.v_prev = in.k_step == 0 ? 0.0 : cs.v;
+            in.have_vprev = in.k_step != 0;
+            measure(C, Ts, in.k_step, kk, B, b, a.s0, a.v0, a.a_m1, a.s_tv, a.v_tv, cs, in);
             StepOut so;
             double sp, vp;
             fb_step<MMAX, NS>(C, M, Hs, Hb, in, A22, D2, code, so, sp, vp, ps, pv);
@@ -1723,28 +1634,16 @@ k_fbs_run(fbs_run_args a) {
             }
             if (kk == kk1 - 1 && lane <= N) { st_sp(stt)[lane] = sp; st_vp(stt)[lane] = vp; }
             code = a.cold ? 0ull : shift_codes(code, N);
-            write_out(a.traj + (size_t)kk * EEPACC_OUT_N * B + b, (size_t)B, so, lane);
+            write_out(a.traj, (size_t)kk * EEPACC_OUT_N, B, b, so, lane);
             if (lane == 0) a.status[(size_t)kk * B + b] = so.status;
             it_total += so.iters;
-            s_prev = so.out[EEPACC_OUT_S]; v_prev = so.out[EEPACC_OUT_V];
-            Fm_prev = so.out[EEPACC_OUT_FM]; Fb_prev = so.out[EEPACC_OUT_FB];
-            t_0 += Ts;                                           // :321
+            cs.advance(so, Ts);
         }
         reinterpret_cast<unsigned long long*>(stt)[lane] = code;
         st_A22(stt)[lane] = A22; st_D2(stt)[lane] = D2;
-        if (lane == 0) {
-            a.carry[0 * (size_t)B + b] = s_prev; a.carry[1 * (size_t)B + b] = v_prev;
-            a.carry[2 * (size_t)B + b] = Fm_prev; a.carry[3 * (size_t)B + b] = Fb_prev;
-            a.carry[4 * (size_t)B + b] = v_tv_measured; a.carry[5 * (size_t)B + b] = t_0;
-            if (a.iters_total) atomicAdd(&a.iters_total[b], it_total);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_fetch_max(&a.done[b], chunk + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+        if (lane == 0) cs.store(a.carry, B, b);
+        return it_total;
+    });
 }
 
 }  // namespace fbs
@@ -1782,14 +1681,10 @@ size_t fbs_smem_bytes(int N) {
 // dynamic LDS a block may ask for: 160 KB per CU minus the kernels' static index table (one ushort per packed entry of P)
 constexpr size_t kFbsLdsBudget = 160 * 1024 - 4608;
 
-static int fbs_run_grid(int N, int n_units, int num_cus) {
-    const size_t smem = fbs_smem_bytes(N);
-    int per_cu = (int)((kFbsLdsBudget) / smem);
-    if (per_cu < 1) per_cu = 1;
-    const int wpb = N > kFNSSmall ? kFWpbLarge : kFWpbSmall;
-    int grid = num_cus * per_cu;
-    const int need = (n_units + wpb - 1) / wpb;
-    return grid > need ? need : grid;
+// blocks of a chip-filling closed-loop launch
+static int fbs_run_max_grid(int N, int num_cus) {
+    const int per_cu = (int)(kFbsLdsBudget / fbs_smem_bytes(N));
+    return num_cus * (per_cu < 1 ? 1 : per_cu);
 }
 
 // scratch for the base inverse of every wave a launch over B instances can have (step: one wave per instance;
@@ -1797,7 +1692,7 @@ static int fbs_run_grid(int N, int n_units, int num_cus) {
 size_t fbs_hb_doubles(int N, int B, int num_cus) {
     const int ns = N > kFNSSmall ? kFNSLarge : kFNSSmall, wpb = N > kFNSSmall ? kFWpbLarge : kFWpbSmall;
     const size_t step_waves = (size_t)((B + wpb - 1) / wpb) * wpb;
-    const size_t run_waves = (size_t)fbs_run_grid(N, 0x7fffffff / 2, num_cus) * wpb;
+    const size_t run_waves = (size_t)fbs_run_max_grid(N, num_cus) * wpb;
     return (step_waves > run_waves ? step_waves : run_waves) * ns * ns;
 }
 
@@ -1824,22 +1719,18 @@ hipError_t launch_fbs_step(const fbs_step_args& a, int N, hipStream_t stream) {
     return hipGetLastError();
 }
 
-hipError_t launch_fbs_run(const fbs_run_args& a, int N, int num_cus, hipStream_t stream) {
-    hipError_t e = hipMemsetAsync(a.work_counter, 0, sizeof(int), stream);
+hipError_t launch_fbs_run(fbs_run_args a, int N, int num_cus, hipStream_t stream) {
+    const bool large = N > kFNSSmall;
+    UnitsLaunch ul;
+    hipError_t e = begin_units(a.work_counter, a.done, a.iters_total, a.B, a.n_steps, a.chunk_steps,
+                               large ? kFWpbLarge : kFWpbSmall, fbs_run_max_grid(N, num_cus), stream, ul);
     if (e != hipSuccess) return e;
-    e = hipMemsetAsync(a.done, 0, sizeof(int) * (size_t)a.B, stream);
-    if (e != hipSuccess) return e;
-    if (a.iters_total) {
-        e = hipMemsetAsync(a.iters_total, 0, sizeof(int32_t) * (size_t)a.B, stream);
-        if (e != hipSuccess) return e;
-    }
+    a.spin_limit = ul.spin_limit;
     const size_t smem = fbs_smem_bytes(N);
-    const int n_units = ((a.n_steps + a.chunk_steps - 1) / a.chunk_steps) * a.B;
-    const int grid = fbs_run_grid(N, n_units, num_cus);
-    if (N > kFNSSmall)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(fbs::k_fbs_run<kFMMaxLarge, kFNSLarge, kFWpbLarge>), dim3(grid), dim3(64 * kFWpbLarge), smem, stream, a);
+    if (large)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(fbs::k_fbs_run<kFMMaxLarge, kFNSLarge, kFWpbLarge>), dim3(ul.grid), dim3(64 * kFWpbLarge), smem, stream, a);
     else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(fbs::k_fbs_run<kFMMaxSmall, kFNSSmall, kFWpbSmall>), dim3(grid), dim3(64 * kFWpbSmall), smem, stream, a);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(fbs::k_fbs_run<kFMMaxSmall, kFNSSmall, kFWpbSmall>), dim3(ul.grid), dim3(64 * kFWpbSmall), smem, stream, a);
     return hipGetLastError();
 }
 

@@ -14,6 +14,7 @@
 #include <stdlib.h>
 #include "eepacc_device.h"
 #include "eepacc_stage.h"
+#include "eepacc_units.h"
 #include "../../include/eepacc.h"
 
 #define EEPACC_IMPL_NS nomb
@@ -53,21 +54,12 @@
 namespace eepacc {
 
 // working-set capacity: rigid rows are linearly independent, so m <= N (+ terminal rows)
-#ifndef EEPACC_MMAX_SMALL
-#define EEPACC_MMAX_SMALL 34
-#endif
-constexpr int kMMaxSmall = EEPACC_MMAX_SMALL, kNSSmall = 32;     // N <= 32: 8 waves / CU (4 per block, 2 blocks)
-constexpr int kBlocksSmall = kMMaxSmall <= 32 ? 3 : 2;
+constexpr int kMMaxSmall = 34, kNSSmall = 32;     // N <= 32: 8 waves / CU (4 per block, 2 blocks)
+constexpr int kBlocksSmall = 2;
 // N <= 63: 44.6 KB of LDS per wave (He packed 16.6 KB, P 17.7 KB), 3 waves per CU (round 2: a full He of 32 KB allowed 2).
-// Trading working-set capacity for more does not work: with a capacity of 50 rigid rows (-DEEPACC_MMAX_LARGE=50) the S2
-// workload at N = 60 overflows the working set on 15 % of the steps (measured), so the full N + 2 stays.
-#ifndef EEPACC_MMAX_LARGE
-#define EEPACC_MMAX_LARGE 66
-#endif
-#ifndef EEPACC_WPB_LARGE
-#define EEPACC_WPB_LARGE 3
-#endif
-constexpr int kMMaxLarge = EEPACC_MMAX_LARGE, kNSLarge = 64, kWpbLarge = EEPACC_WPB_LARGE;
+// Trading working-set capacity for more does not work: with a capacity of 50 rigid rows the S2 workload at N = 60
+// overflows the working set on 15 % of the steps (measured), so the full N + 2 stays.
+constexpr int kMMaxLarge = 66, kNSLarge = 64, kWpbLarge = 3;
 constexpr int kChunkStepsDefault = nomb::kChunkStepsDefault;
 
 #ifdef EEPACC_AB_TIMING
@@ -128,29 +120,17 @@ hipError_t launch_run_abmpc(const DevCfg* dC, int N, int variant, int B, int k_s
                             double* carry, unsigned long long* codes, double* traj,
                             int32_t* status, int32_t* iters_total, int* work_counter, int* done, int* err_word, int num_cus,
                             hipStream_t stream) {
-    hipError_t e = hipMemsetAsync(work_counter, 0, sizeof(int), stream);
+    const bool large = N > kNSSmall;
+    const int kChunkSteps = pick_chunk_steps(n_steps, B, num_cus * (large ? kWpbLarge : 4 * kBlocksSmall));
+    // one chip-filling wave of blocks: LDS admits 8 (small) / 3 (large) waves per CU
+    UnitsLaunch ul;
+    hipError_t e = begin_units(work_counter, done, iters_total, B, n_steps, kChunkSteps, large ? kWpbLarge : 4,
+                               num_cus * (large ? 1 : kBlocksSmall), stream, ul);
     if (e != hipSuccess) return e;
-    e = hipMemsetAsync(done, 0, sizeof(int) * (size_t)B, stream);
-    if (e != hipSuccess) return e;
-    if (iters_total) {
-        e = hipMemsetAsync(iters_total, 0, sizeof(int32_t) * (size_t)B, stream);
-        if (e != hipSuccess) return e;
-    }
-    const int kChunkSteps = pick_chunk_steps(n_steps, B, num_cus * (N > kNSSmall ? kWpbLarge : 4 * kBlocksSmall));
-    // bound of the inter-unit spin wait (a debug hook lowers it to exercise the failure path)
-    int spin_limit = 1 << 26;
-    if (const char* ev = getenv("EEPACC_DEBUG_SPIN_LIMIT")) spin_limit = atoi(ev);
-    const int n_units = ((n_steps + kChunkSteps - 1) / kChunkSteps) * B;
-    // one chip-filling wave of blocks: LDS admits 8 (small) / 2 (large) waves per CU
-    if (N > kNSSmall) {
-        int grid = num_cus * 1, need = (n_units + kWpbLarge - 1) / kWpbLarge;
-        if (grid > need) grid = need;
-        EEPACC_LAUNCH(k_run_abmpc, kMMaxLarge, kNSLarge, kWpbLarge, grid, dC, B, k_start, n_steps, s0, v0, a_m1, s_tv, v_tv, carry, codes, traj, status, iters_total, work_counter, done, kChunkSteps, err_word, spin_limit);
-    } else {
-        int grid = num_cus * kBlocksSmall, need = (n_units + 3) / 4;
-        if (grid > need) grid = need;
-        EEPACC_LAUNCH(k_run_abmpc, kMMaxSmall, kNSSmall, 4, grid, dC, B, k_start, n_steps, s0, v0, a_m1, s_tv, v_tv, carry, codes, traj, status, iters_total, work_counter, done, kChunkSteps, err_word, spin_limit);
-    }
+    if (large)
+        EEPACC_LAUNCH(k_run_abmpc, kMMaxLarge, kNSLarge, kWpbLarge, ul.grid, dC, B, k_start, n_steps, s0, v0, a_m1, s_tv, v_tv, carry, codes, traj, status, iters_total, work_counter, done, kChunkSteps, err_word, ul.spin_limit);
+    else
+        EEPACC_LAUNCH(k_run_abmpc, kMMaxSmall, kNSSmall, 4, ul.grid, dC, B, k_start, n_steps, s0, v0, a_m1, s_tv, v_tv, carry, codes, traj, status, iters_total, work_counter, done, kChunkSteps, err_word, ul.spin_limit);
     return hipGetLastError();
 }
 

@@ -6,7 +6,7 @@
 namespace eepacc {
 namespace wv {
 
-#define EEPACC_WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
+#define WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 

@@ -449,20 +449,23 @@ def test_host_wrapper_equals_device_path(torch_mod, lead_trace):
         assert np.abs(th[:, OUT[nm], 0] - G[nm + "_opt"][:n]).max() < TOL[nm], nm
 
 
-def test_handoff_timeout_is_reported(torch_mod, lead_trace, monkeypatch):
+@pytest.mark.parametrize("ctrl", ["abmpc", "fbmpc"])
+def test_handoff_timeout_is_reported(ctrl, torch_mod, lead_trace, monkeypatch):
     """Debug hook EEPACC_DEBUG_SPIN_LIMIT=0: a work unit whose predecessor is not yet published gives up at
     once.  The unit must not continue from stale state: its steps carry status 3, the rest of the launch is
-    abandoned and eepacc_synchronize reports EEPACC_EDEVICE; after a reset the handle works again."""
+    abandoned and eepacc_synchronize reports EEPACC_EDEVICE; after a reset the handle works again.  Both closed-loop
+    kernels (ABMPC, structured FBMPC) hand their work units off through the same code."""
     from eepacc_mpc_casadi_matlab_amd.engine import EepaccError
     OPT, V, _, _ = make_case("ABO", 20)
     B, n_steps = 64, 80
     sc = make_s2(B, n_steps, lead_trace["V_TO_2Hz"], seed=5)
     eng = _engine(OPT, V, B)
-    good, gst = eng.run_abmpc(sc["s0"], sc["v0"], sc["a_minus1"], sc["s_tv"], sc["v_tv"])
+    run = getattr(eng, "run_" + ctrl)
+    good, gst = run(sc["s0"], sc["v0"], sc["a_minus1"], sc["s_tv"], sc["v_tv"])
     eng.synchronize()
     good = good.cpu().numpy()
     monkeypatch.setenv("EEPACC_DEBUG_SPIN_LIMIT", "0")
-    traj, status = eng.run_abmpc(sc["s0"], sc["v0"], sc["a_minus1"], sc["s_tv"], sc["v_tv"])
+    traj, status = run(sc["s0"], sc["v0"], sc["a_minus1"], sc["s_tv"], sc["v_tv"])
     st = status.cpu().numpy()
     if (st == 3).any():
         with pytest.raises(EepaccError):
@@ -477,6 +480,9 @@ def test_handoff_timeout_is_reported(torch_mod, lead_trace, monkeypatch):
     else:       # every predecessor happened to be published in time
         eng.synchronize()
     monkeypatch.delenv("EEPACC_DEBUG_SPIN_LIMIT")
-    again, ast = eng.run_abmpc(sc["s0"], sc["v0"], sc["a_minus1"], sc["s_tv"], sc["v_tv"])
+    again, ast = run(sc["s0"], sc["v0"], sc["a_minus1"], sc["s_tv"], sc["v_tv"])
     eng.synchronize()
-    assert np.array_equal(again.cpu().numpy(), good) and int(ast.cpu().numpy().sum()) == 0
+    ast = ast.cpu().numpy()
+    assert np.array_equal(again.cpu().numpy(), good) and np.array_equal(ast, gst.cpu().numpy())
+    # ABMPC solves every step of this scenario; FBMPC meets infeasible measured states (status 1), never status 3
+    assert int(ast.sum()) == 0 if ctrl == "abmpc" else not (ast == 3).any()
