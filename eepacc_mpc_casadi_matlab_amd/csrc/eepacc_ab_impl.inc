@@ -1,8 +1,8 @@
-// eepacc_ab_impl.inc -- device code of the ABMPC kernels.  Included four times by eepacc_kernels.hip: once
+// eepacc_ab_impl.inc -- device code of the ABMPC kernels.  Included five times by eepacc_kernels.hip: once
 // per value of EEPACC_IMPL_MB (move blocking compiled out / in), once with EEPACC_IMPL_BL (the baseline
-// controller's row grouping, CreateQP_BL.m: one slack for all soft rows) and once with EEPACC_IMPL_ICE (the ICE-map
-// fuel term, whose Hessian is built and inverted every step), each time into its own namespace, so that the
-// default path carries no register or instruction cost for the variants.
+// controller's row grouping, CreateQP_BL.m: one slack for all soft rows) and twice with EEPACC_IMPL_ICE (the ICE-map
+// fuel term, whose Hessian is built and inverted every step; without / with move blocking), each time into its own
+// namespace, so that the default path carries no register or instruction cost for the variants.
 namespace eepacc {
 namespace EEPACC_IMPL_NS {
 using namespace wv;
@@ -1325,6 +1325,98 @@ __device__ void force_allocation(const DevCfg& C, double s_meas, double v_meas, 
     a_real = (Fm + Fb + F_r) / C.m / C.lambda;
 }
 
+// ICE-map variant with move blocking: Hbar = E'HE in the leader-indexed layout the host builds for the withmb kernels
+// (eepacc_capi.cpp): on each leader row / column H summed over the block, identity on the non-leader rows.  Lane b, the
+// leader of a block, forms the entries (a, b) of every leader a (a >= b when packed) from the block pair and then writes
+// unit / zero on the pair's non-leader rows and columns; the block pairs partition the matrix, so the lanes work in place.
+template <int NS>
+__device__ __forceinline__ void he_mb_fold(double* He, const Cfg& c, int N, int lane) {
+    auto at = [](int i, int j) { return kPackedHe<NS> ? (i >= j ? he_tri(i) + j : he_tri(j) + i) : i * NS + j; };
+    if (lane < N && c.mb_lead[lane] == lane) {
+        const int b = lane, be = c.mb_end[b];
+        for (int a = kPackedHe<NS> ? b : 0; a < N; a = c.mb_end[a] + 1) {
+            const int ae = c.mb_end[a];
+            double s = 0.0;
+            for (int i = a; i <= ae; ++i)
+                for (int j = b; j <= be; ++j) s += He[at(i, j)];
+            for (int i = a; i <= ae; ++i)
+                for (int j = b; j <= be; ++j)
+                    if (!kPackedHe<NS> || i >= j) He[at(i, j)] = (i == a && j == b) ? s : (i == j ? 1.0 : 0.0);
+        }
+    }
+    WSYNC();
+}
+
+// Packed lower triangle of NS = 64 spread evenly over the lanes: column p = lane % 32 (64 - p entries) is paired with
+// column 63 - p (p + 1 entries); of the pair's 65 entries, lanes 0-31 take the first 33 and lanes 32-63 the other 32.
+// Entry u of this lane is (i, j); false where the lane has no entry u.
+__device__ __forceinline__ bool he_pair_entry(int lane, int u, int& i, int& j) {
+    const int p = lane & 31, t = (lane >> 5) * 33 + u;
+    if (t < 64 - p) { i = p + t; j = p; } else { i = t - 1; j = 63 - p; }
+    return t <= 64;
+}
+constexpr int kPairEntries = 33;
+
+// ICE-map Hessian at NS = 64 (the small path in ab_step, on the packed triangle): build H from the closed forms into He
+// (M.ws = Rsuf, the suffix sums of cq_k), fold it for move blocking, invert it in place by symmetric sweeps (the pivot row
+// staged in M.wa) and write the negated result, the step's base inverse, to the wave's scratch Hb (full N x N).
+// Returns 1 when a pivot is not positive (status 2).
+template <int MMAX, int NS>
+__device__ __forceinline__ int ice_build_invert_packed(const DevCfg& C, const Cfg& c, WaveMem<MMAX, NS>& M, double* He,
+                                                       double* __restrict__ Hb, int N, int lane) {
+    static_assert(NS == 64, "the lane pairing covers the 64 x 64 triangle");
+    if (lane < NS) M.wv[lane] = lane < N ? C.Tvec[lane] : 0.0;
+    WSYNC();
+    // jerk weights q_k = 2 w_j / T_k^2 of the two columns this lane's entries lie in (and of the stage after each)
+    const int p = lane & 31;
+    auto qj = [&](int k) { return k < N ? 2.0 * C.w_j / (M.wv[k] * M.wv[k]) : 0.0; };
+    const double qA0 = qj(p), qA1 = qj(p + 1), qB0 = qj(63 - p), qB1 = qj(64 - p);
+#pragma unroll 1
+    for (int u = 0; u < kPairEntries; ++u) {
+        int i, j;
+        if (!he_pair_entry(lane, u, i, j)) continue;
+        double hv = 0.0;
+        if (i < N) {
+            const double q0 = j == p ? qA0 : qB0, q1 = j == p ? qA1 : qB1;
+            hv = 2.0 * M.wv[i] * M.wv[j] * M.ws[i];
+            if (i == j) hv += 2.0 * C.w_a + q0 + q1;
+            else if (i == j + 1) hv -= q1;
+        }
+        He[he_tri(i) + j] = hv;
+    }
+    WSYNC();
+    if (kMoveBlocking && c.mb_len != 0) he_mb_fold<NS>(He, c, N, lane);
+    int bad = 0;
+    for (int k = 0; k < N; ++k) {
+        const double d = He[he_tri(k) + k];
+        if (!(d > 0.0)) { bad = 1; break; }
+        const double inv = 1.0 / d;
+        if (lane < NS) M.wa[lane] = lane < N ? He[lane >= k ? he_tri(lane) + k : he_tri(k) + lane] : 0.0;
+        WSYNC();
+        const double fA = M.wa[p] * inv, fB = M.wa[63 - p] * inv;
+#pragma unroll 3
+        for (int u = 0; u < kPairEntries; ++u) {
+            int i, j;
+            if (!he_pair_entry(lane, u, i, j) || i >= N) continue;
+            const int e = he_tri(i) + j;
+            const double f = j == p ? fA : fB, ck = M.wa[i], old = He[e];
+            He[e] = (i == k) ? (j == k ? -inv : f) : (j == k ? ck * inv : fma(-ck, f, old));
+        }
+        WSYNC();
+    }
+#pragma unroll 1
+    for (int u = 0; u < kPairEntries; ++u) {
+        int i, j;
+        if (!he_pair_entry(lane, u, i, j) || i >= N) continue;
+        const int e = he_tri(i) + j;
+        const double x = -He[e];
+        He[e] = x;
+        Hb[i * N + j] = x;                   // base inverse of this step (cold restarts re-read it)
+        Hb[j * N + i] = x;
+    }
+    return bad;
+}
+
 // One ABMPC step for the wave's instance (ABO/RunOpt_ABMPC.m:193-329).  `code` carries the
 // working set between steps (already shifted by the caller).
 template <int MMAX, int NS>
@@ -1431,7 +1523,7 @@ __device__ __forceinline__ void ab_step(const DevCfg& C, WaveMem<MMAX, NS>& M, d
     double grad_total = 0.0;
     const double* Hbase = C.Hinv;
     int h_bad = 0;
-    if constexpr (kIce && !kPackedHe<NS>) {
+    if constexpr (kIce) {
         // ICE-map fuel term (CreateQP_AB.m:154-159): stage k carries the curvature 2 cq_k on v_k and the linear terms
         // lv_k v_k + la_k a_k with the gear ratio tau_est(k) = LUTgearshift(v_est(k)) (LUTgearshift.m:17-41,
         // EstimateRouteAndComfortBounds.m:63-66).  v_k = v_0 + sum_{i<k} T_i a_i, so
@@ -1448,52 +1540,57 @@ __device__ __forceinline__ void ab_step(const DevCfg& C, WaveMem<MMAX, NS>& M, d
         if (stg) { L.g0 = L.T * Wsuf + lak; if (lane == 0) L.g0 -= 2.0 * C.w_j / L.T * in.a_prev; }
         if (lane <= N) M.ws[lane] = Rsuf;
         WSYNC();
-        if (lane < NS) {
-            const int j = lane;
-            const double Tj = j < N ? C.Tvec[j] : 0.0;
-            const double qjj = j < N ? 2.0 * C.w_j / (Tj * Tj) : 0.0;
-            const double qjn = (j + 1 < N) ? 2.0 * C.w_j / (C.Tvec[j + 1] * C.Tvec[j + 1]) : 0.0;
-            for (int i = 0; i < NS; ++i) {
-                double hv = 0.0;
-                if (i < N && j < N) {
-                    hv = 2.0 * C.Tvec[i] * Tj * (i > j ? M.ws[i] : Rsuf);
-                    if (i == j) hv += 2.0 * C.w_a + qjj + qjn;
-                    else if (i == j - 1) hv -= qjj;
-                    else if (i == j + 1) hv -= qjn;
+        if constexpr (kPackedHe<NS>) {
+            h_bad = ice_build_invert_packed<MMAX, NS>(C, c, M, Hs, Hb, N, lane);
+        } else {
+            if (lane < NS) {
+                const int j = lane;
+                const double Tj = j < N ? C.Tvec[j] : 0.0;
+                const double qjj = j < N ? 2.0 * C.w_j / (Tj * Tj) : 0.0;
+                const double qjn = (j + 1 < N) ? 2.0 * C.w_j / (C.Tvec[j + 1] * C.Tvec[j + 1]) : 0.0;
+                for (int i = 0; i < NS; ++i) {
+                    double hv = 0.0;
+                    if (i < N && j < N) {
+                        hv = 2.0 * C.Tvec[i] * Tj * (i > j ? M.ws[i] : Rsuf);
+                        if (i == j) hv += 2.0 * C.w_a + qjj + qjn;
+                        else if (i == j - 1) hv -= qjj;
+                        else if (i == j + 1) hv -= qjn;
+                    }
+                    Hs[i * NS + j] = hv;
                 }
-                Hs[i * NS + j] = hv;
             }
-        }
-        WSYNC();
-        {
-            // all 64 lanes work: lane l updates rows [r0, r0 + RPL) of column l % NS (NS = 32: two lanes per column)
-            constexpr int HALVES = 64 / NS, RPL = NS / HALVES;
-            const int jcol = lane & (NS - 1), r0 = (lane / NS) * RPL;
-            double* col = Hs + jcol;
-            for (int k = 0; k < N; ++k) {
-                const double d = Hs[k * NS + k];
-                if (!(d > 0.0)) { h_bad = 1; break; }
-                const double inv = 1.0 / d;
-                if (lane < NS) M.wa[lane] = (lane < N) ? Hs[k * NS + lane] : 0.0;
-                WSYNC();
-                const double hkj = M.wa[jcol];
-                const double f = hkj * inv;
-                const bool piv = jcol == k;
+            WSYNC();
+            if (kMoveBlocking && c.mb_len != 0) he_mb_fold<NS>(Hs, c, N, lane);
+            {
+                // all 64 lanes work: lane l updates rows [r0, r0 + RPL) of column l % NS (NS = 32: two lanes per column)
+                constexpr int HALVES = 64 / NS, RPL = NS / HALVES;
+                const int jcol = lane & (NS - 1), r0 = (lane / NS) * RPL;
+                double* col = Hs + jcol;
+                for (int k = 0; k < N; ++k) {
+                    const double d = Hs[k * NS + k];
+                    if (!(d > 0.0)) { h_bad = 1; break; }
+                    const double inv = 1.0 / d;
+                    if (lane < NS) M.wa[lane] = (lane < N) ? Hs[k * NS + lane] : 0.0;
+                    WSYNC();
+                    const double hkj = M.wa[jcol];
+                    const double f = hkj * inv;
+                    const bool piv = jcol == k;
 #pragma unroll
-                for (int ii = 0; ii < RPL; ++ii) {
-                    const int i = r0 + ii;
-                    const double ck = M.wa[i], old = col[i * NS];
-                    const double upd = piv ? ck * inv : fma(-ck, f, old);
-                    col[i * NS] = (i == k) ? (piv ? -inv : f) : upd;
+                    for (int ii = 0; ii < RPL; ++ii) {
+                        const int i = r0 + ii;
+                        const double ck = M.wa[i], old = col[i * NS];
+                        const double upd = piv ? ck * inv : fma(-ck, f, old);
+                        col[i * NS] = (i == k) ? (piv ? -inv : f) : upd;
+                    }
+                    WSYNC();
                 }
-                WSYNC();
             }
-        }
-        for (int e = lane; e < NS * NS; e += 64) {
-            const double x = -Hs[e];
-            Hs[e] = x;
-            const int i = e / NS, j = e % NS;
-            if (i < N && j < N) Hb[i * N + j] = x;           // base inverse of this step (cold restarts re-read it)
+            for (int e = lane; e < NS * NS; e += 64) {
+                const double x = -Hs[e];
+                Hs[e] = x;
+                const int i = e / NS, j = e % NS;
+                if (i < N && j < N) Hb[i * N + j] = x;           // base inverse of this step (cold restarts re-read it)
+            }
         }
         Hbase = Hb;
     } else {

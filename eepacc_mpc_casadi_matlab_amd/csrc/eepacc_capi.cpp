@@ -98,8 +98,8 @@ static bool spd_inverse(std::vector<long double>& A, int n) {
     return true;
 }
 
-// kernel variant of a handle: 0 plain, 1 blocked moves, 2 baseline controller
-static int ab_variant(const DevCfg& C) { return C.bl_mode ? 2 : (C.ab_fuel_term == 2 ? 3 : (C.mb_any ? 1 : 0)); }
+// kernel variant of a handle: 0 plain, 1 blocked moves, 2 baseline controller, 3 ICE-map fuel term, 4 ICE-map with blocked moves
+static int ab_variant(const DevCfg& C) { return C.bl_mode ? 2 : (C.ab_fuel_term == 2 ? (C.mb_any ? 4 : 3) : (C.mb_any ? 1 : 0)); }
 
 static int build_cfg(const eepacc_settings* S, const eepacc_vehicle* V, DevCfg& C, std::vector<double>& Hinv) {
     memset(&C, 0, sizeof(C));
@@ -120,10 +120,8 @@ static int build_cfg(const eepacc_settings* S, const eepacc_vehicle* V, DevCfg& 
     if (S->N_integratePlant < 1) return fail(EEPACC_EINVAL, "N_integratePlant < 1");
     if (S->ab_fuel_term < 0 || S->ab_fuel_term > 2) return fail(EEPACC_EINVAL, "ab_fuel_term must be 0, 1 or 2");
     if (S->ab_fuel_term == 2 && !S->bl_mode) {
-        // ICE-map fuel term (CreateQP_AB.m:154-159): step-varying Hessian, built and inverted in LDS by its own kernel variant
-        if (N > 32) return fail(EEPACC_ENOTSUP, "ab_fuel_term == 2 (ICE-map fuel term) is built for N_hor <= 32");
-        for (int k = 0; S->Mb && k < N; ++k)
-            if (S->Mb[k] != 0) return fail(EEPACC_ENOTSUP, "ab_fuel_term == 2 (ICE-map fuel term) is not built with move blocking");
+        // ICE-map fuel term (CreateQP_AB.m:154-159): step-varying Hessian, built (folded for Mb) and inverted in LDS by its
+        // own kernel variant, at every N and with or without move blocking
         if (!(V->tau_fd > 0.0) || !(V->eta_drive > 0.0) || !(V->R_w > 0.0))
             return fail(EEPACC_EINVAL, "ab_fuel_term == 2 needs V.tau_fd, V.eta_drive, V.R_w > 0 (SetVehicleParameters.m:92,100-101)");
         for (int g2 = 0; g2 < 8; ++g2) if (!(V->tau_gb[g2] > 0.0)) return fail(EEPACC_EINVAL, "ab_fuel_term == 2 needs positive gear ratios V.tau_gb");

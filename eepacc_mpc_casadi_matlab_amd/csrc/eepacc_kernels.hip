@@ -38,11 +38,18 @@
 #undef EEPACC_IMPL_MB
 #undef EEPACC_IMPL_BL
 
-// ICE-map fuel term (CreateQP_AB.m:154-159): step-varying Hessian, built and inverted in LDS every step
-#define EEPACC_IMPL_NS ice
-#define EEPACC_IMPL_MB false
+// ICE-map fuel term (CreateQP_AB.m:154-159): step-varying Hessian, built and inverted in LDS every step; without and with
+// move blocking (icemb folds the Hessian into E'HE before the inversion).  Two namespaces: compiled into one, the blocking
+// code costs the small ICE kernel 18 % of its throughput at N = 30 even where the handle has no Mb.
 #define EEPACC_IMPL_BL false
 #define EEPACC_IMPL_ICE true
+#define EEPACC_IMPL_NS ice
+#define EEPACC_IMPL_MB false
+#include "eepacc_ab_impl.inc"
+#undef EEPACC_IMPL_NS
+#undef EEPACC_IMPL_MB
+#define EEPACC_IMPL_NS icemb
+#define EEPACC_IMPL_MB true
 #include "eepacc_ab_impl.inc"
 #undef EEPACC_IMPL_NS
 #undef EEPACC_IMPL_MB
@@ -80,7 +87,8 @@ size_t ab_smem_bytes(int N) {
 #define EEPACC_LAUNCH_NS(NSP, KERNEL, MM, NSV, WPB, GRID, ...)                                                \
     hipLaunchKernelGGL(HIP_KERNEL_NAME(NSP::KERNEL<MM, NSV, WPB>), dim3(GRID), dim3(64 * WPB), ab_smem_bytes(N), stream, __VA_ARGS__)
 #define EEPACC_LAUNCH(KERNEL, MM, NSV, WPB, GRID, ...)                                                        \
-    do { if (variant == 3) EEPACC_LAUNCH_NS(ice, KERNEL, MM, NSV, WPB, GRID, __VA_ARGS__);                    \
+    do { if (variant == 4) EEPACC_LAUNCH_NS(icemb, KERNEL, MM, NSV, WPB, GRID, __VA_ARGS__);                  \
+         else if (variant == 3) EEPACC_LAUNCH_NS(ice, KERNEL, MM, NSV, WPB, GRID, __VA_ARGS__);               \
          else if (variant == 2) EEPACC_LAUNCH_NS(blc, KERNEL, MM, NSV, WPB, GRID, __VA_ARGS__);               \
          else if (variant == 1) EEPACC_LAUNCH_NS(withmb, KERNEL, MM, NSV, WPB, GRID, __VA_ARGS__);            \
          else EEPACC_LAUNCH_NS(nomb, KERNEL, MM, NSV, WPB, GRID, __VA_ARGS__); } while (0)
@@ -100,10 +108,13 @@ int pick_chunk_steps(int n_steps, int B, int resident_waves) {
 }
 
 // per-wave scratch of the ICE variant (base inverse of the step): one NS x NS block for every wave a launch can have
+// (the kernels index it by blockIdx.x * WPB + wave: k_ab_step has ceil(B / WPB) blocks, k_run_abmpc at most one
+// chip-filling wave of blocks, see launch_run_abmpc)
 size_t ab_hb_doubles(int N, int B, int num_cus) {
-    if (N > kNSSmall) return 0;
-    const size_t step_waves = (size_t)((B + 3) / 4) * 4, run_waves = (size_t)num_cus * kBlocksSmall * 4;
-    return (step_waves > run_waves ? step_waves : run_waves) * kNSSmall * kNSSmall;
+    const bool large = N > kNSSmall;
+    const size_t wpb = large ? kWpbLarge : 4, ns = large ? kNSLarge : kNSSmall;
+    const size_t step_waves = (size_t)((B + wpb - 1) / wpb) * wpb, run_waves = (size_t)num_cus * (large ? 1 : kBlocksSmall) * wpb;
+    return (step_waves > run_waves ? step_waves : run_waves) * ns * ns;
 }
 
 hipError_t launch_ab_step(const DevCfg* dC, int N, int variant, int B, const double* s, const double* v, const double* a_prev,
@@ -141,7 +152,7 @@ hipError_t launch_postprocess(const DevCfg* dC, int B, int n_steps, const double
 }
 
 hipError_t set_max_smem() {
-    const void* fns[16] = {reinterpret_cast<const void*>(&nomb::k_ab_step<kMMaxSmall, kNSSmall, 4>),
+    const void* fns[20] = {reinterpret_cast<const void*>(&nomb::k_ab_step<kMMaxSmall, kNSSmall, 4>),
                           reinterpret_cast<const void*>(&nomb::k_ab_step<kMMaxLarge, kNSLarge, kWpbLarge>),
                           reinterpret_cast<const void*>(&nomb::k_run_abmpc<kMMaxSmall, kNSSmall, 4>),
                           reinterpret_cast<const void*>(&nomb::k_run_abmpc<kMMaxLarge, kNSLarge, kWpbLarge>),
@@ -156,8 +167,12 @@ hipError_t set_max_smem() {
                           reinterpret_cast<const void*>(&ice::k_ab_step<kMMaxSmall, kNSSmall, 4>),
                           reinterpret_cast<const void*>(&ice::k_ab_step<kMMaxLarge, kNSLarge, kWpbLarge>),
                           reinterpret_cast<const void*>(&ice::k_run_abmpc<kMMaxSmall, kNSSmall, 4>),
-                          reinterpret_cast<const void*>(&ice::k_run_abmpc<kMMaxLarge, kNSLarge, kWpbLarge>)};
-    for (int i = 0; i < 16; ++i) {
+                          reinterpret_cast<const void*>(&ice::k_run_abmpc<kMMaxLarge, kNSLarge, kWpbLarge>),
+                          reinterpret_cast<const void*>(&icemb::k_ab_step<kMMaxSmall, kNSSmall, 4>),
+                          reinterpret_cast<const void*>(&icemb::k_ab_step<kMMaxLarge, kNSLarge, kWpbLarge>),
+                          reinterpret_cast<const void*>(&icemb::k_run_abmpc<kMMaxSmall, kNSSmall, 4>),
+                          reinterpret_cast<const void*>(&icemb::k_run_abmpc<kMMaxLarge, kNSLarge, kWpbLarge>)};
+    for (int i = 0; i < 20; ++i) {
         // 160 KB of LDS per CU minus the kernel's static index table (one ushort per packed entry of P)
         const int mm = (i & 1) ? kMMaxLarge : kMMaxSmall;
         const int dyn = 160 * 1024 - ((mm * (mm + 1) / 2 * 2 + 255) & ~255);
