@@ -3,6 +3,8 @@
 // controller's row grouping, CreateQP_BL.m: one slack for all soft rows) and twice with EEPACC_IMPL_ICE (the ICE-map
 // fuel term, whose Hessian is built and inverted every step; without / with move blocking), each time into its own
 // namespace, so that the default path carries no register or instruction cost for the variants.
+// The tables of the active-set method (the inverse He of the effective Hessian, the inverse Schur block P of the working
+// set) are maintained by eepacc_schur.h, which the FBMPC kernels share; it is included once, outside these namespaces.
 namespace eepacc {
 namespace EEPACC_IMPL_NS {
 using namespace wv;
@@ -177,60 +179,10 @@ __device__ __forceinline__ void hom_traj(const Lane& L, double x, double& sh, do
     sh = scan_excl(inc);
 }
 
-// Storage of the per-wave inverse He.  NS <= 32: full NS x NS (zero padded), every load of a product has an immediate
-// offset.  NS = 64: packed lower triangle (entry (i,j), i >= j, at i(i+1)/2 + j): 16.6 KB instead of 32 KB, which is
-// what lets a third wave onto a CU at N = 60.  Lane k reads (i,k) for i >= k and (k,i) for i < k; the triangular
-// numbers are a permutation modulo 32, so both access patterns spread over the LDS banks.
+// Storage of the per-wave inverse He (layouts and products: eepacc_schur.h).  NS <= 32: full NS x NS (zero padded).
+// NS = 64: packed lower triangle: 16.6 KB instead of 32 KB, which is what lets a third wave onto a CU at N = 60.
 template <int NS> constexpr bool kPackedHe = NS > 32;
 template <int NS> constexpr int kHeDoubles = kPackedHe<NS> ? NS * (NS + 1) / 2 : NS * NS;
-__device__ __forceinline__ int he_tri(int i) { return i * (i + 1) / 2; }
-
-// out_k = sum_i Hinv[i][k] * yv[i]   (Hinv symmetric, table in LDS, yv in LDS)
-template <int NS>
-__device__ __forceinline__ double hinv_mul(const double* Hs, const double* yv, int N, int lane) {
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-    if constexpr (kPackedHe<NS>) {
-        const int k = lane & (NS - 1), tk = he_tri(k);
-#pragma unroll
-        for (int i = 0; i < NS; i += 4) {
-            a0 = fma(Hs[(i + 0) >= k ? he_tri(i + 0) + k : tk + (i + 0)], yv[i + 0], a0);
-            a1 = fma(Hs[(i + 1) >= k ? he_tri(i + 1) + k : tk + (i + 1)], yv[i + 1], a1);
-            a2 = fma(Hs[(i + 2) >= k ? he_tri(i + 2) + k : tk + (i + 2)], yv[i + 2], a2);
-            a3 = fma(Hs[(i + 3) >= k ? he_tri(i + 3) + k : tk + (i + 3)], yv[i + 3], a3);
-        }
-    } else {
-        const double* col = Hs + (lane & (NS - 1));
-#pragma unroll
-        for (int i = 0; i < NS; i += 4) {
-            a0 = fma(col[(i + 0) * NS], yv[i + 0], a0);
-            a1 = fma(col[(i + 1) * NS], yv[i + 1], a1);
-            a2 = fma(col[(i + 2) * NS], yv[i + 2], a2);
-            a3 = fma(col[(i + 3) * NS], yv[i + 3], a3);
-        }
-    }
-    return lane < N ? (a0 + a1) + (a2 + a3) : 0.0;
-}
-
-// two products with one pass over the table
-template <int NS>
-__device__ __forceinline__ void hinv_mul2(const double* Hs, const double* y0, const double* y1, int N, int lane,
-                                          double& o0, double& o1) {
-    double a0 = 0.0, a1 = 0.0, b0 = 0.0, b1 = 0.0;
-    const int k = lane & (NS - 1), tk = he_tri(k);
-    const double* col = Hs + k;
-#pragma unroll
-    for (int i = 0; i < NS; i += 2) {
-        double h0, h1;
-        if constexpr (kPackedHe<NS>) {
-            h0 = Hs[(i + 0) >= k ? he_tri(i + 0) + k : tk + (i + 0)];
-            h1 = Hs[(i + 1) >= k ? he_tri(i + 1) + k : tk + (i + 1)];
-        } else { h0 = col[(i + 0) * NS]; h1 = col[(i + 1) * NS]; }
-        a0 = fma(h0, y0[i + 0], a0); b0 = fma(h0, y1[i + 0], b0);
-        a1 = fma(h1, y0[i + 1], a1); b1 = fma(h1, y1[i + 1], b1);
-    }
-    o0 = lane < N ? a0 + a1 : 0.0;
-    o1 = lane < N ? b0 + b1 : 0.0;
-}
 
 // a-space normal of the row (kq; al,be,ga,de) evaluated at this lane j:
 __device__ __forceinline__ double normal_at(const Lane& L, int kq, double al, double be, double ga, double de, double tau_kq) {
@@ -267,8 +219,6 @@ __device__ __forceinline__ double adjoint(const Lane& L, const double* ws, const
 
 enum Ev : int { EV_NONE = 0, EV_DROP, EV_COMPL, EV_DROPH, EV_CAP, EV_CAPIN };
 
-struct SolveStats { int status, iters, events, m; };
-
 // The quadratic slack xi_h of stage k, once above its bound, is eliminated into the objective:
 // H_eff = H + q * sum_k n_k n_k'  (n_k: a-space normal of the headway-policy row).  He holds
 // H_eff^-1 for this wave; adding / removing one stage is a Sherman-Morrison rank-one update.
@@ -280,32 +230,14 @@ __device__ __forceinline__ void he_rank1(const Lane& L, const Cfg& c, WaveMem<MM
     const double nk = mb_reduce(L, c, normal_at(L, k, 1.0, chwk, 0.0, 0.0, tauv[k]));
     if (lane < NS) M.yv[lane] = nk;
     WSYNC();
-    const double y = hinv_mul<NS>(He, M.yv, N, lane);          // in the reduced variables: the table is updated with it
+    const double y = he_mul<NS, kPackedHe<NS>>(He, M.yv, N, lane);          // in the reduced variables: the table is updated with it
     double sy, vy;
     hom_traj(L, mb_expand(L, c, y), sy, vy);
     const double ny = bcast(sy + chwk * vy, k);                 // n_k' y
     const double kappa = add ? c.qH / (1.0 + c.qH * ny) : -c.qH / (1.0 - c.qH * ny);
     if (lane < NS) M.ub[lane] = y;          // y is zero beyond N
     WSYNC();
-    if (lane < NS) {
-        const double yj = kappa * y;
-        if constexpr (kPackedHe<NS>) {
-            // lane j owns column j of the lower triangle: entries (i, j), i >= j
-            for (int i = lane; i < NS; ++i) {
-                const int e = he_tri(i) + lane;
-                He[e] = fma(-M.ub[i], yj, He[e]);
-            }
-        } else {
-            double* col = He + lane;
-#pragma unroll
-            for (int i = 0; i < NS; i += 4) {
-                const double h0 = col[(i + 0) * NS], h1 = col[(i + 1) * NS], h2 = col[(i + 2) * NS], h3 = col[(i + 3) * NS];
-                const double y0 = M.ub[i], y1 = M.ub[i + 1], y2 = M.ub[i + 2], y3 = M.ub[i + 3];
-                col[(i + 0) * NS] = fma(-y0, yj, h0); col[(i + 1) * NS] = fma(-y1, yj, h1);
-                col[(i + 2) * NS] = fma(-y2, yj, h2); col[(i + 3) * NS] = fma(-y3, yj, h3);
-            }
-        }
-    }
+    if (lane < NS) he_sub_outer<NS, kPackedHe<NS>>(He, M.ub, kappa * y, lane);
     WSYNC();
 }
 
@@ -338,12 +270,8 @@ __device__ __forceinline__ void he_load_base(double* He, const double* __restric
 
 // ----------------------------------------------------------------------------------------------
 // rebuild the working-set list + effective rows from the state codes, build S = C Hinv C' + D,
-// invert it in place (symmetric sweeps).  returns m (or -1 if S was numerically singular).
-// fast = 1: the last event appended the plain row (kq, tq) whose column sv = C u, rv = P sv and pivot
-// zz = c'u - sv'rv are still in LDS -> bordered update of P;  fast = 2: it dropped the row at list
-// position drop_pos -> rank-one downdate;  fast = 0 (or any inconsistency): full rebuild.
-struct FastInfo { int fast, m_old, kq, tq, drop_pos; double zz; };
-
+// invert it in place.  returns m (or -1 if S was numerically singular).  F says which of the three ways of
+// eepacc_schur.h brings P up to date: bordered update, downdate or full rebuild.
 template <int MMAX, int NS>
 __device__ __forceinline__ int rebuild_and_factor(Lane& L, const Cfg& c, WaveMem<MMAX, NS>& M, double* Hs, const double* tauv,
                                                   const FastInfo& F) {
@@ -357,7 +285,6 @@ __device__ __forceinline__ int rebuild_and_factor(Lane& L, const Cfg& c, WaveMem
 #endif
     he_sync(L, c, M, Hs, tauv);
     RTOC(9);
-    double* const colk = M.ws;      // 3 (NS + 1) >= MMAX doubles
     // count this lane's active rows
     const int cnt = __popcll(codes_eq1(L.code));
     double basef = scan_excl((double)cnt);
@@ -407,47 +334,12 @@ __device__ __forceinline__ int rebuild_and_factor(Lane& L, const Cfg& c, WaveMem
         // position of the new row in the new (lane-major) list
         const int pl = rows_below(L, F.tq);
         const int p = __builtin_amdgcn_readlane(L.base + pl, __builtin_amdgcn_readfirstlane(F.kq));
-        const double iz = 1.0 / F.zz;
-        const int nnz = m * (m + 1) / 2;
-        // in place, highest entries first: an entry moves to a higher packed index, so a chunk never
-        // overwrites what a later (lower) chunk still has to read
-        for (int e0 = ((nnz - 1) >> 6) << 6; e0 >= 0; e0 -= 64) {
-            const int e = e0 + lane;
-            double v = 0.0;
-            if (e < nnz) {
-                const int code = rc[e], r = code >> 8, cc = code & 255;
-                const int i = r < p ? r : r - 1, j = cc < p ? cc : cc - 1;
-                if (r == p && cc == p) v = iz;
-                else if (r == p) v = -M.rv[j] * iz;
-                else if (cc == p) v = -M.rv[i] * iz;
-                else v = M.P[pidx(i, j)] + M.rv[i] * M.rv[j] * iz;
-            }
-            WSYNC();
-            if (e < nnz) M.P[e] = v;
-            WSYNC();
-        }
+        schur_insert(M.P, M.rv, rc, m, p, 1.0 / F.zz, lane);
         RTOC(12);
         return m;
     }
     if (F.fast == 2 && m == F.m_old - 1) {
-        const int p = F.drop_pos, mo = F.m_old;
-        if (lane < mo) colk[lane] = M.P[pidx(lane, p)];
-        WSYNC();
-        const double ip = 1.0 / colk[p];
-        const int nnz = m * (m + 1) / 2;
-        // lowest entries first: an entry moves to a lower packed index
-        for (int e0 = 0; e0 < nnz; e0 += 64) {
-            const int e = e0 + lane;
-            double v = 0.0;
-            if (e < nnz) {
-                const int code = rc[e], r = code >> 8, cc = code & 255;
-                const int i = r < p ? r : r + 1, j = cc < p ? cc : cc + 1;
-                v = M.P[pidx(i, j)] - colk[i] * colk[j] * ip;
-            }
-            WSYNC();
-            if (e < nnz) M.P[e] = v;
-            WSYNC();
-        }
+        schur_remove(M.P, M.ws, rc, F.m_old, m, F.drop_pos, lane);
         RTOC(12);
         return m;
     }
@@ -469,7 +361,7 @@ __device__ __forceinline__ int rebuild_and_factor(Lane& L, const Cfg& c, WaveMem
             if (lane < NS) { M.yv[lane] = c0; M.lam[lane] = c1; }
             WSYNC();
             double u0, u1;
-            hinv_mul2<NS>(Hs, M.yv, M.lam, N, lane, u0, u1);
+            he_mul2<NS, kPackedHe<NS>>(Hs, M.yv, M.lam, N, lane, u0, u1);
             u0 = mb_expand(L, c, u0); u1 = mb_expand(L, c, u1);
             WSYNC();
             double su0, vu0, su1, vu1;
@@ -483,36 +375,10 @@ __device__ __forceinline__ int rebuild_and_factor(Lane& L, const Cfg& c, WaveMem
         WSYNC();
     }
     RTOC(11);
-    // in-place inversion by symmetric sweeps: after sweeping every pivot P = -S^-1
-    int singular = 0;
-    if (lane < m) M.sv[lane] = fabs(M.P[pidx(lane, lane)]);     // original diagonal (pivot scale)
-    WSYNC();
-    // the packed lower triangle is spread over all 64 lanes (entry e = lane + 64 t; its row and column
-    // come from a small table), so a sweep costs m(m+1)/128 entry updates per lane instead of m
-    const int nnz = m * (m + 1) / 2;
-    for (int k = 0; k < m; ++k) {
-        const double d = M.P[pidx(k, k)];
-        if (!(d > 1e-12 * M.sv[k])) { singular = 1 + k; break; }
-        const double inv = 1.0 / d;
-        if (lane < m) colk[lane] = M.P[pidx(lane, k)];
-        WSYNC();
-#pragma unroll 2
-        for (int e = lane; e < nnz; e += 64) {
-            const int code = rc[e], r = code >> 8, cc = code & 255;
-            const double c0 = colk[r];
-            const double cl = colk[cc] * inv;
-            double v0 = M.P[e] - c0 * cl;
-            if (cc == k) v0 = c0 * inv;
-            if (r == k) v0 = (cc == k) ? -inv : cl;
-            M.P[e] = v0;
-        }
-        WSYNC();
-    }
+    // (scratch column in ws | wv | wa: 3 (NS + 1) >= MMAX doubles)
+    const int singular = schur_invert(M.P, M.sv, M.ws, rc, m, lane);
     RTOC(12);
     if (singular) return kBaseline ? -(9 + singular) : -1;        // baseline controller: -(10 + list position of the dependent row)
-    if (lane < m)
-        for (int r = lane; r < m; ++r) M.P[pidx(r, lane)] = -M.P[pidx(r, lane)];
-    WSYNC();
     return m;
 }
 
@@ -585,32 +451,9 @@ __device__ __forceinline__ double direction_side(const Lane& L, WaveMem<MMAX, NS
     return adjoint<NS>(L, M.ws, M.wv, M.wa, M.ub);
 }
 
-// C x for the working-set rows (x given through LDS images x / sx / vx): result for lane i < m
-template <int MMAX, int NS>
-__device__ __forceinline__ double rows_dot_img(const WaveMem<MMAX, NS>& M, int i, int N, const double* x,
-                                               const double* sx, const double* vx) {
-    const int ki = M.w_k[i];
-    double s = M.e_al[i] * sx[ki] + M.e_be[i] * vx[ki];
-    if (ki < N) s += M.e_ga[i] * x[ki];
-    if (ki > 0) s += M.e_de[i] * x[ki - 1];
-    return s;
-}
 template <int MMAX, int NS>
 __device__ __forceinline__ double rows_dot(const WaveMem<MMAX, NS>& M, int i, int N) {
     return rows_dot_img(M, i, N, M.ub, M.sub, M.vub);
-}
-
-// lam = -P (d + C h (+ nothing else)); h given through ub/sub/vub
-template <int MMAX, int NS>
-__device__ __forceinline__ void solve_multipliers(WaveMem<MMAX, NS>& M, int m, int lane, int N) {
-    if (lane < m) M.sv[lane] = M.e_d[lane] + rows_dot(M, lane, N);
-    WSYNC();
-    if (lane < m) {
-        double acc = 0.0;
-        for (int j = 0; j < m; ++j) acc = fma(M.P[pidx(lane, j)], M.sv[j], acc);
-        M.lam[lane] = -acc;
-    }
-    WSYNC();
 }
 
 // primal point from the multipliers: a = -Hinv (g_eff + lam_q c_q + C' lam); also refreshes the
@@ -624,7 +467,7 @@ __device__ __forceinline__ void primal_from_multipliers(Lane& L, const Cfg& c, W
     g = mb_reduce(L, c, g);
     if (L.lane < NS) M.yv[L.lane] = g;
     WSYNC();
-    L.a = -mb_expand(L, c, hinv_mul<NS>(Hs, M.yv, L.N, L.lane));
+    L.a = -mb_expand(L, c, he_mul<NS, kPackedHe<NS>>(Hs, M.yv, L.N, L.lane));
     hom_traj(L, L.a, L.sh, L.vh);
     L.am1 = dpp_zero<0x138, 0xf>(L.a);
     if (L.lane < L.N) M.av[L.lane] = L.a;
@@ -835,8 +678,6 @@ __device__ __forceinline__ double slide_limit(const Lane& L, const Lane& L0, con
     return best;
 }
 
-struct Incoming { int kq, qcode, tq, gq; bool is_bound; double al, be, ga, de, d; };
-
 // right-hand side ba[t] of lane k for wave-uniform t and k: a scalar switch picks the register, one broadcast
 __device__ __forceinline__ double ba_at(const Lane& L, int t, int k) {
     double x = 0.0;
@@ -986,7 +827,7 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const Cfg& c, WaveMem<MM
             double g = mb_reduce(L, c, gradient_side(L, c, M, 0, false, lam_q, q.kq, q.al, q.be, q.ga, q.de));
             if (lane < NS) M.yv[lane] = g;
             WSYNC();
-            double h = mb_expand(L, c, hinv_mul<NS>(Hs, M.yv, N, lane));
+            double h = mb_expand(L, c, he_mul<NS, kPackedHe<NS>>(Hs, M.yv, N, lane));
             double shh, vhh;
             hom_traj(L, h, shh, vhh);
             if (lane < N) M.ub[lane] = h;
@@ -1113,7 +954,7 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const Cfg& c, WaveMem<MM
         double cj = mb_reduce(L, c, normal_at(L, kq, q.al, q.be, q.ga, q.de, tauv[kq]));
         if (lane < NS) M.yv[lane] = cj;
         WSYNC();
-        double u = mb_expand(L, c, hinv_mul<NS>(Hs, M.yv, N, lane));
+        double u = mb_expand(L, c, he_mul<NS, kPackedHe<NS>>(Hs, M.yv, N, lane));
         double su, vu;
         hom_traj(L, u, su, vu);
         if (lane < N) M.ub[lane] = u;
@@ -1268,7 +1109,7 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const Cfg& c, WaveMem<MM
             const double y = mb_reduce(L, c, direction_side(L, M, m, kq, q.al, q.be, q.ga, q.de));
             if (lane < NS) M.yv[lane] = y;
             WSYNC();
-            const double z = mb_expand(L, c, hinv_mul<NS>(Hs, M.yv, N, lane));
+            const double z = mb_expand(L, c, he_mul<NS, kPackedHe<NS>>(Hs, M.yv, N, lane));
             double sz, vz;
             hom_traj(L, z, sz, vz);
             L.a = fma(-tstep, z, L.a); L.sh = fma(-tstep, sz, L.sh); L.vh = fma(-tstep, vz, L.vh);
@@ -1528,7 +1369,7 @@ __device__ __forceinline__ void ab_step(const DevCfg& C, WaveMem<MMAX, NS>& M, d
         // lv_k v_k + la_k a_k with the gear ratio tau_est(k) = LUTgearshift(v_est(k)) (LUTgearshift.m:17-41,
         // EstimateRouteAndComfortBounds.m:63-66).  v_k = v_0 + sum_{i<k} T_i a_i, so
         //   g_j = T_j sum_{k>j} (2 cq_k v_0 + lv_k) + la_j,   H_ij = 2 T_i T_j sum_{k>max(i,j)} cq_k + (acceleration, jerk)
-        // change every step: closed forms from two suffix sums, inverse in LDS by symmetric sweeps (as eepacc_fbs.hip)
+        // change every step: closed forms from two suffix sums, inverse in LDS by symmetric sweeps
         double tg = C.ice_gb[7];
 #pragma unroll
         for (int g2 = 6; g2 >= 0; --g2) if (v_est < C.ice_up[g2]) tg = C.ice_gb[g2];
@@ -1561,30 +1402,7 @@ __device__ __forceinline__ void ab_step(const DevCfg& C, WaveMem<MMAX, NS>& M, d
             }
             WSYNC();
             if (kMoveBlocking && c.mb_len != 0) he_mb_fold<NS>(Hs, c, N, lane);
-            {
-                // all 64 lanes work: lane l updates rows [r0, r0 + RPL) of column l % NS (NS = 32: two lanes per column)
-                constexpr int HALVES = 64 / NS, RPL = NS / HALVES;
-                const int jcol = lane & (NS - 1), r0 = (lane / NS) * RPL;
-                double* col = Hs + jcol;
-                for (int k = 0; k < N; ++k) {
-                    const double d = Hs[k * NS + k];
-                    if (!(d > 0.0)) { h_bad = 1; break; }
-                    const double inv = 1.0 / d;
-                    if (lane < NS) M.wa[lane] = (lane < N) ? Hs[k * NS + lane] : 0.0;
-                    WSYNC();
-                    const double hkj = M.wa[jcol];
-                    const double f = hkj * inv;
-                    const bool piv = jcol == k;
-#pragma unroll
-                    for (int ii = 0; ii < RPL; ++ii) {
-                        const int i = r0 + ii;
-                        const double ck = M.wa[i], old = col[i * NS];
-                        const double upd = piv ? ck * inv : fma(-ck, f, old);
-                        col[i * NS] = (i == k) ? (piv ? -inv : f) : upd;
-                    }
-                    WSYNC();
-                }
-            }
+            h_bad = he_invert_full<NS>(Hs, M.wa, N, lane);
             for (int e = lane; e < NS * NS; e += 64) {
                 const double x = -Hs[e];
                 Hs[e] = x;

@@ -21,12 +21,16 @@
 // sensitivities are  dv_k/du_i = Pi_k gamma_i,  ds_k/du_i = gamma_i (Theta_k - Theta_{i+1})  (i < k), so the
 // forward response and the adjoint are plain wave prefix / suffix sums with per-lane scalings (DPP), and the
 // entries of H = Psi' Q Psi have closed forms (built per step, inverted in LDS by symmetric sweeps).
+//
+// The tables of the active-set method (the inverse He of the effective Hessian, the inverse Schur block P of the working
+// set) are maintained by eepacc_schur.h, shared with the ABMPC kernels.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
 #include "eepacc_device.h"
 #include "eepacc_stage.h"
 #include "eepacc_units.h"
+#include "eepacc_schur.h"
 #include "eepacc_fbs.h"
 #include "../../include/eepacc.h"
 
@@ -203,35 +207,6 @@ __device__ __forceinline__ void hom_traj(const Lane& L, double x, double& sh, do
     sh = scan_excl((L.lane < L.N) ? L.T * vh : 0.0);
 }
 
-// out_k = sum_i He[i][k] * yv[i]   (He symmetric NS x NS in LDS, zero padded)
-template <int NS>
-__device__ __forceinline__ double hinv_mul(const double* Hs, const double* yv, int N, int lane) {
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-    const double* col = Hs + (lane & (NS - 1));
-#pragma unroll
-    for (int i = 0; i < NS; i += 4) {
-        a0 = fma(col[(i + 0) * NS], yv[i + 0], a0);
-        a1 = fma(col[(i + 1) * NS], yv[i + 1], a1);
-        a2 = fma(col[(i + 2) * NS], yv[i + 2], a2);
-        a3 = fma(col[(i + 3) * NS], yv[i + 3], a3);
-    }
-    return lane < N ? (a0 + a1) + (a2 + a3) : 0.0;
-}
-template <int NS>
-__device__ __forceinline__ void hinv_mul2(const double* Hs, const double* y0, const double* y1, int N, int lane,
-                                          double& o0, double& o1) {
-    double a0 = 0.0, a1 = 0.0, b0 = 0.0, b1 = 0.0;
-    const double* col = Hs + (lane & (NS - 1));
-#pragma unroll
-    for (int i = 0; i < NS; i += 2) {
-        const double h0 = col[(i + 0) * NS], h1 = col[(i + 1) * NS];
-        a0 = fma(h0, y0[i + 0], a0); b0 = fma(h0, y1[i + 0], b0);
-        a1 = fma(h1, y0[i + 1], a1); b1 = fma(h1, y1[i + 1], b1);
-    }
-    o0 = lane < N ? a0 + a1 : 0.0;
-    o1 = lane < N ? b0 + b1 : 0.0;
-}
-
 // u-space normal of the row (kq; al,be,ga,de) evaluated at this lane j (Pi_kq, Th_kq: wave-uniform)
 __device__ __forceinline__ double normal_at(const Lane& L, int kq, double al, double be, double ga, double de,
                                             double Pi_kq, double Th_kq) {
@@ -331,8 +306,6 @@ __device__ __forceinline__ Tup eff_row(const Lane& L, const RC& c, const double*
     return R;
 }
 
-struct SolveStats { int status, iters, events, m; };
-
 // ----------------------------------------------------------------------------------------------
 // per-wave inverse He of the effective Hessian.  Rank-one: penalty q n n' of a stage whose xi_h is off its bound.
 template <int MMAX, int NS>
@@ -342,24 +315,14 @@ __device__ __forceinline__ void he_rank1(const Lane& L, const RC& c, FMem<MMAX, 
     const double nk = normal_at(L, k, 1.0, chwk, 0.0, 0.0, bcast(L.Pi, k), bcast(L.Th, k));
     if (lane < NS) M.ws[lane] = nk;
     WSYNC();
-    const double y = hinv_mul<NS>(He, M.ws, N, lane);
+    const double y = he_mul<NS, false>(He, M.ws, N, lane);
     double sy, vy;
     hom_traj(L, y, sy, vy);
     const double ny = bcast(sy + chwk * vy, k);
     const double kappa = add ? c.qH / (1.0 + c.qH * ny) : -c.qH / (1.0 - c.qH * ny);
     if (lane < NS) M.ub[lane] = y;
     WSYNC();
-    if (lane < NS) {
-        const double yj = kappa * y;
-        double* col = He + lane;
-#pragma unroll
-        for (int i = 0; i < NS; i += 4) {
-            const double h0 = col[(i + 0) * NS], h1 = col[(i + 1) * NS], h2 = col[(i + 2) * NS], h3 = col[(i + 3) * NS];
-            const double y0 = M.ub[i], y1 = M.ub[i + 1], y2 = M.ub[i + 2], y3 = M.ub[i + 3];
-            col[(i + 0) * NS] = fma(-y0, yj, h0); col[(i + 1) * NS] = fma(-y1, yj, h1);
-            col[(i + 2) * NS] = fma(-y2, yj, h2); col[(i + 3) * NS] = fma(-y3, yj, h3);
-        }
-    }
+    if (lane < NS) he_sub_outer<NS, false>(He, M.ub, kappa * y, lane);
     WSYNC();
 }
 
@@ -375,7 +338,7 @@ __device__ __forceinline__ bool he_rank2(const Lane& L, const RC& c, FMem<MMAX, 
     if (lane < NS) { M.ws[lane] = sg; M.wv[lane] = fv; }
     WSYNC();
     double y1, y2;
-    hinv_mul2<NS>(He, M.ws, M.wv, N, lane, y1, y2);
+    he_mul2<NS, false>(He, M.ws, M.wv, N, lane, y1, y2);
     double s1, v1, s2, v2;
     hom_traj(L, y1, s1, v1);
     hom_traj(L, y2, s2, v2);
@@ -438,10 +401,8 @@ __device__ __forceinline__ void he_sync(Lane& L, const RC& c, FMem<MMAX, NS>& M,
 
 // ----------------------------------------------------------------------------------------------
 // working-set list + effective rows from the codes, S = C He C', inverse Schur block P (packed, in place).
-// Same three paths as the ABMPC kernel: bordered update after a plain row was added (fast = 1), rank-one
-// downdate after a plain row left (fast = 2), full rebuild otherwise.
-struct FastInfo { int fast, m_old, kq, tq, drop_pos; double zz; };
-
+// Bordered update after a plain row was added (F.fast = 1), rank-one downdate after a plain row left (F.fast = 2), full
+// rebuild otherwise; P itself is maintained by eepacc_schur.h.  Returns m (-1: S numerically singular, -2: m > MMAX).
 template <int MMAX, int NS>
 __device__ __forceinline__ int rebuild_and_factor(Lane& L, const RC& c, FMem<MMAX, NS>& M, double* Hs, const FastInfo& F) {
     const int lane = L.lane, N = L.N;
@@ -469,43 +430,11 @@ __device__ __forceinline__ int rebuild_and_factor(Lane& L, const RC& c, FMem<MMA
     if (F.fast == 1 && m == F.m_old + 1 && F.m_old > 0) {
         const int pl = __popcll(codes_eq1(L.code) & ((1ull << (2 * F.tq)) - 1ull));
         const int p = bcast_i(L.base + pl, F.kq);
-        const double iz = 1.0 / F.zz;
-        const int nnz = m * (m + 1) / 2;
-        for (int e0 = ((nnz - 1) >> 6) << 6; e0 >= 0; e0 -= 64) {
-            const int e = e0 + lane;
-            double v = 0.0;
-            if (e < nnz) {
-                const int code = rc[e], r = code >> 8, cc = code & 255;
-                const int i = r < p ? r : r - 1, j = cc < p ? cc : cc - 1;
-                if (r == p && cc == p) v = iz;
-                else if (r == p) v = -M.rv[j] * iz;
-                else if (cc == p) v = -M.rv[i] * iz;
-                else v = M.P[pidx(i, j)] + M.rv[i] * M.rv[j] * iz;
-            }
-            WSYNC();
-            if (e < nnz) M.P[e] = v;
-            WSYNC();
-        }
+        schur_insert(M.P, M.rv, rc, m, p, 1.0 / F.zz, lane);
         return m;
     }
     if (F.fast == 2 && m == F.m_old - 1) {
-        const int p = F.drop_pos, mo = F.m_old;
-        if (lane < mo) M.wa[lane] = M.P[pidx(lane, p)];
-        WSYNC();
-        const double ip = 1.0 / M.wa[p];
-        const int nnz = m * (m + 1) / 2;
-        for (int e0 = 0; e0 < nnz; e0 += 64) {
-            const int e = e0 + lane;
-            double v = 0.0;
-            if (e < nnz) {
-                const int code = rc[e], r = code >> 8, cc = code & 255;
-                const int i = r < p ? r : r + 1, j = cc < p ? cc : cc + 1;
-                v = M.P[pidx(i, j)] - M.wa[i] * M.wa[j] * ip;
-            }
-            WSYNC();
-            if (e < nnz) M.P[e] = v;
-            WSYNC();
-        }
+        schur_remove(M.P, M.wa, rc, F.m_old, m, F.drop_pos, lane);
         return m;
     }
     // S columns, two per pass over He
@@ -524,7 +453,7 @@ __device__ __forceinline__ int rebuild_and_factor(Lane& L, const RC& c, FMem<MMA
             if (lane < NS) { M.ws[lane] = c0; M.wv[lane] = c1; }
             WSYNC();
             double u0, u1;
-            hinv_mul2<NS>(Hs, M.ws, M.wv, N, lane, u0, u1);
+            he_mul2<NS, false>(Hs, M.ws, M.wv, N, lane, u0, u1);
             WSYNC();
             double su0, vu0, su1, vu1;
             hom_traj(L, u0, su0, vu0);
@@ -536,32 +465,7 @@ __device__ __forceinline__ int rebuild_and_factor(Lane& L, const RC& c, FMem<MMA
         }
         WSYNC();
     }
-    int singular = 0;
-    if (lane < m) M.sv[lane] = fabs(M.P[pidx(lane, lane)]);
-    WSYNC();
-    const int nnz = m * (m + 1) / 2;
-    for (int k = 0; k < m; ++k) {
-        const double d = M.P[pidx(k, k)];
-        if (!(d > 1e-12 * M.sv[k])) { singular = 1; break; }
-        const double inv = 1.0 / d;
-        if (lane < m) M.wa[lane] = M.P[pidx(lane, k)];
-        WSYNC();
-#pragma unroll 2
-        for (int e = lane; e < nnz; e += 64) {
-            const int code = rc[e], r = code >> 8, cc = code & 255;
-            const double c0 = M.wa[r];
-            const double cl = M.wa[cc] * inv;
-            double v0 = M.P[e] - c0 * cl;
-            if (cc == k) v0 = c0 * inv;
-            if (r == k) v0 = (cc == k) ? -inv : cl;
-            M.P[e] = v0;
-        }
-        WSYNC();
-    }
-    if (singular) return -1;
-    if (lane < m)
-        for (int r = lane; r < m; ++r) M.P[pidx(r, lane)] = -M.P[pidx(r, lane)];
-    WSYNC();
+    if (schur_invert(M.P, M.sv, M.wa, rc, m, lane)) return -1;
     return m;
 }
 
@@ -618,36 +522,13 @@ __device__ __forceinline__ double gradient_side(const Lane& L, const RC& c, FMem
 }
 
 template <int MMAX, int NS>
-__device__ __forceinline__ double rows_dot_img(const FMem<MMAX, NS>& M, int i, int N, const double* x, const double* sx, const double* vx) {
-    const int ki = M.w_k[i];
-    double s = M.e_al[i] * sx[ki] + M.e_be[i] * vx[ki];
-    if (ki < N) s += M.e_ga[i] * x[ki];
-    if (ki > 0) s += M.e_de[i] * x[ki - 1];
-    return s;
-}
-
-template <int MMAX, int NS>
-__device__ __forceinline__ void solve_multipliers(FMem<MMAX, NS>& M, int m, int lane, int N) {
-    if (lane < m) M.sv[lane] = M.e_d[lane] + rows_dot_img(M, lane, N, M.ub, M.sub, M.vub);
-    WSYNC();
-    if (lane < m) {
-        double acc = 0.0;
-        for (int j = 0; j < m; ++j) acc = fma(M.P[pidx(lane, j)], M.sv[j], acc);
-        M.lam[lane] = -acc;
-    }
-    WSYNC();
-}
-
-struct Incoming { int kq, qcode, tq, gq; bool is_bound; double al, be, ga, de, d; };
-
-template <int MMAX, int NS>
 __device__ __forceinline__ void primal_from_multipliers(Lane& L, const RC& c, FMem<MMAX, NS>& M, const double* Hs, int m, const LG& lg,
                                                         double lam_q, const Incoming& q, double& grad_total) {
     const double g = gradient_side(L, c, M, m, &lg, M.lam, lam_q, q.kq, q.al, q.be, q.ga, q.de);
     grad_total = g;
     if (L.lane < NS) M.ws[L.lane] = g;
     WSYNC();
-    L.u = -hinv_mul<NS>(Hs, M.ws, L.N, L.lane);
+    L.u = -he_mul<NS, false>(Hs, M.ws, L.N, L.lane);
     hom_traj(L, L.u, L.sh, L.vh);
     L.um1 = lane_prev(L.u);
     if (L.lane < L.N) M.av[L.lane] = L.u;
@@ -912,7 +793,7 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const RC& c, FMem<MMAX, 
             const double g = gradient_side(L, c, M, 0, &lg, nullptr, lam_q, q.kq, q.al, q.be, q.ga, q.de);
             if (lane < NS) M.ws[lane] = g;
             WSYNC();
-            const double h = hinv_mul<NS>(Hs, M.ws, N, lane);
+            const double h = he_mul<NS, false>(Hs, M.ws, N, lane);
             double shh, vhh;
             hom_traj(L, h, shh, vhh);
             if (lane < N) M.ub[lane] = h;
@@ -964,7 +845,7 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const RC& c, FMem<MMAX, 
         const double cj = normal_at(L, kq, q.al, q.be, q.ga, q.de, bcast(L.Pi, kq), bcast(L.Th, kq));
         if (lane < NS) M.ws[lane] = cj;
         WSYNC();
-        const double ud = hinv_mul<NS>(Hs, M.ws, N, lane);
+        const double ud = he_mul<NS, false>(Hs, M.ws, N, lane);
         double su, vu;
         hom_traj(L, ud, su, vu);
         if (lane < N) M.ub[lane] = ud;
@@ -999,7 +880,7 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const RC& c, FMem<MMAX, 
                 const double gz = gradient_side(L, c, M, m, nullptr, M.rv, 0.0, 0, 0.0, 0.0, 0.0, 0.0);
                 if (lane < NS) M.ws[lane] = gz;
                 WSYNC();
-                const double hz = hinv_mul<NS>(Hs, M.ws, N, lane);
+                const double hz = he_mul<NS, false>(Hs, M.ws, N, lane);
                 double sz, vzz;
                 hom_traj(L, hz, sz, vzz);
                 vz = vu - vzz;
@@ -1361,31 +1242,7 @@ __device__ __forceinline__ void fb_step(const DevCfg& C, FMem<MMAX, NS>& M, doub
 #endif
     FT_TOC(0);
     // in-place inverse by symmetric sweeps (H is positive definite: cond ~ 1e2); afterwards Hs = -H^-1
-    int h_bad = 0;
-    {
-        // all 64 lanes work: lane l updates rows [r0, r0 + RPL) of column l % NS (NS = 32: two lanes per column)
-        constexpr int HALVES = 64 / NS, RPL = NS / HALVES;
-        const int jcol = lane & (NS - 1), r0 = (lane / NS) * RPL;
-        double* col = Hs + jcol;
-        for (int k = 0; k < N; ++k) {
-            const double d = Hs[k * NS + k];
-            if (!(d > 0.0)) { h_bad = 1; break; }
-            const double inv = 1.0 / d;
-            if (lane < NS) M.wa[lane] = (lane < N) ? Hs[k * NS + lane] : 0.0;
-            WSYNC();
-            const double hkj = M.wa[jcol];
-            const double f = hkj * inv;
-            const bool piv = jcol == k;
-#pragma unroll
-            for (int ii = 0; ii < RPL; ++ii) {
-                const int i = r0 + ii;
-                const double ck = M.wa[i], old = col[i * NS];
-                const double upd = piv ? ck * inv : fma(-ck, f, old);
-                col[i * NS] = (i == k) ? (piv ? -inv : f) : upd;
-            }
-            WSYNC();
-        }
-    }
+    const int h_bad = he_invert_full<NS>(Hs, M.wa, N, lane);
     for (int e = lane; e < NS * NS; e += 64) { const double x = -Hs[e]; Hs[e] = x; Hb[e] = x; }
     WSYNC();
     FT_TOC(1);

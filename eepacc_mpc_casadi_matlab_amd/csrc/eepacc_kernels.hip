@@ -15,6 +15,7 @@
 #include "eepacc_device.h"
 #include "eepacc_stage.h"
 #include "eepacc_units.h"
+#include "eepacc_schur.h"
 #include "../../include/eepacc.h"
 
 #define EEPACC_IMPL_NS nomb
