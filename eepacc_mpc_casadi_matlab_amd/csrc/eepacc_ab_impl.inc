@@ -290,7 +290,7 @@ __device__ __forceinline__ int rebuild_and_factor(Lane& L, const Cfg& c, WaveMem
     double basef = scan_excl((double)cnt);
     L.base = (int)(basef + 0.5);
     int m = (int)(wave_sum((double)cnt) + 0.5);
-    if (m > MMAX) return -2;
+    if (m > schur_capacity<MMAX>()) return -2;      // one row per lane (eepacc_schur.h): at most 64, whatever the tables hold
     // the pivot row of each linear group at this lane (what an active member is measured against), once per call
     struct PRow { double al, be, ga, de, d; };
     PRow PR[3];

@@ -402,7 +402,7 @@ __device__ __forceinline__ void he_sync(Lane& L, const RC& c, FMem<MMAX, NS>& M,
 // ----------------------------------------------------------------------------------------------
 // working-set list + effective rows from the codes, S = C He C', inverse Schur block P (packed, in place).
 // Bordered update after a plain row was added (F.fast = 1), rank-one downdate after a plain row left (F.fast = 2), full
-// rebuild otherwise; P itself is maintained by eepacc_schur.h.  Returns m (-1: S numerically singular, -2: m > MMAX).
+// rebuild otherwise; P itself is maintained by eepacc_schur.h.  Returns m (-1: S numerically singular, -2: m > schur_capacity<MMAX>()).
 template <int MMAX, int NS>
 __device__ __forceinline__ int rebuild_and_factor(Lane& L, const RC& c, FMem<MMAX, NS>& M, double* Hs, const FastInfo& F) {
     const int lane = L.lane, N = L.N;
@@ -410,7 +410,7 @@ __device__ __forceinline__ int rebuild_and_factor(Lane& L, const RC& c, FMem<MMA
     const int cnt = __popcll(codes_eq1(L.code));
     L.base = (int)(scan_excl((double)cnt) + 0.5);
     const int m = (int)(wave_sum((double)cnt) + 0.5);
-    if (m > MMAX) return -2;
+    if (m > schur_capacity<MMAX>()) return -2;      // one row per lane (eepacc_schur.h): at most 64, whatever the tables hold
     {
         const Locals S = locals_of<NS>(L, c, M.ba);
         int pos = L.base;

@@ -61,12 +61,14 @@
 // host-side launchers used by eepacc_capi.cpp
 namespace eepacc {
 
-// working-set capacity: rigid rows are linearly independent, so m <= N (+ terminal rows)
+// working-set tables: rigid rows are linearly independent, so m <= N (+ terminal rows) and the tables hold N + 2 rows.
+// The capacity the solvers accept is schur_capacity<MMAX>() = min(MMAX, 64): the working-set linear algebra handles one
+// row per lane (eepacc_schur.h), so at N = 63 a working set of 65 rows is refused as an overflow, like one above MMAX.
 constexpr int kMMaxSmall = 34, kNSSmall = 32;     // N <= 32: 8 waves / CU (4 per block, 2 blocks)
 constexpr int kBlocksSmall = 2;
 // N <= 63: 44.6 KB of LDS per wave (He packed 16.6 KB, P 17.7 KB), 3 waves per CU (round 2: a full He of 32 KB allowed 2).
 // Trading working-set capacity for more does not work: with a capacity of 50 rigid rows the S2 workload at N = 60
-// overflows the working set on 15 % of the steps (measured), so the full N + 2 stays.
+// overflows the working set on 15 % of the steps (measured), so the tables stay at N + 2 (capacity 64, see above).
 constexpr int kMMaxLarge = 66, kNSLarge = 64, kWpbLarge = 3;
 constexpr int kChunkStepsDefault = nomb::kChunkStepsDefault;
 

@@ -136,6 +136,13 @@ __device__ __forceinline__ int he_invert_full(double* Hs, double* colk, int N, i
 // P: the inverse Schur block of the m working-set rows, packed lower triangle in LDS (pidx).  The triangle is spread
 // over all 64 lanes (entry e = lane + 64 t; its row and column come from the small table rc = rc_table<MMAX>()), so an
 // update costs m(m+1)/128 entry updates per lane instead of m.
+//
+// Contract: m <= 64.  A row's scratch entry (the pivot column colk, the pivot scale sv, a multiplier) is loaded by the
+// lane of the same number, so everything below -- and the solvers' own `lane < m` loads around it -- handles one row per
+// lane; at m = 65 or 66 rows 64 and 65 would never be loaded or sign-flipped.  A solver whose tables hold MMAX > 64 rows
+// (MMAX = N + 2 at the long horizons, for the table sizes) still refuses a working set above schur_capacity<MMAX>().
+template <int MMAX>
+__host__ __device__ constexpr int schur_capacity() { return MMAX < 64 ? MMAX : 64; }
 
 // Bordered update: a row joined the list at position p (m: new size).  rv = P sv of the old P, iz = 1 / pivot.
 __device__ __forceinline__ void schur_insert(double* P, const double* rv, const unsigned short* rc, int m, int p,
