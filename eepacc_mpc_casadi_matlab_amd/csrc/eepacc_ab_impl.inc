@@ -1,8 +1,10 @@
-// eepacc_ab_impl.inc -- device code of the ABMPC kernels.  Included five times by eepacc_kernels.hip: once
+// eepacc_ab_impl.inc -- device code of the ABMPC kernels.  Included six times by eepacc_kernels.hip: once
 // per value of EEPACC_IMPL_MB (move blocking compiled out / in), once with EEPACC_IMPL_BL (the baseline
-// controller's row grouping, CreateQP_BL.m: one slack for all soft rows) and twice with EEPACC_IMPL_ICE (the ICE-map
-// fuel term, whose Hessian is built and inverted every step; without / with move blocking), each time into its own
-// namespace, so that the default path carries no register or instruction cost for the variants.
+// controller's row grouping, CreateQP_BL.m: one slack for all soft rows), once with EEPACC_IMPL_BL and EEPACC_IMPL_TV
+// (the target-vehicle MPC, CreateQP_TV.m: the baseline QP without its vehicle-following rows and without lead inputs)
+// and twice with EEPACC_IMPL_ICE (the ICE-map fuel term, whose Hessian is built and inverted every step; without /
+// with move blocking), each time into its own namespace, so that the default path carries no register or instruction
+// cost for the variants.
 // The tables of the active-set method (the inverse He of the effective Hessian, the inverse Schur block P of the working
 // set) are maintained by eepacc_schur.h, which the FBMPC kernels share; it is included once, outside these namespaces.
 namespace eepacc {
@@ -16,6 +18,12 @@ constexpr bool kIce = EEPACC_IMPL_ICE;      // ICE-map fuel term (CreateQP_AB.m:
 #else
 constexpr bool kIce = false;
 #endif
+#ifdef EEPACC_IMPL_TV
+constexpr bool kTargetVeh = EEPACC_IMPL_TV;     // RunOpt_TVMPC (CreateQP_TV.m): a baseline variant (kBaseline is set too)
+#else
+constexpr bool kTargetVeh = false;
+#endif
+static_assert(!kTargetVeh || kBaseline, "the target-vehicle MPC is a variant of the baseline controller");
 
 
 #undef PTIC
@@ -47,6 +55,15 @@ __device__ __forceinline__ int group_of(int t) {
     if constexpr (kBaseline) return t < R_AMAX ? G_NONE : G_F;
     return t < R_AMAX ? G_NONE : (t < R_SAFE1 ? G_F : (t < R_VINC ? G_S : (t == R_VINC ? G_V : G_H)));
 }
+// Row types this variant has.  CreateQP_TV.m:229-284 is CreateQP_BL.m's stage without the two headway rows (and without
+// the two rows of the terminal stage); the travel-incentive and headway-policy rows are ABMPC's alone.  The type
+// numbering, and with it the nibble of a type in the state-code word, stays: the unrolled loops over the types skip the
+// four at compile time, so 12 of the 16 nibbles and 12 of the 16 right-hand sides Lane::ba are live in this variant.
+__device__ __forceinline__ constexpr bool row_live(int t) {
+    return !kTargetVeh || !(t == R_SAFE1 || t == R_SAFE2 || t == R_VINC || t == R_HWP);
+}
+// the quadratic slack of the headway-policy row is above its bound at this lane (never, where the row type is compiled out)
+#define EEPACC_HWP_ON(L) (row_live(R_HWP) && code_of(L, R_HWP) == 3)
 __device__ __forceinline__ double row_al(int t) {
     return (t == R_SLO) ? -1.0 : ((t == R_SHI || t == R_SAFE1 || t == R_SAFE2 || t == R_HWP) ? 1.0 : 0.0);
 }
@@ -243,6 +260,7 @@ __device__ __forceinline__ void he_rank1(const Lane& L, const Cfg& c, WaveMem<MM
 
 template <int MMAX, int NS>
 __device__ __forceinline__ void he_sync(Lane& L, const Cfg& c, WaveMem<MMAX, NS>& M, double* He, const double* tauv) {
+    if constexpr (!row_live(R_HWP)) return;
     const unsigned long long want = __ballot(L.lane < L.N && code_of(L, R_HWP) == 3);
     unsigned long long diff = want ^ L.kmask;
     while (diff) {
@@ -302,7 +320,7 @@ __device__ __forceinline__ int rebuild_and_factor(Lane& L, const Cfg& c, WaveMem
         if (p >= 0) {
             double pba = 0.0;
 #pragma unroll
-            for (int u = R_AMAX; u <= R_VINC; ++u) if (u == p) pba = L.ba[u];
+            for (int u = R_AMAX; u <= R_VINC; ++u) if (row_live(u) && u == p) pba = L.ba[u];
             r.al = row_al(p); r.be = row_be(p, c.tau_min, L.chw); r.ga = row_ga(p); r.de = row_de(p, lane); r.d = pba;
         }
         PR[gi] = r;
@@ -310,6 +328,7 @@ __device__ __forceinline__ int rebuild_and_factor(Lane& L, const Cfg& c, WaveMem
     int pos = L.base;
 #pragma unroll
     for (int t = 0; t < kNumRowTypes; ++t) {
+        if (!row_live(t)) continue;
         int cd = code_of(L, t);
         if (cd == 1) {
             int g = lane_group(L, t);
@@ -392,14 +411,14 @@ __device__ __forceinline__ double gradient_side(const Lane& L, const Cfg& c, Wav
     if (lane < N) {
 #pragma unroll
         for (int t = R_AMAX; t <= R_VINC; ++t) {
-            if (code_of(L, t) == 2) {
+            if (row_live(t) && code_of(L, t) == 2) {
                 double w = group_w(c, group_of(t));
                 s += w * row_al(t); v += w * row_be(t, c.tau_min, L.chw);
                 a0 += w * row_ga(t); a1 += w * row_de(t, lane);
             }
         }
     }
-    if (lane < N && code_of(L, R_HWP) == 3) {
+    if (lane < N && EEPACC_HWP_ON(L)) {
         // quadratic slack above its bound: penalty w*xi + q/2 xi^2, xi = n'a - b; linear part (w - q b) n
         const double wl = c.wH - c.qH * L.ba[R_HWP];
         s += wl * row_al(R_HWP); v += wl * row_be(R_HWP, c.tau_min, L.chw);
@@ -517,7 +536,7 @@ __device__ __forceinline__ double group_xi(const Lane& L, const Cfg& c, int g) {
     if (p < 0) return group_lb(L, g);
     double pba = 0.0;
 #pragma unroll
-    for (int u = R_AMAX; u <= R_VINC; ++u) if (u == p) pba = L.ba[u];
+    for (int u = R_AMAX; u <= R_VINC; ++u) if (row_live(u) && u == p) pba = L.ba[u];
     return row_val(L, c, p, pba);
 }
 
@@ -544,6 +563,7 @@ __device__ __forceinline__ int warm_repair(Lane& L, const Cfg& c, const WaveMem<
     int pos = L.base;
 #pragma unroll
     for (int t = 0; t < kNumRowTypes; ++t) {
+        if (!row_live(t)) continue;
         int cd = code_of(L, t);
         if (cd != 1) continue;
         int g2 = lane_group(L, t);
@@ -621,6 +641,7 @@ __device__ __forceinline__ int lane_violation(const Lane& L, const Cfg& c, doubl
     const unsigned cand = L.valid & ~L.ign;
 #pragma unroll
     for (int t = 0; t < kNumRowTypes; ++t) {
+        if (!row_live(t)) continue;
         if (!((cand >> t) & 1u)) continue;
         if (code_of(L, t) != 0) continue;
         int g2 = lane_group(L, t);
@@ -635,7 +656,7 @@ __device__ __forceinline__ int lane_violation(const Lane& L, const Cfg& c, doubl
         if (pivot_of(L, G_S) >= 0 && !((L.ign >> (16 + G_S)) & 1u) && L.lbS - xiS > myb) { myb = L.lbS - xiS; myp = 16 + G_S; }
         if (pivot_of(L, G_V) >= 0 && !((L.ign >> (16 + G_V)) & 1u) && L.lbV - xiV > myb) { myb = L.lbV - xiV; myp = 16 + G_V; }
         // penalised quadratic slack: xi_h = n'a - b must stay above its bound
-        if (code_of(L, R_HWP) == 3 && !((L.ign >> (16 + G_H)) & 1u)) {
+        if (EEPACC_HWP_ON(L) && !((L.ign >> (16 + G_H)) & 1u)) {
             double xih = row_val(L, c, R_HWP, L.ba[R_HWP]);
             if (L.lbH - xih > myb) { myb = L.lbH - xih; myp = 16 + G_H; }
         }
@@ -661,6 +682,7 @@ __device__ __forceinline__ double slide_limit(const Lane& L, const Lane& L0, con
     const unsigned cand = L.valid & ~L.ign;
 #pragma unroll
     for (int t = 0; t < kNumRowTypes; ++t) {
+        if (!row_live(t)) continue;
         if (!((cand >> t) & 1u)) continue;
         if (code_of(L, t) != 0) continue;
         const bool soft = lane_group(L, t) == G_F;
@@ -681,11 +703,15 @@ __device__ __forceinline__ double slide_limit(const Lane& L, const Lane& L0, con
 // right-hand side ba[t] of lane k for wave-uniform t and k: a scalar switch picks the register, one broadcast
 __device__ __forceinline__ double ba_at(const Lane& L, int t, int k) {
     double x = 0.0;
-    switch (t) {
+    switch (t) {          // (types the variant does not have, row_live, fall through to the default)
         case 0: x = L.ba[0]; break;   case 1: x = L.ba[1]; break;   case 2: x = L.ba[2]; break;   case 3: x = L.ba[3]; break;
         case 4: x = L.ba[4]; break;   case 5: x = L.ba[5]; break;   case 6: x = L.ba[6]; break;   case 7: x = L.ba[7]; break;
-        case 8: x = L.ba[8]; break;   case 9: x = L.ba[9]; break;   case 10: x = L.ba[10]; break; case 11: x = L.ba[11]; break;
-        case 12: x = L.ba[12]; break; case 13: x = L.ba[13]; break; case 14: x = L.ba[14]; break; default: x = L.ba[15]; break;
+        case 8: x = L.ba[8]; break;   case 9: x = L.ba[9]; break;
+        case 10: if constexpr (row_live(10)) { x = L.ba[10]; break; }
+        case 11: if constexpr (row_live(11)) { x = L.ba[11]; break; }
+        case 12: x = L.ba[12]; break; case 13: x = L.ba[13]; break;
+        case 14: if constexpr (row_live(14)) { x = L.ba[14]; break; }
+        default: x = L.ba[row_live(15) ? 15 : 13]; break;
     }
     return bcast(x, k);
 }
@@ -788,7 +814,7 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const Cfg& c, WaveMem<MM
                 if (lane == pl) {
                     int idx = p - L.base;
 #pragma unroll
-                    for (int t = 0; t < kNumRowTypes; ++t) if (code_of(L, t) == 1) { if (idx == 0) set_code(L, t, 0); --idx; }
+                    for (int t = 0; t < kNumRowTypes; ++t) if (row_live(t) && code_of(L, t) == 1) { if (idx == 0) set_code(L, t, 0); --idx; }
                 }
                 ++dep_drops;
                 WSYNC();
@@ -992,6 +1018,7 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const Cfg& c, WaveMem<MM
             int pos = L.base;
 #pragma unroll
             for (int t = 0; t < kNumRowTypes; ++t) {
+                if (!row_live(t)) continue;
                 int cd = code_of(L, t);
                 if (cd != 1) continue;
                 int g2 = lane_group(L, t);
@@ -1081,6 +1108,7 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const Cfg& c, WaveMem<MM
                     int pos = L.base;
 #pragma unroll
                     for (int t = 0; t < kNumRowTypes; ++t) {
+                        if (!row_live(t)) continue;
                         if (code_of(L, t) != 1) continue;
                         const double l = M.lam[pos] - tstep * M.rv[pos];
                         ++pos;
@@ -1295,12 +1323,17 @@ __device__ __forceinline__ void ab_step(const DevCfg& C, WaveMem<MMAX, NS>& M, d
     } else {
         estimate_traj(C, C.paramEstSetting, C.tConstACC_ego, in.s, in.v, in.a_prev, lane, s_est, v_est);
     }
-    estimate_traj(C, C.TVestSetting, C.tConstACC_tar, in.s_tv, in.v_tv, in.a_tv_prev, lane, stv_est, vtv_est);
+    // (target-vehicle MPC: no lead vehicle, RunOpt_TVMPC.m:157 estimates its own trajectory only)
+    if constexpr (kTargetVeh) { stv_est = 0.0; vtv_est = 0.0; }
+    else estimate_traj(C, C.TVestSetting, C.tConstACC_tar, in.s_tv, in.v_tv, in.a_tv_prev, lane, stv_est, vtv_est);
     const double dist_hor = bcast(s_est, N) - in.s;                          // :200
-    const double stv_Nm1 = bcast(stv_est, N - 1);
+    const double stv_Nm1 = kTargetVeh ? 0.0 : bcast(stv_est, N - 1);
     // bounds (A3)
     double v_lim, v_curv, v_stop, v_TL, a_min, a_max, j_min, j_max;
-    route_bounds(C, s_est, v_est, in.t0, lane < N ? lane : N - 1, v_lim, v_curv, v_stop, v_TL, a_min, a_max, j_min, j_max);
+    // CreateQP_TV.m:44-45 hands EstimateRouteAndComfortBounds v_est = zeros: of :63-208 only the gear estimate (unused by
+    // CreateQP_TV) and the comfort limits read v_est, and at 0 < 5 m/s those are the low-speed limits at every stage
+    route_bounds(C, s_est, kTargetVeh ? 0.0 : v_est, in.t0, lane < N ? lane : N - 1, v_lim, v_curv, v_stop, v_TL, a_min, a_max, j_min, j_max);
+    if constexpr (kTargetVeh) { v_lim *= 0.8; v_curv *= 0.8; }              // CreateQP_TV.m:265,271 (stop and traffic-light caps unscaled)
     const double T_hwp = 2.0, A_hwp = 2.0, G_hwp = -0.0246 * T_hwp + 0.010819;
     L.chw = T_hwp + G_hwp * v_est;
     // free response of the double integrator and a-space right-hand sides (A4 + A5)
@@ -1311,14 +1344,17 @@ __device__ __forceinline__ void ab_step(const DevCfg& C, WaveMem<MMAX, NS>& M, d
     b[R_JMAX] = L.T * j_max + (lane == 0 ? in.a_prev : 0.0);
     b[R_JMIN] = -(L.T * j_min + (lane == 0 ? in.a_prev : 0.0));
     b[R_VLIM] = v_lim; b[R_VCURV] = v_curv; b[R_VSTOP] = v_stop; b[R_VTL] = v_TL;
-    b[R_VINC] = -fmin(v_lim, v_curv);
-    b[R_SAFE1] = stv_est - C.h_min; b[R_SAFE2] = stv_est; b[R_HWP] = stv_est - A_hwp;
-    if (lane == N) { b[R_SAFE1] = stv_Nm1 - C.h_min; b[R_SAFE2] = stv_Nm1; }
+    if constexpr (!kTargetVeh) {
+        b[R_VINC] = -fmin(v_lim, v_curv);
+        b[R_SAFE1] = stv_est - C.h_min; b[R_SAFE2] = stv_est; b[R_HWP] = stv_est - A_hwp;
+        if (lane == N) { b[R_SAFE1] = stv_Nm1 - C.h_min; b[R_SAFE2] = stv_Nm1; }
+    }
     unsigned valid = 0u;
     L.lbF = L.lbS = L.lbV = L.lbH = 0.0;
     int infeasible_const = 0;
 #pragma unroll
     for (int t = 0; t < kNumRowTypes; ++t) {
+        if (!row_live(t)) continue;
         double al = row_al(t), be = row_be(t, c.tau_min, L.chw);
         L.ba[t] = b[t] - al * sf - be * vf;
         bool exists;
@@ -1327,7 +1363,7 @@ __device__ __forceinline__ void ab_step(const DevCfg& C, WaveMem<MMAX, NS>& M, d
             if (t == R_SHI && !(C.s_goal < 1e300)) exists = false;
             if ((t == R_VLIM || t == R_VCURV || t == R_VSTOP || t == R_VTL) && !C.ab_route_rows) exists = false;
             if (kBaseline && (t == R_VINC || t == R_HWP)) exists = false;
-        } else exists = (lane == N) && (t == R_SAFE1 || t == R_SAFE2);
+        } else exists = (lane == N) && (t == R_SAFE1 || t == R_SAFE2);      // (CreateQP_TV.m:288-292: no terminal rows; skipped above)
         if (exists && lane == 0 && row_ga(t) == 0.0) {
             // stage-0 rows without an a-component are constants: fold into slack bounds
             exists = false;
@@ -1508,14 +1544,14 @@ __device__ __forceinline__ void ab_step(const DevCfg& C, WaveMem<MMAX, NS>& M, d
         xiF = fmax(group_xi(L, c, G_F), L.lbF);
         xiS = fmax(group_xi(L, c, G_S), L.lbS);
         xiV = fmax(group_xi(L, c, G_V), L.lbV);
-        xiH = (code_of(L, R_HWP) == 3) ? fmax(row_val(L, c, R_HWP, L.ba[R_HWP]), L.lbH) : L.lbH;
+        xiH = EEPACC_HWP_ON(L) ? fmax(row_val(L, c, R_HWP, L.ba[R_HWP]), L.lbH) : L.lbH;
     }
     // 1/2 a'Ha + g'a with H a = -(grad_total - g0) - g0 ... : H a = -grad_total  => a'(g0 - grad/2)
     // 1/2 a'Ha = 1/2 a'H_eff a - q/2 sum_K (n_k'a)^2 and H_eff a = -grad_total
     double part = (lane < N) ? L.a * (L.g0 - 0.5 * grad_total) : 0.0;
     if (kBaseline && lane < N) part += C.bl_eps * L.a * (centre - 0.5 * L.a);      // the LP's proximal term is not part of sol.cost
     part += C.w_f * xiF + C.w_s * xiS + C.w_v * xiV + c.wH * xiH + 0.5 * c.qH * xiH * xiH;
-    if (lane < N && code_of(L, R_HWP) == 3) {
+    if (lane < N && EEPACC_HWP_ON(L)) {
         const double na = row_val(L, c, R_HWP, L.ba[R_HWP]) + L.ba[R_HWP];      // n_k'a
         part -= 0.5 * c.qH * na * na;
     }
@@ -1583,7 +1619,8 @@ k_ab_step(const DevCfg* __restrict__ Cp, int B,
     double* Hs;
     WaveMem<MMAX, NS>& M = *wave_mem<MMAX, NS>(smem, C.N, Hs);
     const int lane = lane_id();
-    StepIn in{s[b], v[b], a_prev[b], t0[b], s_tv[b], v_tv[b], a_tv_prev[b]};
+    StepIn in{s[b], v[b], a_prev[b], t0[b], 0.0, 0.0, 0.0};
+    if constexpr (!kTargetVeh) { in.s_tv = s_tv[b]; in.v_tv = v_tv[b]; in.a_tv_prev = a_tv_prev[b]; }       // (no lead inputs: the launcher passes none)
     unsigned long long code = codes[(size_t)b * 64 + lane];
     StepOut so;
     double sp, vp;
@@ -1631,7 +1668,8 @@ k_run_abmpc(const DevCfg* __restrict__ Cp, int B, int k_start, int n_steps,
         double* predp = C.pred + (size_t)b * 128;
         for (int kk = kk0; kk < kk1; ++kk) {
             StepIn in;
-            measure(C, Ts, k_start + kk, kk, B, b, s0, v0, a_m1, s_tv, v_tv, cs, in);
+            if constexpr (kTargetVeh) measure_no_lead(C, Ts, k_start + kk, b, s0, v0, a_m1, cs, in);
+            else measure(C, Ts, k_start + kk, kk, B, b, s0, v0, a_m1, s_tv, v_tv, cs, in);
             StepOut so;
             double sp, vp;
             ab_step<MMAX, NS>(C, M, Hs, in, code, so, sp, vp, predp, kk > kk0,

@@ -98,8 +98,9 @@ static bool spd_inverse(std::vector<long double>& A, int n) {
     return true;
 }
 
-// kernel variant of a handle: 0 plain, 1 blocked moves, 2 baseline controller, 3 ICE-map fuel term, 4 ICE-map with blocked moves
-static int ab_variant(const DevCfg& C) { return C.bl_mode ? 2 : (C.ab_fuel_term == 2 ? (C.mb_any ? 4 : 3) : (C.mb_any ? 1 : 0)); }
+// kernel variant of a handle: 0 plain, 1 blocked moves, 2 baseline controller, 3 ICE-map fuel term, 4 ICE-map with blocked moves,
+// 5 target-vehicle MPC
+static int ab_variant(const DevCfg& C) { return C.bl_mode == 2 ? 5 : C.bl_mode ? 2 : (C.ab_fuel_term == 2 ? (C.mb_any ? 4 : 3) : (C.mb_any ? 1 : 0)); }
 
 static int build_cfg(const eepacc_settings* S, const eepacc_vehicle* V, DevCfg& C, std::vector<double>& Hinv) {
     memset(&C, 0, sizeof(C));
@@ -178,11 +179,14 @@ static int build_cfg(const eepacc_settings* S, const eepacc_vehicle* V, DevCfg& 
         C.max_iter = 15 * N + 60;
         if (const char* ev = getenv("EEPACC_DEBUG_BL_MAX_ITER")) C.max_iter = atoi(ev);
         // RunOpt_BLMPC: CreateQP_BL.m:36-39,131-148  W_BL = [w_v (travel incentive), w_a, w_j, w_f]
-        if (S->bl_mode != 1) return fail(EEPACC_EINVAL, "bl_mode must be 0 or 1");
+        // bl_mode = 2: RunOpt_TVMPC, CreateQP_TV.m:36-39 W_TV = [w_v, w_a, w_j, w_f] in W_BL, TV_*_Lim* in BL_*_Lim*
+        if (S->bl_mode != 1 && S->bl_mode != 2) return fail(EEPACC_EINVAL, "bl_mode must be 0, 1 (RunOpt_BLMPC) or 2 (RunOpt_TVMPC)");
         if (C.mb_any) return fail(EEPACC_ENOTSUP, "the baseline controller has no move blocking (RunOpt_BLMPC.m)");
+        if (S->bl_mode == 2 && !C.const_T)
+            return fail(EEPACC_EINVAL, "bl_mode = 2: Tvec must be uniform (TV_Ts, CreateQP_TV.m:29)");
         if (S->W_BL[0] < 0 || S->W_BL[1] < 0 || S->W_BL[2] < 0 || !(S->W_BL[3] > 0))
             return fail(EEPACC_EINVAL, "W_BL weights must be non-negative (w_f positive)");
-        C.bl_mode = 1;
+        C.bl_mode = S->bl_mode;
         C.ab_fuel_term = 0; C.ab_route_rows = 1;            // CreateQP_BL.m:264-288: the four speed caps are always present
         C.w_FC = 0.0; C.w_a = S->W_BL[1]; C.w_j = S->W_BL[2]; C.w_f = S->W_BL[3];
         C.w_v = 0.0; C.w_s = 0.0; C.w_h = 1.0;              // groups that do not exist in the baseline QP
@@ -391,10 +395,19 @@ extern "C" int eepacc_reset(eepacc_handle* h) {
     return EEPACC_OK;
 }
 
+// a handle created with bl_mode = 2 poses RunOpt_TVMPC's problem and takes no lead inputs: only the eepacc_tv_* / eepacc_run_tvmpc*
+// entry points run it
+static int not_tv(const eepacc_handle* h, const char* who) {
+    if (h && h->cfg.bl_mode == 2)
+        return fail(EEPACC_EINVAL, std::string(who) + ": this handle was created with bl_mode = 2 (RunOpt_TVMPC); use eepacc_tv_step / eepacc_run_tvmpc");
+    return EEPACC_OK;
+}
+
 extern "C" int eepacc_ab_step(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
                               const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
                               double* out, double* s_pred, double* v_pred, int32_t* status, void* stream) {
     if (!h) return fail(EEPACC_EINVAL, "NULL handle");
+    { const int rc = not_tv(h, "eepacc_ab_step"); if (rc != EEPACC_OK) return rc; }
     if (B < 0 || B > h->max_batch) return fail(EEPACC_EINVAL, "B exceeds max_batch of the handle");
     if (B == 0) return EEPACC_OK;
     if (!s || !v || !a_prev || !t0 || !s_tv || !v_tv || !a_tv_prev || !out || !status)
@@ -410,6 +423,7 @@ extern "C" int eepacc_run_abmpc(eepacc_handle* h, int B, int n_steps, const doub
                                 const double* a_minus1, const double* s_tv, const double* v_tv, double* traj,
                                 int32_t* status, void* stream) {
     if (!h) return fail(EEPACC_EINVAL, "NULL handle");
+    { const int rc = not_tv(h, "eepacc_run_abmpc"); if (rc != EEPACC_OK) return rc; }
     if (B < 0 || B > h->max_batch || n_steps < 0) return fail(EEPACC_EINVAL, "bad B / n_steps");
     if (B == 0 || n_steps == 0) return EEPACC_OK;
     if (!s0 || !v0 || !a_minus1 || !s_tv || !v_tv || !traj || !status)
@@ -597,6 +611,7 @@ extern "C" int eepacc_fb_step(eepacc_handle* h, int B, const double* s, const do
                               double* out, double* s_pred, double* v_pred, int32_t* status, void* stream) {
     (void)v_prev; (void)Fm_prev; (void)Fb_prev;   // accepted and unused, as in CreateQP_FB.m:1 (inputs v_minus1, Fm_minus1, Fb_minus1)
     if (!h) return fail(EEPACC_EINVAL, "NULL handle");
+    { const int rc = not_tv(h, "eepacc_fb_step"); if (rc != EEPACC_OK) return rc; }
     if (B < 0 || B > h->max_batch) return fail(EEPACC_EINVAL, "B exceeds max_batch of the handle");
     if (B == 0) return EEPACC_OK;
     if (!s || !v || !a_prev || !t0 || !s_tv || !v_tv || !a_tv_prev || !out || !status)
@@ -622,6 +637,7 @@ extern "C" int eepacc_run_fbmpc(eepacc_handle* h, int B, int n_steps, const doub
                                 const double* a_minus1, const double* s_tv, const double* v_tv,
                                 double* traj, int32_t* status, void* stream) {
     if (!h) return fail(EEPACC_EINVAL, "NULL handle");
+    { const int rc = not_tv(h, "eepacc_run_fbmpc"); if (rc != EEPACC_OK) return rc; }
     if (B < 0 || B > h->max_batch || n_steps < 0) return fail(EEPACC_EINVAL, "eepacc_run_fbmpc: bad B / n_steps");
     if (B == 0 || n_steps == 0) return EEPACC_OK;
     if (!s0 || !v0 || !a_minus1 || !s_tv || !v_tv || !traj || !status)
@@ -702,7 +718,7 @@ static int run_host(eepacc_handle* h, bool fb, int B, int n_steps, const double*
 // RunOpt_BLMPC by name: the ABMPC entry points on a handle that was created as the baseline controller
 static int need_bl(const eepacc_handle* h) {
     if (!h) return fail(EEPACC_EINVAL, "NULL handle");
-    if (!h->cfg.bl_mode) return fail(EEPACC_EINVAL, "this handle was not created with bl_mode = 1 (RunOpt_BLMPC)");
+    if (h->cfg.bl_mode != 1) return fail(EEPACC_EINVAL, "this handle was not created with bl_mode = 1 (RunOpt_BLMPC)");
     return EEPACC_OK;
 }
 extern "C" int eepacc_bl_step(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
@@ -734,4 +750,66 @@ extern "C" int eepacc_run_fbmpc_host(eepacc_handle* h, int B, int n_steps, const
                                      const double* a_minus1, const double* s_tv, const double* v_tv,
                                      double* traj, int32_t* status) {
     return run_host(h, true, B, n_steps, s0, v0, a_minus1, s_tv, v_tv, traj, status);
+}
+
+// RunOpt_TVMPC (ABO/RunOpt_TVMPC.m): the target-vehicle MPC, a handle created with bl_mode = 2.  No lead inputs: the
+// kernels of this variant read none and the launchers get null pointers.
+static int need_tv(const eepacc_handle* h) {
+    if (!h) return fail(EEPACC_EINVAL, "NULL handle");
+    if (h->cfg.bl_mode != 2) return fail(EEPACC_EINVAL, "this handle was not created with bl_mode = 2 (RunOpt_TVMPC)");
+    return EEPACC_OK;
+}
+extern "C" int eepacc_tv_step(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
+                              const double* t0, double* out, double* s_pred, double* v_pred, int32_t* status, void* stream) {
+    const int rc = need_tv(h);
+    if (rc != EEPACC_OK) return rc;
+    if (B < 0 || B > h->max_batch) return fail(EEPACC_EINVAL, "B exceeds max_batch of the handle");
+    if (B == 0) return EEPACC_OK;
+    if (!s || !v || !a_prev || !t0 || !out || !status) return fail(EEPACC_EINVAL, "eepacc_tv_step: NULL buffer");
+    HIPCHK(hipSetDevice(h->device));
+    h->last_B = B;
+    HIPCHK(eepacc::launch_ab_step(h->d_cfg, h->cfg.N, ab_variant(h->cfg), B, s, v, a_prev, t0, nullptr, nullptr, nullptr, h->d_codes,
+                                  out, s_pred, v_pred, status, h->d_iters, (hipStream_t)stream));
+    return EEPACC_OK;
+}
+extern "C" int eepacc_run_tvmpc(eepacc_handle* h, int B, int n_steps, const double* s0, const double* v0,
+                                const double* a_minus1, double* traj, int32_t* status, void* stream) {
+    const int rc = need_tv(h);
+    if (rc != EEPACC_OK) return rc;
+    if (B < 0 || B > h->max_batch || n_steps < 0) return fail(EEPACC_EINVAL, "eepacc_run_tvmpc: bad B / n_steps");
+    if (B == 0 || n_steps == 0) return EEPACC_OK;
+    if (!s0 || !v0 || !a_minus1 || !traj || !status) return fail(EEPACC_EINVAL, "eepacc_run_tvmpc: NULL buffer");
+    HIPCHK(hipSetDevice(h->device));
+    if (h->k_done > 0 && h->carry_B != B)
+        return fail(EEPACC_EINVAL, "eepacc_run_tvmpc: B changed while resuming; call eepacc_reset first");
+    h->last_B = B;
+    HIPCHK(eepacc::launch_run_abmpc(h->d_cfg, h->cfg.N, ab_variant(h->cfg), B, h->k_done, n_steps, s0, v0, a_minus1, nullptr, nullptr,
+                                    h->d_carry, h->d_codes, traj, status, h->d_iters, h->d_counter, h->d_done, h->d_err, h->num_cus,
+                                    (hipStream_t)stream));
+    h->k_done += n_steps; h->carry_B = B;
+    return EEPACC_OK;
+}
+extern "C" int eepacc_run_tvmpc_host(eepacc_handle* h, int B, int n_steps, const double* s0, const double* v0,
+                                     const double* a_minus1, double* traj, int32_t* status) {
+    int rc = need_tv(h);
+    if (rc != EEPACC_OK) return rc;
+    if (B < 1 || B > h->max_batch || n_steps < 1) return fail(EEPACC_EINVAL, "bad B / n_steps");
+    if (!s0 || !v0 || !a_minus1 || !traj || !status) return fail(EEPACC_EINVAL, "NULL buffer");
+    HIPCHK(hipSetDevice(h->device));
+    DevBufs d;
+    const size_t nB = (size_t)B, nT = (size_t)n_steps * B;
+    HIPCHK(hipMalloc(&d.in, 3 * nB * sizeof(double)));
+    HIPCHK(hipMalloc(&d.traj, nT * EEPACC_OUT_N * sizeof(double)));
+    HIPCHK(hipMalloc(&d.status, nT * sizeof(int32_t)));
+    HIPCHK(hipMemcpy(d.in, s0, nB * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d.in + nB, v0, nB * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d.in + 2 * nB, a_minus1, nB * sizeof(double), hipMemcpyHostToDevice));
+    rc = eepacc_reset(h);
+    if (rc != EEPACC_OK) return rc;
+    rc = eepacc_run_tvmpc(h, B, n_steps, d.in, d.in + nB, d.in + 2 * nB, d.traj, d.status, nullptr);
+    if (rc != EEPACC_OK) return rc;
+    rc = eepacc_synchronize(h, nullptr);
+    HIPCHK(hipMemcpy(traj, d.traj, nT * EEPACC_OUT_N * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(status, d.status, nT * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return rc;
 }

@@ -38,6 +38,17 @@
 #undef EEPACC_IMPL_NS
 #undef EEPACC_IMPL_MB
 #undef EEPACC_IMPL_BL
+// target-vehicle MPC (RunOpt_TVMPC): the baseline variant with CreateQP_TV's row catalogue (no vehicle-following rows, 0.8
+// of the speed-limit and curve caps, low-speed comfort limits) and no lead inputs
+#define EEPACC_IMPL_NS tvc
+#define EEPACC_IMPL_MB false
+#define EEPACC_IMPL_BL true
+#define EEPACC_IMPL_TV true
+#include "eepacc_ab_impl.inc"
+#undef EEPACC_IMPL_NS
+#undef EEPACC_IMPL_MB
+#undef EEPACC_IMPL_BL
+#undef EEPACC_IMPL_TV
 
 // ICE-map fuel term (CreateQP_AB.m:154-159): step-varying Hessian, built and inverted in LDS every step; without and with
 // move blocking (icemb folds the Hessian into E'HE before the inversion).  Two namespaces: compiled into one, the blocking
@@ -90,7 +101,8 @@ size_t ab_smem_bytes(int N) {
 #define EEPACC_LAUNCH_NS(NSP, KERNEL, MM, NSV, WPB, GRID, ...)                                                \
     hipLaunchKernelGGL(HIP_KERNEL_NAME(NSP::KERNEL<MM, NSV, WPB>), dim3(GRID), dim3(64 * WPB), ab_smem_bytes(N), stream, __VA_ARGS__)
 #define EEPACC_LAUNCH(KERNEL, MM, NSV, WPB, GRID, ...)                                                        \
-    do { if (variant == 4) EEPACC_LAUNCH_NS(icemb, KERNEL, MM, NSV, WPB, GRID, __VA_ARGS__);                  \
+    do { if (variant == 5) EEPACC_LAUNCH_NS(tvc, KERNEL, MM, NSV, WPB, GRID, __VA_ARGS__);                    \
+         else if (variant == 4) EEPACC_LAUNCH_NS(icemb, KERNEL, MM, NSV, WPB, GRID, __VA_ARGS__);                  \
          else if (variant == 3) EEPACC_LAUNCH_NS(ice, KERNEL, MM, NSV, WPB, GRID, __VA_ARGS__);               \
          else if (variant == 2) EEPACC_LAUNCH_NS(blc, KERNEL, MM, NSV, WPB, GRID, __VA_ARGS__);               \
          else if (variant == 1) EEPACC_LAUNCH_NS(withmb, KERNEL, MM, NSV, WPB, GRID, __VA_ARGS__);            \
@@ -155,7 +167,7 @@ hipError_t launch_postprocess(const DevCfg* dC, int B, int n_steps, const double
 }
 
 hipError_t set_max_smem() {
-    const void* fns[20] = {reinterpret_cast<const void*>(&nomb::k_ab_step<kMMaxSmall, kNSSmall, 4>),
+    const void* fns[24] = {reinterpret_cast<const void*>(&nomb::k_ab_step<kMMaxSmall, kNSSmall, 4>),
                           reinterpret_cast<const void*>(&nomb::k_ab_step<kMMaxLarge, kNSLarge, kWpbLarge>),
                           reinterpret_cast<const void*>(&nomb::k_run_abmpc<kMMaxSmall, kNSSmall, 4>),
                           reinterpret_cast<const void*>(&nomb::k_run_abmpc<kMMaxLarge, kNSLarge, kWpbLarge>),
@@ -174,8 +186,12 @@ hipError_t set_max_smem() {
                           reinterpret_cast<const void*>(&icemb::k_ab_step<kMMaxSmall, kNSSmall, 4>),
                           reinterpret_cast<const void*>(&icemb::k_ab_step<kMMaxLarge, kNSLarge, kWpbLarge>),
                           reinterpret_cast<const void*>(&icemb::k_run_abmpc<kMMaxSmall, kNSSmall, 4>),
-                          reinterpret_cast<const void*>(&icemb::k_run_abmpc<kMMaxLarge, kNSLarge, kWpbLarge>)};
-    for (int i = 0; i < 20; ++i) {
+                          reinterpret_cast<const void*>(&icemb::k_run_abmpc<kMMaxLarge, kNSLarge, kWpbLarge>),
+                          reinterpret_cast<const void*>(&tvc::k_ab_step<kMMaxSmall, kNSSmall, 4>),
+                          reinterpret_cast<const void*>(&tvc::k_ab_step<kMMaxLarge, kNSLarge, kWpbLarge>),
+                          reinterpret_cast<const void*>(&tvc::k_run_abmpc<kMMaxSmall, kNSSmall, 4>),
+                          reinterpret_cast<const void*>(&tvc::k_run_abmpc<kMMaxLarge, kNSLarge, kWpbLarge>)};
+    for (int i = 0; i < 24; ++i) {
         // 160 KB of LDS per CU minus the kernel's static index table (one ushort per packed entry of P)
         const int mm = (i & 1) ? kMMaxLarge : kMMaxSmall;
         const int dyn = 160 * 1024 - ((mm * (mm + 1) / 2 * 2 + 255) & ~255);

@@ -105,6 +105,22 @@ __device__ __forceinline__ void measure(const DevCfg& C, double Ts, int k, int k
     in.t0 = cs.t0;
 }
 
+// The same without a lead vehicle (RunOpt_TVMPC.m:134-154): the target-vehicle MPC follows nobody, its kernels get no traces.
+template <class StepIn>
+__device__ __forceinline__ void measure_no_lead(const DevCfg& C, double Ts, int k, int b, const double* s0,
+                                                const double* v0, const double* a_m1, Carry& cs, StepIn& in) {
+    if (k == 0) {                                        // RunOpt_TVMPC.m:134-137
+        in.s = s0[b]; in.v = v0[b]; in.a_prev = a_m1[b];
+    } else {                                             // :143-153
+        double sm, vm;
+        plant_rk4(C, cs.s, cs.v, cs.Fm + cs.Fb, sm, vm);
+        in.s = sm; in.v = vm;
+        in.a_prev = (vm - cs.v) / Ts;
+    }
+    in.s_tv = 0.0; in.v_tv = 0.0; in.a_tv_prev = 0.0;
+    in.t0 = cs.t0;
+}
+
 // Instances take very different numbers of working-set changes (per-instance run times spread 0.75x..1.7x around the
 // mean), so the simulation is cut into work units (instance, chunk of chunk_steps MPC steps) handed out through a
 // device-wide counter in chunk-major order.  The loop state of an instance travels between units through HBM: the

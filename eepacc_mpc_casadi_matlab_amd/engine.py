@@ -54,6 +54,9 @@ def load_library() -> C.CDLL:
     lib.eepacc_bl_step.argtypes = lib.eepacc_ab_step.argtypes
     lib.eepacc_run_blmpc.argtypes = lib.eepacc_run_abmpc.argtypes
     lib.eepacc_run_blmpc_host.argtypes = lib.eepacc_run_abmpc_host.argtypes
+    lib.eepacc_tv_step.argtypes = [vp, C.c_int] + [dp] * 4 + [dp, dp, dp, dp, vp]
+    lib.eepacc_run_tvmpc.argtypes = [vp, C.c_int, C.c_int] + [dp] * 3 + [dp, dp, vp]
+    lib.eepacc_run_tvmpc_host.argtypes = [vp, C.c_int, C.c_int] + [c_double_p] * 3 + [c_double_p, ip]
     lib.eepacc_postprocess.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, dp, vp]
     lib.eepacc_last_iterations.argtypes = [vp, C.c_int, ip]
     lib.eepacc_fb_step.argtypes = [vp, C.c_int] + [dp] * 10 + [dp, dp, dp, dp, vp]
@@ -69,7 +72,7 @@ def load_library() -> C.CDLL:
 ABI_SYMBOLS = ["eepacc_last_error", "eepacc_version", "eepacc_sizeof_settings", "eepacc_sizeof_vehicle", "eepacc_create", "eepacc_destroy", "eepacc_reset",
                "eepacc_ab_step", "eepacc_run_abmpc", "eepacc_fb_step", "eepacc_run_fbmpc",
                "eepacc_run_abmpc_host", "eepacc_run_fbmpc_host", "eepacc_bl_step", "eepacc_run_blmpc", "eepacc_run_blmpc_host",
-               "eepacc_postprocess",
+               "eepacc_tv_step", "eepacc_run_tvmpc", "eepacc_run_tvmpc_host", "eepacc_postprocess",
                "eepacc_last_iterations", "eepacc_qp_solve_batched", "eepacc_synchronize", "eepacc_build_flags"]
 
 
@@ -158,6 +161,50 @@ class Engine:
     def run_blmpc(self, s0, v0, a_minus1, s_tv, v_tv, resume: bool = False, out=None):
         """eepacc_run_blmpc: run_abmpc on a handle created from settings.Settings_BL (refused on any other handle)."""
         return self.run_abmpc(s0, v0, a_minus1, s_tv, v_tv, resume=resume, out=out, by_name_bl=True)
+
+    # target-vehicle MPC (ABO/RunOpt_TVMPC.m): a handle created from settings.Settings_TV; no lead inputs -----------------
+    def tv_step(self, s, v, a_prev, t0, want_pred: bool = True):
+        """eepacc_tv_step: one step of RunOpt_TVMPC's loop (:156-277) for B instances; results as ab_step."""
+        t = self.torch
+        B = int(t.as_tensor(s).numel())
+        ins = [self._d(x, B) for x in (s, v, a_prev, t0)]
+        out = t.empty((OUT_N, B), dtype=t.float64, device=self.device)
+        sp = t.empty((self.N + 1, B), dtype=t.float64, device=self.device) if want_pred else None
+        vp = t.empty((self.N + 1, B), dtype=t.float64, device=self.device) if want_pred else None
+        status = t.empty((B,), dtype=t.int32, device=self.device)
+        _check(self.lib.eepacc_tv_step(self.h, B, *[x.data_ptr() for x in ins], out.data_ptr(),
+                                       sp.data_ptr() if want_pred else None,
+                                       vp.data_ptr() if want_pred else None, status.data_ptr(), self._stream()))
+        return out, sp, vp, status
+
+    def run_tvmpc(self, s0, v0, a_minus1, n_steps: int, resume: bool = False, out=None):
+        """eepacc_run_tvmpc: closed loop of n_steps from s0 = TVinitDist, v0 = TVinitVel, a_minus1 (each [B]).
+        Returns traj [n_steps, OUT_N, B], status [n_steps, B]; resume / out as run_abmpc."""
+        t = self.torch
+        if not resume:
+            self.reset()
+        B = int(t.as_tensor(s0).numel())
+        n_steps = int(n_steps)
+        ins = [self._d(x, B) for x in (s0, v0, a_minus1)]
+        if out is not None:
+            traj, status = out[0][:n_steps], out[1][:n_steps]
+            assert traj.shape == (n_steps, OUT_N, B) and traj.is_contiguous() and status.is_contiguous()
+        else:
+            traj = t.empty((n_steps, OUT_N, B), dtype=t.float64, device=self.device)
+            status = t.empty((n_steps, B), dtype=t.int32, device=self.device)
+        _check(self.lib.eepacc_run_tvmpc(self.h, B, n_steps, *[x.data_ptr() for x in ins], traj.data_ptr(),
+                                         status.data_ptr(), self._stream()))
+        return traj, status
+
+    def run_tvmpc_host(self, s0, v0, a_minus1, n_steps: int):
+        """eepacc_run_tvmpc_host: host (numpy) buffers in and out -- the entry the MEX gateway calls."""
+        ins = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1)) for x in (s0, v0, a_minus1)]
+        B = ins[0].size
+        assert all(x.size == B for x in ins)
+        traj = np.empty((n_steps, OUT_N, B)); status = np.empty((n_steps, B), dtype=np.int32)
+        _check(self.lib.eepacc_run_tvmpc_host(self.h, B, int(n_steps), *[as_dptr(x) for x in ins], as_dptr(traj),
+                                              status.ctypes.data_as(C.POINTER(C.c_int32))))
+        return traj, status
 
     # FBMPC: same two operators (ABO/RunOpt_FBMPC.m:161-331) -----------------------------------
     def fb_step(self, s, v, v_prev, a_prev, Fm_prev, Fb_prev, t0, s_tv, v_tv, a_tv_prev, want_pred: bool = True):
@@ -316,6 +363,62 @@ def RunOpt_BLMPC(OPTsettings: Dict[str, Any], V: Optional[Dict[str, float]] = No
     sol["P_opt"] = P.cpu().numpy()[:, 0]; sol["E_opt"] = E.cpu().numpy()[:, 0]
     sol["j_opt"] = np.diff(sol["a_opt"]) / Ts
     return sol
+
+
+def RunOpt_TVMPC(OPTsettings: Dict[str, Any], V: Optional[Dict[str, float]] = None, device: int = 0):
+    """[s_opt, v_opt, numSolverErrors] = RunOpt_TVMPC(OPTsettings)  -- ABO/RunOpt_TVMPC.m:1, one target vehicle.
+
+    Starts from TVinitDist, TVinitVel, a_minus1 (:22-24) and runs kk = 0 .. t_sim/TV_Ts (:129).  The reference allocates
+    s_opt with t_sim/TV_Ts entries and the loop appends one (:115,219): both arrays have t_sim/TV_Ts + 1 entries."""
+    from .settings import SetVehicleParameters, Settings_TV
+    if V is None:
+        V = SetVehicleParameters(OPTsettings.get("tree", "ABO"))
+    TV = Settings_TV(OPTsettings)
+    eng = Engine(TV, V, device=device, max_batch=1)
+    n_steps = int(round(OPTsettings["t_sim"] / float(OPTsettings["TV_Ts"]))) + 1
+    traj, status = eng.run_tvmpc([OPTsettings["TVinitDist"]], [OPTsettings["TVinitVel"]], [OPTsettings["a_minus1"]], n_steps)
+    eng.synchronize()
+    tr = traj.cpu().numpy()[:, :, 0]
+    return tr[:, OUT["s"]].copy(), tr[:, OUT["v"]].copy(), int((status.cpu().numpy()[:, 0] != 0).sum())
+
+
+def generate_lead_and_run(OPTsettings: Dict[str, Any], V: Optional[Dict[str, float]] = None, kind: str = "ab", batch: int = 1,
+                          device: int = 0, s_init=None, v_init=None, a_minus1=None, tv_init=None, engines=None):
+    """What ABO/Main.m:82-89 does for a use case with generateTVMPC and IncludeTV, for a batch: the lead vehicle's trace is
+    generated by RunOpt_TVMPC on the device, TVlength is subtracted from its distance (:88) and the result is handed to
+    run_abmpc / run_fbmpc / run_blmpc (kind "ab" / "fb" / "bl") as device tensors, with no host copy in between.
+
+    tv_init = (s0, v0, a_minus1) of the lead vehicles, each [batch] (default: TVinitDist, TVinitVel, a_minus1);
+    s_init, v_init, a_minus1: the ego vehicles' (default: the settings').  engines = (tv_engine, ego_engine) reuses handles.
+    The two controllers share the sample grid, so TV_Ts must equal Tvec[0]: anything else is refused, not resampled.
+    Returns (traj, status, s_tv, v_tv): the ego closed loop and the [n_steps, batch] lead traces it was fed."""
+    from .settings import SetVehicleParameters, Settings_TV, Settings_BL
+    if kind not in ("ab", "fb", "bl"):
+        raise ValueError("kind must be 'ab', 'fb' or 'bl'")
+    Ts = float(np.asarray(OPTsettings["Tvec"]).ravel()[0])
+    if float(OPTsettings["TV_Ts"]) != Ts:
+        raise ValueError("TV_Ts = %g differs from Tvec[0] = %g: the lead trace would have to be resampled (ABO/Main.m:82-89 "
+                         "takes it sample for sample); refused" % (float(OPTsettings["TV_Ts"]), Ts))
+    if V is None:
+        V = SetVehicleParameters(OPTsettings.get("tree", "ABO"))
+    B = int(batch)
+    if engines is None:
+        tv = Engine(Settings_TV(OPTsettings), V, device=device, max_batch=B)
+        ego = Engine(Settings_BL(OPTsettings) if kind == "bl" else OPTsettings, V, device=device, max_batch=B)
+    else:
+        tv, ego = engines
+    t = tv.torch
+    full = lambda x, d: np.full(B, float(d)) if x is None else x
+    n_steps = int(round(OPTsettings["t_sim"] / Ts)) + 1
+    tv0 = tv_init if tv_init is not None else (np.full(B, float(OPTsettings["TVinitDist"])),
+                                               np.full(B, float(OPTsettings["TVinitVel"])), np.full(B, float(OPTsettings["a_minus1"])))
+    lead, _ = tv.run_tvmpc(tv0[0], tv0[1], tv0[2], n_steps)
+    s_tv = (lead[:, OUT["s"], :] - float(OPTsettings["TVlength"])).contiguous()      # Main.m:88
+    v_tv = lead[:, OUT["v"], :].contiguous()
+    run = {"ab": ego.run_abmpc, "fb": ego.run_fbmpc, "bl": ego.run_blmpc}[kind]
+    traj, status = run(full(s_init, OPTsettings["s_init"]), full(v_init, OPTsettings["v_init"]),
+                       full(a_minus1, OPTsettings["a_minus1"]), s_tv, v_tv)
+    return traj, status, s_tv, v_tv
 
 
 def RunOpt_FBMPC(OPTsettings: Dict[str, Any], V: Optional[Dict[str, float]] = None, device: int = 0) -> Dict[str, Any]:

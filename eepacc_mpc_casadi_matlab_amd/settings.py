@@ -244,6 +244,7 @@ def Settings(OPT: Dict[str, Any] | None = None, tree: str = "ABO", N_hor: int = 
         w_c, w_v, w_h, w_f = 0.1, 8e5, 1e4, 1e10
         OPT["W_AB"] = 1e-3 * np.array([w_c * 3e5, w_c * 1e7, w_v, w_h, w_f * 9e0, w_f])
     OPT["W_BL"] = np.array([1e2, 0.0, 0.0, 1e7])                             # :66-71 [w_v, w_a, w_j, w_f]
+    OPT["W_TV"] = np.array([1e2, 0.0, 0.0, 1e7])                             # :73-78 [w_v, w_a, w_j, w_f]
     Ts = OPT["Ts"]
     OPT.update(s_init=0.0, v_init=0 / 3.6, a_minus1=0.0)                     # :85-87
     OPT["FBuseTaylor"] = True                                                # :98
@@ -269,6 +270,8 @@ def Settings(OPT: Dict[str, Any] | None = None, tree: str = "ABO", N_hor: int = 
                BL_N_hor=OPT["N_hor"], BL_Ts=Ts, BL_trajEstSett=1)            # :131-139
     OPT.update(h_min=2.0, tau_min=0.5)                                       # :203-204
     OPT.update(TVlength=4.0, TVinitDist=10.0, TVinitVel=0.0, TV_N_hor=20, TV_Ts=0.5)  # :207-212
+    OPT.update(TV_trajEstSett=1, TV_a_LimLowVel=1.0, TV_a_LimHighVel=0.5, TV_j_LimLowVel=2.0, TV_j_LimHighVel=0.5)  # :213-218
+    OPT["TVMPCmaxIterHPIPM"] = 1000                                          # :117 (HPIPM form, not built)
     OPT.update(stopVel=0.2, stopRefDist=100.0, stopRefVelSlope=1.0, TLStopRegionSize=2.0,
                TLstopVel=-1.0, alpha_TTL=3.34)                               # :221-226
     OPT["b_quadr"] = np.array([185, 1.296e-20, 2.301, 0, 0.003728, -0.000181])  # :229
@@ -301,6 +304,27 @@ def Settings_BL(OPT: Dict[str, Any]) -> Dict[str, Any]:
     B.update(bl_mode=1, N_hor=N, Tvec=float(OPT["BL_Ts"]) * np.ones(N), Mb=np.zeros(N, dtype=np.int32),
              paramEstSetting=int(OPT["BL_trajEstSett"]))
     return B
+
+
+def Settings_TV(OPT: Dict[str, Any]) -> Dict[str, Any]:
+    """The view of OPTsettings that RunOpt_TVMPC takes (ABO/RunOpt_TVMPC.m:18-24, CreateQP_TV.m:26-39,
+    EstimateVehicleTrajectory.m:20-24, EstimateRouteAndComfortBounds.m:47-52): horizon TV_N_hor with the uniform step TV_Ts,
+    estimator TV_trajEstSett, weights W_TV and the target-vehicle comfort limits, carried in the fields of the baseline
+    controller (include/eepacc.h); bl_mode = 2 selects CreateQP_TV.
+
+    RunPlantModel.m steps the plant by Tvec(1) while RunOpt_TVMPC.m:153,277 differences and advances time by TV_Ts; a
+    handle has one step length, so TV_Ts must equal Tvec[0] (the reference's settings have both at Ts)."""
+    Ts = float(OPT["TV_Ts"])
+    if Ts != float(np.asarray(OPT["Tvec"]).ravel()[0]):
+        raise ValueError("TV_Ts = %g differs from Tvec[0] = %g: the plant model steps Tvec(1) (RunPlantModel.m), the "
+                         "target-vehicle MPC is built for TV_Ts == Tvec[0] only" % (Ts, float(np.asarray(OPT["Tvec"]).ravel()[0])))
+    T = dict(OPT)
+    N = int(OPT["TV_N_hor"])
+    T.update(bl_mode=2, N_hor=N, Tvec=Ts * np.ones(N), Mb=np.zeros(N, dtype=np.int32),
+             paramEstSetting=int(OPT["TV_trajEstSett"]), W_BL=np.asarray(OPT["W_TV"], dtype=np.float64),
+             BL_a_LimLowVel=OPT["TV_a_LimLowVel"], BL_a_LimHighVel=OPT["TV_a_LimHighVel"],
+             BL_j_LimLowVel=OPT["TV_j_LimLowVel"], BL_j_LimHighVel=OPT["TV_j_LimHighVel"])
+    return T
 
 
 def Run_DrivingCycle(OPT: Dict[str, Any], V_TO_10Hz: np.ndarray | None = None,

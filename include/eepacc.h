@@ -115,7 +115,20 @@ typedef struct eepacc_settings {
      * so it is solved by the proximal-point iteration  a_{j+1} = argmin LP(a) + bl_lp_eps/2 |a - a_j|^2,  a_0 = 0
      * (bl_lp_eps <= 0: 0.1), each solve warm from the last working set, until the point stays (at most bl_prox_iter
      * re-centrings; 0: 40, < 0: none, i.e. the single regularised solve of earlier versions): for a linear program that
-     * ends after finitely many steps at an optimum of the LP itself. */
+     * ends after finitely many steps at an optimum of the LP itself.
+     *
+     * Target-vehicle MPC (ABO/RunOpt_TVMPC.m, ABO/Functions/MPCs/CreateQP_TV.m).  bl_mode = 2 makes a handle a
+     * RunOpt_TVMPC, the controller that synthesises a lead vehicle's trace along the route.  It poses CreateQP_TV's
+     * problem (solverToUse 0 / 1 branch, z = [s v a xi_f]): CreateQP_BL's without the two headway rows per stage and the
+     * two rows of the terminal stage, with 0.8 of the speed-limit and curve caps (:262-272; stop and traffic-light caps
+     * unscaled) and the comfort limits evaluated at v_est = 0 (:44-45), i.e. the low-speed limits at every stage.  The
+     * struct has no fields of its own for it; the caller passes N_hor = TV_N_hor, Tvec[k] = TV_Ts (uniform; it is also
+     * the plant's step, RunPlantModel.m steps Tvec(1), so TV_Ts must equal the ego controller's Tvec(1)),
+     * paramEstSetting = TV_trajEstSett, W_BL = W_TV = [w_v, w_a, w_j, w_f] and BL_a_LimLowVel .. BL_j_LimHighVel =
+     * TV_a_LimLowVel .. TV_j_LimHighVel (ABO/Settings.m:73-78,207-218); bl_lp_eps / bl_prox_iter act as for bl_mode = 1
+     * (W_TV is a linear program too).  tau_min, h_min, TVestSetting and tConstACC_tar are not read.  Such a handle runs
+     * through eepacc_tv_step / eepacc_run_tvmpc / eepacc_run_tvmpc_host only; every ABMPC / BLMPC / FBMPC entry point
+     * returns EEPACC_EINVAL on it.  solverToUse = 2 (n_x = 3, hard +-8 m/s^2 bounds) stays EEPACC_ENOTSUP. */
     int32_t bl_mode, bl_prox_iter;
     double  W_BL[4];
     double  BL_a_LimLowVel, BL_a_LimHighVel, BL_j_LimLowVel, BL_j_LimHighVel;   /* ABO/Settings.m:131-134 */
@@ -243,6 +256,27 @@ int  eepacc_run_blmpc(eepacc_handle* h, int B, int n_steps,
 int  eepacc_run_blmpc_host(eepacc_handle* h, int B, int n_steps,
                            const double* s0, const double* v0, const double* a_minus1,
                            const double* s_tv, const double* v_tv,
+                           double* traj, int32_t* status);
+
+/* Target-vehicle MPC by name: [s_opt, v_opt, numSolverErrors] = RunOpt_TVMPC(OPTsettings) (ABO/RunOpt_TVMPC.m:1,
+ * ABO/Main.m:85) and the body of its loop (:156-277).  They require a handle created with bl_mode = 2 (EEPACC_EINVAL
+ * otherwise).  The controller follows no vehicle, so there are no lead inputs.  eepacc_tv_step: device inputs s, v, a_prev,
+ * t0 [B]; outputs as eepacc_ab_step.  eepacc_run_tvmpc: n_steps iterations (RunOpt_TVMPC runs t_sim/TV_Ts + 1) from
+ * s0 = TVinitDist, v0 = TVinitVel, a_minus1 [B]; t_0 starts at 0 and advances by TV_Ts, the previous solution starts as
+ * zeros (:126,134-141); traj [n_steps][EEPACC_OUT_N][B] with EEPACC_OUT_S / EEPACC_OUT_V = s_opt / v_opt and the xi_v,
+ * xi_h, xi_s entries zero; status [n_steps][B] mirrors exitMessage (numSolverErrors = its sum).  Like eepacc_run_abmpc a
+ * launch continues the previous one until eepacc_reset, so a long trace can be generated in chunks.  The trace can be
+ * handed on to eepacc_run_abmpc / _fbmpc / _blmpc of another handle on the device (after subtracting TVlength,
+ * ABO/Main.m:88): rows EEPACC_OUT_S and EEPACC_OUT_V of traj are the [n_steps][B] layout those read, with row stride
+ * EEPACC_OUT_N * B. */
+int  eepacc_tv_step(eepacc_handle* h, int B,
+                    const double* s, const double* v, const double* a_prev, const double* t0,
+                    double* out, double* s_pred, double* v_pred, int32_t* status, void* stream);
+int  eepacc_run_tvmpc(eepacc_handle* h, int B, int n_steps,
+                      const double* s0, const double* v0, const double* a_minus1,
+                      double* traj, int32_t* status, void* stream);
+int  eepacc_run_tvmpc_host(eepacc_handle* h, int B, int n_steps,
+                           const double* s0, const double* v0, const double* a_minus1,
                            double* traj, int32_t* status);
 
 /* Post-processing of a closed-loop trajectory (ABO/RunOpt_ABMPC.m:343-349): rpm, Tm,

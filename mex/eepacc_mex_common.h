@@ -181,9 +181,13 @@ static void emx_read_inputs(const mxArray* O, int fb, eepacc_mex_inputs* in) {
     in->Ts = S->Tvec[0];
     in->n_steps = (int)floor(emx_scalar(O, "t_sim") / in->Ts + 0.5) + 1;      /* kk = 0:N_sim (:154) */
     in->s_init = emx_scalar(O, "s_init"); in->v_init = emx_scalar(O, "v_init"); in->a_minus1 = emx_scalar(O, "a_minus1");
+#ifdef EEPACC_MEX_NO_LEAD              /* RunOpt_TVMPC.c: the target-vehicle MPC follows nobody, OPTsettings need not hold a lead trace */
+    in->s_tv = NULL; in->v_tv = NULL;
+#else
     in->s_tv = emx_vector(O, "s_tv", &n, 1); in->v_tv = emx_vector(O, "v_tv", &n2, 1);
     if (n < in->n_steps || n2 < in->n_steps)
         mexErrMsgIdAndTxt("eepacc:badField", "s_tv / v_tv must hold t_sim/Ts + 1 = %d samples", in->n_steps);
+#endif
     emx_vehicle(&in->V);
 }
 
