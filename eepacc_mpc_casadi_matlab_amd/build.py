@@ -6,6 +6,7 @@ built with other flags (e.g. the -DEEPACC_AB_TIMING / -DEEPACC_DEBUG_STATUS inst
 change the meaning of the iteration and status outputs) is stale and gets rebuilt."""
 from __future__ import annotations
 
+import glob
 import os
 import subprocess
 from concurrent.futures import ThreadPoolExecutor
@@ -16,8 +17,6 @@ OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libeepacc.so")
 FLAGFILE = os.path.join(HERE, "libeepacc.flags")
 SOURCES = ["eepacc_kernels.hip", "eepacc_qp_dense.hip", "eepacc_fb.hip", "eepacc_fbs.hip", "eepacc_capi.cpp", "eepacc_casadi_c.cpp", "eepacc_nlp.hip", "eepacc_nlp_tables.cpp"]
-HEADERS = ["eepacc_device.h", "eepacc_qp_dense.h", "eepacc_fb.h", "eepacc_stage.h", "eepacc_wave.h", "eepacc_fbs.h", "eepacc_units.h", "eepacc_schur.h", "eepacc_ab_impl.inc", "eepacc_nlp_solve.inc", os.path.join("..", "..", "include", "eepacc.h"),
-           os.path.join("..", "..", "include", "eepacc_casadi_c.h"), os.path.join("..", "..", "include", "eepacc_nlp.h")]
 BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 
 
@@ -33,12 +32,18 @@ def built_flags() -> str | None:
         return None
 
 
+def headers() -> list[str]:
+    """Everything a source can include: a change to any of them makes every object stale."""
+    inc = os.path.join(HERE, os.pardir, "include")
+    return glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + glob.glob(os.path.join(inc, "*.h"))
+
+
 def is_stale() -> bool:
     if not os.path.exists(LIB) or built_flags() != extra_flags():
         return True
     t = os.path.getmtime(LIB)
-    return any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in SOURCES + HEADERS
-               if os.path.exists(os.path.join(CSRC, f)))
+    srcs = [os.path.join(CSRC, f) for f in SOURCES if os.path.exists(os.path.join(CSRC, f))]
+    return any(os.path.getmtime(f) > t for f in srcs + headers())
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -48,7 +53,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     flags = extra_flags()
     os.makedirs(OBJ, exist_ok=True)
     srcs = [s for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
-    newest_hdr = max(os.path.getmtime(os.path.join(CSRC, f)) for f in HEADERS if os.path.exists(os.path.join(CSRC, f)))
+    newest_hdr = max(os.path.getmtime(f) for f in headers())
     same_flags = built_flags() == flags
 
     def compile_one(src: str) -> str:

@@ -1,10 +1,9 @@
-// eepacc_ab_impl.inc -- device code of the ABMPC kernels.  Included six times by eepacc_kernels.hip: once
-// per value of EEPACC_IMPL_MB (move blocking compiled out / in), once with EEPACC_IMPL_BL (the baseline
-// controller's row grouping, CreateQP_BL.m: one slack for all soft rows), once with EEPACC_IMPL_BL and EEPACC_IMPL_TV
-// (the target-vehicle MPC, CreateQP_TV.m: the baseline QP without its vehicle-following rows and without lead inputs)
-// and twice with EEPACC_IMPL_ICE (the ICE-map fuel term, whose Hessian is built and inverted every step; without /
-// with move blocking), each time into its own namespace, so that the default path carries no register or instruction
-// cost for the variants.
+// eepacc_ab_impl.inc -- device code of the ABMPC kernels.  Included by eepacc_kernels.hip once per entry of its
+// EEPACC_AB_VARIANTS list, each time into its own namespace EEPACC_IMPL_NS with the four switches EEPACC_IMPL_MB (move
+// blocking compiled out / in), EEPACC_IMPL_BL (the baseline controller's row grouping, CreateQP_BL.m: one slack for all
+// soft rows), EEPACC_IMPL_TV (with _BL: the target-vehicle MPC, CreateQP_TV.m: the baseline QP without its
+// vehicle-following rows and without lead inputs) and EEPACC_IMPL_ICE (the ICE-map fuel term, whose Hessian is built and
+// inverted every step), so that the default path carries no register or instruction cost for the variants.
 // The tables of the active-set method (the inverse He of the effective Hessian, the inverse Schur block P of the working
 // set) are maintained by eepacc_schur.h, which the FBMPC kernels share; it is included once, outside these namespaces.
 namespace eepacc {
@@ -13,16 +12,8 @@ using namespace wv;
 
 constexpr bool kMoveBlocking = EEPACC_IMPL_MB;
 constexpr bool kBaseline = EEPACC_IMPL_BL;
-#ifdef EEPACC_IMPL_ICE
 constexpr bool kIce = EEPACC_IMPL_ICE;      // ICE-map fuel term (CreateQP_AB.m:154-159): the Hessian changes every step
-#else
-constexpr bool kIce = false;
-#endif
-#ifdef EEPACC_IMPL_TV
 constexpr bool kTargetVeh = EEPACC_IMPL_TV;     // RunOpt_TVMPC (CreateQP_TV.m): a baseline variant (kBaseline is set too)
-#else
-constexpr bool kTargetVeh = false;
-#endif
 static_assert(!kTargetVeh || kBaseline, "the target-vehicle MPC is a variant of the baseline controller");
 
 
@@ -1690,35 +1681,6 @@ k_run_abmpc(const DevCfg* __restrict__ Cp, int B, int k_start, int n_steps,
         if (lane == 0) cs.store(carry, B, b);
         return it_total;
     });
-}
-
-// A10: post-processing (ABO/RunOpt_ABMPC.m:343-349), one thread per instance, sequential in time
-__global__ void k_postprocess(const DevCfg* __restrict__ Cp, int B, int n_steps, const double* __restrict__ traj,
-                              double* __restrict__ rpm, double* __restrict__ Tm, double* __restrict__ P,
-                              double* __restrict__ E) {
-    const DevCfg& C = *Cp;
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const double Ts = C.Tvec[0];
-    double acc = 0.0;
-    const double kr = (30.0 / 3.14159265358979323846);
-    for (int k = 0; k < n_steps; ++k) {
-        const double v = traj[((size_t)k * EEPACC_OUT_N + EEPACC_OUT_V) * B + b];
-        const double x = traj[((size_t)k * EEPACC_OUT_N + EEPACC_OUT_FM) * B + b];
-        const double y = kr * v * C.phi;
-        const double sg = (x > 0.0) ? 1.0 : ((x < 0.0) ? -1.0 : 0.0);
-        const double tm = x / C.phi / pow(C.eta_TF, sg);
-        const double* bb = C.b5;
-        const double x2 = x * x, x3 = x2 * x, x4 = x3 * x, x5 = x4 * x;
-        const double y2 = y * y, y3 = y2 * y, y4 = y3 * y, y5 = y4 * y;
-        const double p = bb[0] + bb[1] * x + bb[2] * y + bb[3] * x2 + bb[4] * x * y + bb[5] * y2 + bb[6] * x3 +
-                         bb[7] * x2 * y + bb[8] * x * y2 + bb[9] * y3 + bb[10] * x4 + bb[11] * x3 * y +
-                         bb[12] * x2 * y2 + bb[13] * x * y3 + bb[14] * y4 + bb[15] * x5 + bb[16] * x4 * y +
-                         bb[17] * x3 * y2 + bb[18] * x2 * y3 + bb[19] * x * y4 + bb[20] * y5;
-        acc += p;
-        const size_t o = (size_t)k * B + b;
-        rpm[o] = y; Tm[o] = tm; P[o] = p; E[o] = Ts * acc;
-    }
 }
 
 }  // namespace EEPACC_IMPL_NS

@@ -7,29 +7,13 @@
 #include <string.h>
 #include <string>
 #include <vector>
+#include <memory>
 #include "eepacc_device.h"
+#include "eepacc_ab.h"
 #include "eepacc_qp_dense.h"
 #include "eepacc_fb.h"
 #include "eepacc_fbs.h"
 #include "../../include/eepacc.h"
-
-namespace eepacc {
-size_t ab_smem_bytes(int N);
-size_t ab_hb_doubles(int N, int B, int num_cus);
-hipError_t launch_ab_step(const DevCfg* dC, int N, int variant, int B, const double* s, const double* v, const double* a_prev,
-                          const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
-                          unsigned long long* codes, double* out, double* s_pred, double* v_pred,
-                          int32_t* status, int32_t* iters, hipStream_t stream);
-hipError_t launch_run_abmpc(const DevCfg* dC, int N, int variant, int B, int k_start, int n_steps, const double* s0,
-                            const double* v0, const double* a_m1, const double* s_tv, const double* v_tv,
-                            double* carry, unsigned long long* codes, double* traj,
-                            int32_t* status, int32_t* iters_total, int* work_counter, int* done, int* err_word, int num_cus,
-                            hipStream_t stream);
-hipError_t launch_postprocess(const DevCfg* dC, int B, int n_steps, const double* traj, double* rpm, double* Tm,
-                              double* P, double* E, hipStream_t stream);
-hipError_t set_max_smem();
-int pick_chunk_steps(int n_steps, int B, int resident_waves);
-}  // namespace eepacc
 
 using eepacc::DevCfg;
 
@@ -38,40 +22,59 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 namespace eepacc { int set_error(int code, const std::string& msg) { return fail(code, msg); } }   // other translation units (eepacc_nlp.hip)
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(EEPACC_EDEVICE, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 
+// Device memory owned by a handle or by a host-pointer wrapper: move-only, freed with its owner.
+template <class T> struct DevMem {
+    T* p = nullptr;
+    DevMem() = default;
+    DevMem(DevMem&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevMem& operator=(DevMem&& o) noexcept { if (this != &o) { release(); p = o.p; o.p = nullptr; } return *this; }
+    ~DevMem() { release(); }
+    void release() { if (p) (void)hipFree(p); p = nullptr; }
+    hipError_t alloc(size_t n) { release(); return hipMalloc(&p, n * sizeof(T)); }
+    hipError_t alloc_zero(size_t n) { const hipError_t e = alloc(n); return e != hipSuccess ? e : hipMemset(p, 0, n * sizeof(T)); }
+    operator T*() const { return p; }
+};
+
+// dense FBMPC path (eepacc_fb.hip + the dense QP operator): buffers for B instances, allocated on first use
+struct FbDense {
+    int B = 0, chunk = 0;
+    DevMem<double> H, g, A, lba, uba;                      // [chunk]
+    DevMem<double> x, x0, cost, meas, carry, A22, D2;      // [B]
+    DevMem<double> sp, vp;                                 // [N+1][B] predictions of the last step
+    DevMem<int32_t> qpstat;
+    DevMem<int> rhok;                                      // [B] regularisation exponent found at the previous step
+};
+
 struct eepacc_handle {
     int device = 0;
     int max_batch = 0;
     DevCfg cfg;
-    DevCfg* d_cfg = nullptr;
-    double* d_Hinv = nullptr;
-    double* d_hb = nullptr;          // ICE variant: per-wave base inverse of the step
-    double* d_pred = nullptr;                // [max_batch][2][64] previous predictions (paramEstSetting 2)
-    unsigned long long* d_codes = nullptr;   // [max_batch][64]
-    int32_t* d_iters = nullptr;              // [max_batch]
-    double* d_carry = nullptr;               // [6][B] closed-loop carry (see Carry, eepacc_units.h)
-    int* d_counter = nullptr;                // work counter of the closed-loop kernel
-    int* d_done = nullptr;                   // [max_batch] chunks finished per instance
-    int* d_err = nullptr;                    // sticky device error word (bit 0: a closed-loop hand-off timed out)
+    DevMem<DevCfg> d_cfg;
+    DevMem<double> d_Hinv;
+    DevMem<double> d_hb;                     // ICE variant: per-wave base inverse of the step
+    DevMem<double> d_pred;                   // [max_batch][2][64] previous predictions (paramEstSetting 2)
+    DevMem<unsigned long long> d_codes;      // [max_batch][64]
+    DevMem<int32_t> d_iters;                 // [max_batch]
+    DevMem<double> d_carry;                  // [6][B] closed-loop carry (see Carry, eepacc_units.h)
+    DevMem<int> d_counter;                   // work counter of the closed-loop kernel
+    DevMem<int> d_done;                      // [max_batch] chunks finished per instance
+    DevMem<int> d_err;                       // sticky device error word (bit 0: a closed-loop hand-off timed out)
     int num_cus = 256;
+    // Resume bookkeeping.  ABMPC / TVMPC resume on k_done / carry_B.  FBMPC resumes on fb_k_done and compares B with last_B,
+    // which every step and closed-loop entry point writes, the ABMPC ones included: an ABMPC call between two FBMPC launches
+    // changes what the FBMPC resume check sees.
     int last_B = 0;
     int k_done = 0;                          // closed-loop steps already run since the last reset
     int carry_B = 0;
-    double* d_qp_ws = nullptr;               // workspace of the dense QP operator
+    DevMem<double> d_qp_ws;                  // workspace of the dense QP operator
     size_t qp_ws_doubles = 0;
-    int* d_qp_counter = nullptr;
-    // FBMPC state (allocated on first use)
-    int fb_B = 0, fb_chunk = 0;
+    DevMem<int> d_qp_counter;
     int fb_k_done = 0;
     bool fb_by_step = false;                 // the FB step counter was advanced by eepacc_fb_step (no closed-loop carry to resume from)
-    double *fb_H = nullptr, *fb_g = nullptr, *fb_A = nullptr, *fb_lba = nullptr, *fb_uba = nullptr;   // [fb_chunk]
-    double *fb_x = nullptr, *fb_x0 = nullptr, *fb_cost = nullptr, *fb_meas = nullptr, *fb_carry = nullptr;   // [fb_B]
-    double *fb_A22 = nullptr, *fb_D2 = nullptr;
-    double *fb_sp = nullptr, *fb_vp = nullptr;   // [N+1][fb_B] predictions of the last step
-    int32_t* fb_qpstat = nullptr;
-    int* fb_rhok = nullptr;                  // [fb_B] regularisation exponent found at the previous step
+    FbDense fb;
     // structured FBMPC path (eepacc_fbs.hip): per-instance state, closed-loop carry, base-inverse scratch
     bool fbs = false;                        // settings are covered by the structured solver
-    double *fbs_state = nullptr, *fbs_carry = nullptr, *fbs_hb = nullptr;
+    DevMem<double> fbs_state, fbs_carry, fbs_hb;
 };
 
 extern "C" const char* eepacc_last_error(void) { return g_err.c_str(); }
@@ -97,10 +100,6 @@ static bool spd_inverse(std::vector<long double>& A, int n) {
     A.swap(I);
     return true;
 }
-
-// kernel variant of a handle: 0 plain, 1 blocked moves, 2 baseline controller, 3 ICE-map fuel term, 4 ICE-map with blocked moves,
-// 5 target-vehicle MPC
-static int ab_variant(const DevCfg& C) { return C.bl_mode == 2 ? 5 : C.bl_mode ? 2 : (C.ab_fuel_term == 2 ? (C.mb_any ? 4 : 3) : (C.mb_any ? 1 : 0)); }
 
 static int build_cfg(const eepacc_settings* S, const eepacc_vehicle* V, DevCfg& C, std::vector<double>& Hinv) {
     memset(&C, 0, sizeof(C));
@@ -289,92 +288,49 @@ extern "C" int eepacc_create(eepacc_handle** out, const eepacc_settings* S, cons
     if (ndev < 1) return fail(EEPACC_EDEVICE, "no HIP device: libeepacc has no CPU path");
     if (device < 0 || device >= ndev) return fail(EEPACC_EINVAL, "device ordinal out of range");
     HIPCHK(hipSetDevice(device));
-    // the handle is destroyed (and everything allocated so far freed) if any later step fails
-    struct Guard { eepacc_handle* h; ~Guard() { if (h) eepacc_destroy(h); } } guard{new eepacc_handle()};
-    eepacc_handle* h = guard.h;
+    // the handle owns its device memory: everything allocated so far is freed if any later step fails
+    std::unique_ptr<eepacc_handle> h(new eepacc_handle());
     h->device = device; h->max_batch = max_batch;
-    HIPCHK(hipMalloc(&h->d_Hinv, Hinv.size() * sizeof(double)));
+    const size_t nB = (size_t)max_batch;
+    HIPCHK(h->d_Hinv.alloc(Hinv.size()));
     HIPCHK(hipMemcpy(h->d_Hinv, Hinv.data(), Hinv.size() * sizeof(double), hipMemcpyHostToDevice));
     C.Hinv = h->d_Hinv;
-    HIPCHK(hipMalloc(&h->d_pred, (size_t)max_batch * 128 * sizeof(double)));
-    HIPCHK(hipMemset(h->d_pred, 0, (size_t)max_batch * 128 * sizeof(double)));
+    HIPCHK(h->d_pred.alloc_zero(nB * 128));
     C.pred = h->d_pred;
-    {
-        hipDeviceProp_t prop;
-        HIPCHK(hipGetDeviceProperties(&prop, device));
-        h->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device));
+    h->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     if (C.ab_fuel_term == 2 && !C.bl_mode) {
-        HIPCHK(hipMalloc(&h->d_hb, eepacc::ab_hb_doubles(C.N, max_batch, h->num_cus) * sizeof(double)));
+        HIPCHK(h->d_hb.alloc(eepacc::ab_hb_doubles(C.N, max_batch, h->num_cus)));
         C.hb = h->d_hb;
     }
     h->cfg = C;
-    HIPCHK(hipMalloc(&h->d_cfg, sizeof(DevCfg)));
+    HIPCHK(h->d_cfg.alloc(1));
     HIPCHK(hipMemcpy(h->d_cfg, &C, sizeof(DevCfg), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&h->d_codes, (size_t)max_batch * 64 * sizeof(unsigned long long)));
-    HIPCHK(hipMemset(h->d_codes, 0, (size_t)max_batch * 64 * sizeof(unsigned long long)));
-    HIPCHK(hipMalloc(&h->d_iters, (size_t)max_batch * sizeof(int32_t)));
-    HIPCHK(hipMemset(h->d_iters, 0, (size_t)max_batch * sizeof(int32_t)));
-    HIPCHK(hipMalloc(&h->d_carry, (size_t)max_batch * 6 * sizeof(double)));
-    HIPCHK(hipMemset(h->d_carry, 0, (size_t)max_batch * 6 * sizeof(double)));
-    HIPCHK(hipMalloc(&h->d_counter, sizeof(int)));
-    HIPCHK(hipMalloc(&h->d_done, sizeof(int) * (size_t)max_batch));
-    HIPCHK(hipMalloc(&h->d_err, sizeof(int)));
-    HIPCHK(hipMemset(h->d_err, 0, sizeof(int)));
-    HIPCHK(hipMalloc(&h->d_qp_counter, sizeof(int)));
-    {
-        hipDeviceProp_t prop;
-        HIPCHK(hipGetDeviceProperties(&prop, device));
-        h->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
+    HIPCHK(h->d_codes.alloc_zero(nB * 64));
+    HIPCHK(h->d_iters.alloc_zero(nB));
+    HIPCHK(h->d_carry.alloc_zero(nB * 6));
+    HIPCHK(h->d_counter.alloc(1));
+    HIPCHK(h->d_done.alloc(nB));
+    HIPCHK(h->d_err.alloc_zero(1));
+    HIPCHK(h->d_qp_counter.alloc(1));
     HIPCHK(eepacc::set_max_smem());
     // FBMPC: structured kernels unless the settings need the dense path (or EEPACC_FB_DENSE=1 asks for it)
     h->fbs = eepacc::fbs_supported(C) && eepacc::fbs_smem_bytes(C.N) <= 160 * 1024 - 4608;
     if (const char* e = getenv("EEPACC_FB_DENSE")) if (atoi(e) != 0) h->fbs = false;
     if (h->fbs) {
         HIPCHK(eepacc::fbs_set_max_smem());
-        const size_t ns = (size_t)max_batch * eepacc::kFbsStateDoubles;
-        HIPCHK(hipMalloc(&h->fbs_state, ns * sizeof(double)));
-        HIPCHK(hipMemset(h->fbs_state, 0, ns * sizeof(double)));
-        HIPCHK(hipMalloc(&h->fbs_carry, (size_t)max_batch * 6 * sizeof(double)));
-        HIPCHK(hipMemset(h->fbs_carry, 0, (size_t)max_batch * 6 * sizeof(double)));
-        HIPCHK(hipMalloc(&h->fbs_hb, eepacc::fbs_hb_doubles(C.N, max_batch, h->num_cus) * sizeof(double)));
+        HIPCHK(h->fbs_state.alloc_zero(nB * eepacc::kFbsStateDoubles));
+        HIPCHK(h->fbs_carry.alloc_zero(nB * 6));
+        HIPCHK(h->fbs_hb.alloc(eepacc::fbs_hb_doubles(C.N, max_batch, h->num_cus)));
     }
-    guard.h = nullptr;
-    *out = h;
+    *out = h.release();
     return EEPACC_OK;
-}
-
-static void fb_free(eepacc_handle* h) {
-    double** ptrs[] = {&h->fb_H, &h->fb_g, &h->fb_A, &h->fb_lba, &h->fb_uba, &h->fb_x, &h->fb_x0, &h->fb_cost,
-                       &h->fb_meas, &h->fb_carry, &h->fb_A22, &h->fb_D2, &h->fb_sp, &h->fb_vp};
-    for (double** p : ptrs) { if (*p) (void)hipFree(*p); *p = nullptr; }
-    if (h->fb_qpstat) (void)hipFree(h->fb_qpstat);
-    h->fb_qpstat = nullptr;
-    if (h->fb_rhok) (void)hipFree(h->fb_rhok);
-    h->fb_rhok = nullptr;
-    h->fb_B = 0; h->fb_chunk = 0;
 }
 
 extern "C" void eepacc_destroy(eepacc_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    if (h->d_cfg) (void)hipFree(h->d_cfg);
-    if (h->d_Hinv) (void)hipFree(h->d_Hinv);
-    if (h->d_hb) (void)hipFree(h->d_hb);
-    if (h->d_pred) (void)hipFree(h->d_pred);
-    if (h->d_codes) (void)hipFree(h->d_codes);
-    if (h->d_iters) (void)hipFree(h->d_iters);
-    if (h->d_carry) (void)hipFree(h->d_carry);
-    if (h->d_counter) (void)hipFree(h->d_counter);
-    if (h->d_done) (void)hipFree(h->d_done);
-    if (h->d_err) (void)hipFree(h->d_err);
-    if (h->fbs_state) (void)hipFree(h->fbs_state);
-    if (h->fbs_carry) (void)hipFree(h->fbs_carry);
-    if (h->fbs_hb) (void)hipFree(h->fbs_hb);
-    if (h->d_qp_ws) (void)hipFree(h->d_qp_ws);
-    if (h->d_qp_counter) (void)hipFree(h->d_qp_counter);
-    fb_free(h);
     delete h;
 }
 
@@ -387,56 +343,105 @@ extern "C" int eepacc_reset(eepacc_handle* h) {
     h->k_done = 0; h->carry_B = 0;
     h->fb_k_done = 0; h->fb_by_step = false;
     if (h->fbs_state) HIPCHK(hipMemset(h->fbs_state, 0, (size_t)h->max_batch * eepacc::kFbsStateDoubles * sizeof(double)));
-    if (h->fb_x0) HIPCHK(hipMemset(h->fb_x0, 0, (size_t)h->fb_B * 6 * h->cfg.N * sizeof(double)));
-    if (h->fb_sp) {
-        HIPCHK(hipMemset(h->fb_sp, 0, (size_t)h->fb_B * (h->cfg.N + 1) * sizeof(double)));
-        HIPCHK(hipMemset(h->fb_vp, 0, (size_t)h->fb_B * (h->cfg.N + 1) * sizeof(double)));
+    if (h->fb.x0) HIPCHK(hipMemset(h->fb.x0, 0, (size_t)h->fb.B * 6 * h->cfg.N * sizeof(double)));
+    if (h->fb.sp) {
+        HIPCHK(hipMemset(h->fb.sp, 0, (size_t)h->fb.B * (h->cfg.N + 1) * sizeof(double)));
+        HIPCHK(hipMemset(h->fb.vp, 0, (size_t)h->fb.B * (h->cfg.N + 1) * sizeof(double)));
     }
     return EEPACC_OK;
 }
 
-// a handle created with bl_mode = 2 poses RunOpt_TVMPC's problem and takes no lead inputs: only the eepacc_tv_* / eepacc_run_tvmpc*
-// entry points run it
+// The kind of a handle decides which entry points run it.  One created with bl_mode = 2 poses RunOpt_TVMPC's problem and takes
+// no lead inputs: only eepacc_tv_step / eepacc_run_tvmpc* run it (need_tv), every other one refuses it (not_tv).  The
+// eepacc_bl_* names are the ABMPC entry points for a handle that was created as the baseline controller (need_bl).
 static int not_tv(const eepacc_handle* h, const char* who) {
-    if (h && h->cfg.bl_mode == 2)
+    if (!h) return fail(EEPACC_EINVAL, "NULL handle");
+    if (h->cfg.bl_mode == 2)
         return fail(EEPACC_EINVAL, std::string(who) + ": this handle was created with bl_mode = 2 (RunOpt_TVMPC); use eepacc_tv_step / eepacc_run_tvmpc");
     return EEPACC_OK;
 }
+static int need_mode(const eepacc_handle* h, int bl_mode, const char* name) {
+    if (!h) return fail(EEPACC_EINVAL, "NULL handle");
+    if (h->cfg.bl_mode != bl_mode)
+        return fail(EEPACC_EINVAL, "this handle was not created with bl_mode = " + std::to_string(bl_mode) + " (" + name + ")");
+    return EEPACC_OK;
+}
+static int need_bl(const eepacc_handle* h) { return need_mode(h, 1, "RunOpt_BLMPC"); }
+static int need_tv(const eepacc_handle* h) { return need_mode(h, 2, "RunOpt_TVMPC"); }
 
+// One step of the ABMPC kernels of the handle's variant.  A target-vehicle handle has no lead inputs: its kernels read none
+// and the launcher gets null pointers.
+static int ab_step_impl(eepacc_handle* h, const char* who, int B, const double* s, const double* v, const double* a_prev,
+                        const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                        double* out, double* s_pred, double* v_pred, int32_t* status, void* stream) {
+    const bool tv = h->cfg.bl_mode == 2;
+    if (B < 0 || B > h->max_batch) return fail(EEPACC_EINVAL, "B exceeds max_batch of the handle");
+    if (B == 0) return EEPACC_OK;
+    if (!s || !v || !a_prev || !t0 || (!tv && (!s_tv || !v_tv || !a_tv_prev)) || !out || !status)
+        return fail(EEPACC_EINVAL, std::string(who) + ": NULL buffer");
+    HIPCHK(hipSetDevice(h->device));
+    h->last_B = B;
+    HIPCHK(eepacc::launch_ab_step(h->d_cfg, h->cfg.N, eepacc::ab_variant(h->cfg), B, s, v, a_prev, t0, tv ? nullptr : s_tv,
+                                  tv ? nullptr : v_tv, tv ? nullptr : a_tv_prev, h->d_codes, out, s_pred, v_pred, status,
+                                  h->d_iters, (hipStream_t)stream));
+    return EEPACC_OK;
+}
+
+// The closed loop of the same kernels; bad_sizes is the entry point's own wording of that refusal.
+static int ab_run_impl(eepacc_handle* h, const char* who, const char* bad_sizes, int B, int n_steps, const double* s0,
+                       const double* v0, const double* a_minus1, const double* s_tv, const double* v_tv, double* traj,
+                       int32_t* status, void* stream) {
+    const bool tv = h->cfg.bl_mode == 2;
+    if (B < 0 || B > h->max_batch || n_steps < 0) return fail(EEPACC_EINVAL, bad_sizes);
+    if (B == 0 || n_steps == 0) return EEPACC_OK;
+    if (!s0 || !v0 || !a_minus1 || (!tv && (!s_tv || !v_tv)) || !traj || !status)
+        return fail(EEPACC_EINVAL, std::string(who) + ": NULL buffer");
+    HIPCHK(hipSetDevice(h->device));
+    if (h->k_done > 0 && h->carry_B != B)
+        return fail(EEPACC_EINVAL, std::string(who) + ": B changed while resuming; call eepacc_reset first");
+    h->last_B = B;
+    HIPCHK(eepacc::launch_run_abmpc(h->d_cfg, h->cfg.N, eepacc::ab_variant(h->cfg), B, h->k_done, n_steps, s0, v0, a_minus1,
+                                    tv ? nullptr : s_tv, tv ? nullptr : v_tv, h->d_carry, h->d_codes, traj, status, h->d_iters,
+                                    h->d_counter, h->d_done, h->d_err, h->num_cus, (hipStream_t)stream));
+    h->k_done += n_steps; h->carry_B = B;
+    return EEPACC_OK;
+}
+
+// eepacc_bl_step / eepacc_run_blmpc report as the ABMPC entry points they stand for
 extern "C" int eepacc_ab_step(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
                               const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
                               double* out, double* s_pred, double* v_pred, int32_t* status, void* stream) {
-    if (!h) return fail(EEPACC_EINVAL, "NULL handle");
-    { const int rc = not_tv(h, "eepacc_ab_step"); if (rc != EEPACC_OK) return rc; }
-    if (B < 0 || B > h->max_batch) return fail(EEPACC_EINVAL, "B exceeds max_batch of the handle");
-    if (B == 0) return EEPACC_OK;
-    if (!s || !v || !a_prev || !t0 || !s_tv || !v_tv || !a_tv_prev || !out || !status)
-        return fail(EEPACC_EINVAL, "eepacc_ab_step: NULL buffer");
-    HIPCHK(hipSetDevice(h->device));
-    h->last_B = B;
-    HIPCHK(eepacc::launch_ab_step(h->d_cfg, h->cfg.N, ab_variant(h->cfg), B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, h->d_codes, out,
-                                  s_pred, v_pred, status, h->d_iters, (hipStream_t)stream));
-    return EEPACC_OK;
+    const int rc = not_tv(h, "eepacc_ab_step");
+    return rc != EEPACC_OK ? rc : ab_step_impl(h, "eepacc_ab_step", B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, out, s_pred, v_pred, status, stream);
+}
+extern "C" int eepacc_bl_step(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
+                              const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                              double* out, double* s_pred, double* v_pred, int32_t* status, void* stream) {
+    const int rc = need_bl(h);
+    return rc != EEPACC_OK ? rc : ab_step_impl(h, "eepacc_ab_step", B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, out, s_pred, v_pred, status, stream);
+}
+extern "C" int eepacc_tv_step(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
+                              const double* t0, double* out, double* s_pred, double* v_pred, int32_t* status, void* stream) {
+    const int rc = need_tv(h);
+    return rc != EEPACC_OK ? rc : ab_step_impl(h, "eepacc_tv_step", B, s, v, a_prev, t0, nullptr, nullptr, nullptr, out, s_pred, v_pred, status, stream);
 }
 
 extern "C" int eepacc_run_abmpc(eepacc_handle* h, int B, int n_steps, const double* s0, const double* v0,
                                 const double* a_minus1, const double* s_tv, const double* v_tv, double* traj,
                                 int32_t* status, void* stream) {
-    if (!h) return fail(EEPACC_EINVAL, "NULL handle");
-    { const int rc = not_tv(h, "eepacc_run_abmpc"); if (rc != EEPACC_OK) return rc; }
-    if (B < 0 || B > h->max_batch || n_steps < 0) return fail(EEPACC_EINVAL, "bad B / n_steps");
-    if (B == 0 || n_steps == 0) return EEPACC_OK;
-    if (!s0 || !v0 || !a_minus1 || !s_tv || !v_tv || !traj || !status)
-        return fail(EEPACC_EINVAL, "eepacc_run_abmpc: NULL buffer");
-    HIPCHK(hipSetDevice(h->device));
-    if (h->k_done > 0 && h->carry_B != B)
-        return fail(EEPACC_EINVAL, "eepacc_run_abmpc: B changed while resuming; call eepacc_reset first");
-    h->last_B = B;
-    HIPCHK(eepacc::launch_run_abmpc(h->d_cfg, h->cfg.N, ab_variant(h->cfg), B, h->k_done, n_steps, s0, v0, a_minus1, s_tv, v_tv,
-                                    h->d_carry, h->d_codes, traj, status, h->d_iters, h->d_counter, h->d_done, h->d_err, h->num_cus,
-                                    (hipStream_t)stream));
-    h->k_done += n_steps; h->carry_B = B;
-    return EEPACC_OK;
+    const int rc = not_tv(h, "eepacc_run_abmpc");
+    return rc != EEPACC_OK ? rc : ab_run_impl(h, "eepacc_run_abmpc", "bad B / n_steps", B, n_steps, s0, v0, a_minus1, s_tv, v_tv, traj, status, stream);
+}
+extern "C" int eepacc_run_blmpc(eepacc_handle* h, int B, int n_steps, const double* s0, const double* v0,
+                                const double* a_minus1, const double* s_tv, const double* v_tv, double* traj,
+                                int32_t* status, void* stream) {
+    const int rc = need_bl(h);
+    return rc != EEPACC_OK ? rc : ab_run_impl(h, "eepacc_run_abmpc", "bad B / n_steps", B, n_steps, s0, v0, a_minus1, s_tv, v_tv, traj, status, stream);
+}
+extern "C" int eepacc_run_tvmpc(eepacc_handle* h, int B, int n_steps, const double* s0, const double* v0,
+                                const double* a_minus1, double* traj, int32_t* status, void* stream) {
+    const int rc = need_tv(h);
+    return rc != EEPACC_OK ? rc : ab_run_impl(h, "eepacc_run_tvmpc", "eepacc_run_tvmpc: bad B / n_steps", B, n_steps, s0, v0, a_minus1, nullptr, nullptr, traj, status, stream);
 }
 
 extern "C" int eepacc_postprocess(eepacc_handle* h, int B, int n_steps, const double* traj, double* rpm,
@@ -485,8 +490,9 @@ static int qp_grid(const eepacc_handle* h, int B) {
 static int qp_workspace(eepacc_handle* h, int grid, int nV) {
     size_t need = (size_t)grid * eepacc_qp_dense_ws_doubles(nV);
     if (need > h->qp_ws_doubles) {
-        if (h->d_qp_ws) { HIPCHK(hipDeviceSynchronize()); (void)hipFree(h->d_qp_ws); h->d_qp_ws = nullptr; h->qp_ws_doubles = 0; }
-        if (hipMalloc(&h->d_qp_ws, need * sizeof(double)) != hipSuccess) return fail(EEPACC_ENOMEM, "dense QP workspace allocation failed");
+        if (h->d_qp_ws) HIPCHK(hipDeviceSynchronize());
+        h->qp_ws_doubles = 0;
+        if (h->d_qp_ws.alloc(need) != hipSuccess) return fail(EEPACC_ENOMEM, "dense QP workspace allocation failed");
         h->qp_ws_doubles = need;
     }
     return EEPACC_OK;
@@ -523,39 +529,30 @@ static int fb_prepare(eepacc_handle* h, int B) {
     const size_t nV = 6 * (size_t)N, nC = (size_t)h->cfg.fb_row0[N] + 2;
     if (nV > EEPACC_QP_MAX_NV || nC > EEPACC_QP_MAX_NC || eepacc_qp_dense_lds_bytes((int)nV, (int)nC) > 160 * 1024)
         return fail(EEPACC_ENOTSUP, "FBMPC: horizon too long for the dense QP operator");
-    if (B <= h->fb_B) return EEPACC_OK;
+    if (B <= h->fb.B) return EEPACC_OK;
     HIPCHK(hipDeviceSynchronize());
-    fb_free(h);
+    FbDense& f = h->fb;
+    f = FbDense();
     // the dense QP data is held for a chunk of instances at a time (about 16 GB at most)
     const size_t per = (nV * nV + nC * nV + nV + 2 * nC) * sizeof(double);
     size_t chunk = (size_t)16e9 / per;
     if (chunk < 1) chunk = 1;
     if (chunk > (size_t)B) chunk = (size_t)B;
     const size_t nB = (size_t)B;
-    bool ok = hipMalloc(&h->fb_H, chunk * nV * nV * sizeof(double)) == hipSuccess &&
-              hipMalloc(&h->fb_g, chunk * nV * sizeof(double)) == hipSuccess &&
-              hipMalloc(&h->fb_A, chunk * nC * nV * sizeof(double)) == hipSuccess &&
-              hipMalloc(&h->fb_lba, chunk * nC * sizeof(double)) == hipSuccess &&
-              hipMalloc(&h->fb_uba, chunk * nC * sizeof(double)) == hipSuccess &&
-              hipMalloc(&h->fb_x, nB * nV * sizeof(double)) == hipSuccess &&
-              hipMalloc(&h->fb_x0, nB * nV * sizeof(double)) == hipSuccess &&
-              hipMalloc(&h->fb_cost, nB * sizeof(double)) == hipSuccess &&
-              hipMalloc(&h->fb_meas, 5 * nB * sizeof(double)) == hipSuccess &&
-              hipMalloc(&h->fb_carry, 5 * nB * sizeof(double)) == hipSuccess &&
-              hipMalloc(&h->fb_A22, nB * N * sizeof(double)) == hipSuccess &&
-              hipMalloc(&h->fb_D2, nB * N * sizeof(double)) == hipSuccess &&
-              hipMalloc(&h->fb_sp, nB * (N + 1) * sizeof(double)) == hipSuccess &&
-              hipMalloc(&h->fb_vp, nB * (N + 1) * sizeof(double)) == hipSuccess &&
-              hipMalloc(&h->fb_qpstat, nB * sizeof(int32_t)) == hipSuccess &&
-              hipMalloc(&h->fb_rhok, nB * sizeof(int)) == hipSuccess;
-    if (!ok) { fb_free(h); return fail(EEPACC_ENOMEM, "FBMPC: device allocation failed"); }
-    HIPCHK(hipMemset(h->fb_x0, 0, nB * nV * sizeof(double)));
-    HIPCHK(hipMemset(h->fb_rhok, 0, nB * sizeof(int)));
-    HIPCHK(hipMemset(h->fb_A22, 0, nB * N * sizeof(double)));
-    HIPCHK(hipMemset(h->fb_D2, 0, nB * N * sizeof(double)));
-    HIPCHK(hipMemset(h->fb_sp, 0, nB * (N + 1) * sizeof(double)));
-    HIPCHK(hipMemset(h->fb_vp, 0, nB * (N + 1) * sizeof(double)));
-    h->fb_B = B; h->fb_chunk = (int)chunk;
+    hipError_t e = hipSuccess;
+    auto get = [&e](auto& m, size_t n) { if (e == hipSuccess) e = m.alloc(n); };
+    get(f.H, chunk * nV * nV); get(f.g, chunk * nV); get(f.A, chunk * nC * nV); get(f.lba, chunk * nC); get(f.uba, chunk * nC);
+    get(f.x, nB * nV); get(f.x0, nB * nV); get(f.cost, nB); get(f.meas, 5 * nB); get(f.carry, 5 * nB);
+    get(f.A22, nB * N); get(f.D2, nB * N); get(f.sp, nB * (N + 1)); get(f.vp, nB * (N + 1));
+    get(f.qpstat, nB); get(f.rhok, nB);
+    if (e != hipSuccess) { f = FbDense(); return fail(EEPACC_ENOMEM, "FBMPC: device allocation failed"); }
+    HIPCHK(hipMemset(h->fb.x0, 0, nB * nV * sizeof(double)));
+    HIPCHK(hipMemset(h->fb.rhok, 0, nB * sizeof(int)));
+    HIPCHK(hipMemset(h->fb.A22, 0, nB * N * sizeof(double)));
+    HIPCHK(hipMemset(h->fb.D2, 0, nB * N * sizeof(double)));
+    HIPCHK(hipMemset(h->fb.sp, 0, nB * (N + 1) * sizeof(double)));
+    HIPCHK(hipMemset(h->fb.vp, 0, nB * (N + 1) * sizeof(double)));
+    h->fb.B = B; h->fb.chunk = (int)chunk;
     h->fb_k_done = 0; h->fb_by_step = false;
     return EEPACC_OK;
 }
@@ -565,41 +562,41 @@ static int fb_one_step(eepacc_handle* h, int B, int mode, const double* s, const
                        const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
                        double* out, double* s_pred, double* v_pred, int32_t* status, hipStream_t stream) {
     const int N = h->cfg.N, nV = 6 * N, nC = h->cfg.fb_row0[N] + 2;
-    for (int b0 = 0; b0 < B; b0 += h->fb_chunk) {
-        const int nb = (B - b0 < h->fb_chunk) ? B - b0 : h->fb_chunk;
+    for (int b0 = 0; b0 < B; b0 += h->fb.chunk) {
+        const int nb = (B - b0 < h->fb.chunk) ? B - b0 : h->fb.chunk;
         eepacc::eepacc_fb_args a;
         a.cfg = h->d_cfg; a.B = B; a.k_step = h->fb_k_done; a.b0 = b0; a.nb = nb; a.mode = mode;
         a.s = s; a.v = v; a.a_prev = a_prev; a.t0 = t0; a.s_tv = s_tv; a.v_tv = v_tv; a.a_tv_prev = a_tv_prev;
-        a.carry = h->fb_carry; a.A22 = h->fb_A22; a.D2 = h->fb_D2;
-        a.sp_prev = h->fb_sp; a.vp_prev = h->fb_vp;
-        a.H = h->fb_H; a.g = h->fb_g; a.A = h->fb_A; a.lba = h->fb_lba; a.uba = h->fb_uba; a.meas = h->fb_meas;
+        a.carry = h->fb.carry; a.A22 = h->fb.A22; a.D2 = h->fb.D2;
+        a.sp_prev = h->fb.sp; a.vp_prev = h->fb.vp;
+        a.H = h->fb.H; a.g = h->fb.g; a.A = h->fb.A; a.lba = h->fb.lba; a.uba = h->fb.uba; a.meas = h->fb.meas;
         HIPCHK(eepacc::launch_fb_build(a, N, stream));
         int grid = qp_grid(h, nb);
         int rc = qp_workspace(h, grid, nV);
         if (rc != EEPACC_OK) return rc;
         eepacc_qp_args q;
-        q.B = nb; q.nV = nV; q.nC = nC; q.H = h->fb_H; q.g = h->fb_g; q.A = h->fb_A; q.lba = h->fb_lba; q.uba = h->fb_uba;
+        q.B = nb; q.nV = nV; q.nC = nC; q.H = h->fb.H; q.g = h->fb.g; q.A = h->fb.A; q.lba = h->fb.lba; q.uba = h->fb.uba;
         q.lbx = nullptr; q.ubx = nullptr;
-        q.x0 = h->fb_x0 + (size_t)b0 * nV; q.x = h->fb_x + (size_t)b0 * nV; q.cost = h->fb_cost + b0;
-        q.status = h->fb_qpstat + b0; q.iters = (B <= h->max_batch) ? h->d_iters + b0 : nullptr;
+        q.x0 = h->fb.x0 + (size_t)b0 * nV; q.x = h->fb.x + (size_t)b0 * nV; q.cost = h->fb.cost + b0;
+        q.status = h->fb.qpstat + b0; q.iters = (B <= h->max_batch) ? h->d_iters + b0 : nullptr;
         q.ws = h->d_qp_ws; q.ws_stride = eepacc_qp_dense_ws_doubles(nV); q.rho_rel = 0.0; q.max_prox = 0;
-        q.counter = h->d_qp_counter; q.rho_k = h->fb_rhok + b0;
+        q.counter = h->d_qp_counter; q.rho_k = h->fb.rhok + b0;
         HIPCHK(hipMemsetAsync(h->d_qp_counter, 0, sizeof(int), stream));
         HIPCHK(eepacc_qp_dense_launch(q, grid, stream));
     }
     eepacc::eepacc_fb_apply_args p;
-    p.cfg = h->d_cfg; p.B = B; p.x = h->fb_x; p.cost = h->fb_cost; p.qp_status = h->fb_qpstat; p.meas = h->fb_meas;
-    p.A22 = h->fb_A22; p.D2 = h->fb_D2; p.out = out; p.s_pred = s_pred; p.v_pred = v_pred; p.status = status;
-    p.carry = mode == 1 ? h->fb_carry : nullptr;
+    p.cfg = h->d_cfg; p.B = B; p.x = h->fb.x; p.cost = h->fb.cost; p.qp_status = h->fb.qpstat; p.meas = h->fb.meas;
+    p.A22 = h->fb.A22; p.D2 = h->fb.D2; p.out = out; p.s_pred = s_pred; p.v_pred = v_pred; p.status = status;
+    p.carry = mode == 1 ? h->fb.carry : nullptr;
     const bool keep_pred = h->cfg.paramEstSetting == 2;
-    if (keep_pred) { p.s_pred = h->fb_sp; p.v_pred = h->fb_vp; }      // stride B: fb_sp/fb_vp hold [N+1][B]
+    if (keep_pred) { p.s_pred = h->fb.sp; p.v_pred = h->fb.vp; }      // stride B: fb_sp/fb_vp hold [N+1][B]
     HIPCHK(eepacc::launch_fb_apply(p, stream));
     if (keep_pred && s_pred && v_pred) {
-        HIPCHK(hipMemcpyAsync(s_pred, h->fb_sp, (size_t)B * (N + 1) * sizeof(double), hipMemcpyDeviceToDevice, stream));
-        HIPCHK(hipMemcpyAsync(v_pred, h->fb_vp, (size_t)B * (N + 1) * sizeof(double), hipMemcpyDeviceToDevice, stream));
+        HIPCHK(hipMemcpyAsync(s_pred, h->fb.sp, (size_t)B * (N + 1) * sizeof(double), hipMemcpyDeviceToDevice, stream));
+        HIPCHK(hipMemcpyAsync(v_pred, h->fb.vp, (size_t)B * (N + 1) * sizeof(double), hipMemcpyDeviceToDevice, stream));
     }
     // the solution is the proximal centre / initial guess of the next step
-    HIPCHK(hipMemcpyAsync(h->fb_x0, h->fb_x, (size_t)B * nV * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    HIPCHK(hipMemcpyAsync(h->fb.x0, h->fb.x, (size_t)B * nV * sizeof(double), hipMemcpyDeviceToDevice, stream));
     h->fb_k_done += 1;
     h->last_B = B;
     return EEPACC_OK;
@@ -610,8 +607,7 @@ extern "C" int eepacc_fb_step(eepacc_handle* h, int B, const double* s, const do
                               const double* s_tv, const double* v_tv, const double* a_tv_prev,
                               double* out, double* s_pred, double* v_pred, int32_t* status, void* stream) {
     (void)v_prev; (void)Fm_prev; (void)Fb_prev;   // accepted and unused, as in CreateQP_FB.m:1 (inputs v_minus1, Fm_minus1, Fb_minus1)
-    if (!h) return fail(EEPACC_EINVAL, "NULL handle");
-    { const int rc = not_tv(h, "eepacc_fb_step"); if (rc != EEPACC_OK) return rc; }
+    if (const int rc = not_tv(h, "eepacc_fb_step")) return rc;
     if (B < 0 || B > h->max_batch) return fail(EEPACC_EINVAL, "B exceeds max_batch of the handle");
     if (B == 0) return EEPACC_OK;
     if (!s || !v || !a_prev || !t0 || !s_tv || !v_tv || !a_tv_prev || !out || !status)
@@ -636,8 +632,7 @@ extern "C" int eepacc_fb_step(eepacc_handle* h, int B, const double* s, const do
 extern "C" int eepacc_run_fbmpc(eepacc_handle* h, int B, int n_steps, const double* s0, const double* v0,
                                 const double* a_minus1, const double* s_tv, const double* v_tv,
                                 double* traj, int32_t* status, void* stream) {
-    if (!h) return fail(EEPACC_EINVAL, "NULL handle");
-    { const int rc = not_tv(h, "eepacc_run_fbmpc"); if (rc != EEPACC_OK) return rc; }
+    if (const int rc = not_tv(h, "eepacc_run_fbmpc")) return rc;
     if (B < 0 || B > h->max_batch || n_steps < 0) return fail(EEPACC_EINVAL, "eepacc_run_fbmpc: bad B / n_steps");
     if (B == 0 || n_steps == 0) return EEPACC_OK;
     if (!s0 || !v0 || !a_minus1 || !s_tv || !v_tv || !traj || !status)
@@ -649,7 +644,7 @@ extern "C" int eepacc_run_fbmpc(eepacc_handle* h, int B, int n_steps, const doub
         return fail(EEPACC_EINVAL, "eepacc_run_fbmpc after eepacc_fb_step: the per-step operator keeps no closed-loop state to resume from; call eepacc_reset first");
     if (h->fbs) {
         // work-unit length: 16 MPC steps, shorter for short launches so that every resident wave still gets several units
-        int chunk_steps = eepacc::pick_chunk_steps(n_steps, B, h->num_cus * 7);
+        int chunk_steps = eepacc::pick_chunk_steps(n_steps, B, eepacc::fbs_run_chunking_waves(h->cfg.N, h->num_cus));
         eepacc::fbs_run_args a;
         a.cfg = h->d_cfg; a.B = B; a.k_start = h->fb_k_done; a.n_steps = n_steps;
         a.s0 = s0; a.v0 = v0; a.a_m1 = a_minus1; a.s_tv = s_tv; a.v_tv = v_tv;
@@ -673,143 +668,60 @@ extern "C" int eepacc_run_fbmpc(eepacc_handle* h, int B, int n_steps, const doub
     return EEPACC_OK;
 }
 
-// Host-pointer wrappers (what the MEX gateways mex/RunOpt_*MPC.c call): copy in, reset, run, wait, copy out.
-namespace {
-struct DevBufs {       // device scratch of the wrappers, freed on every return path
-    double *in = nullptr, *tv = nullptr, *traj = nullptr;
-    int32_t* status = nullptr;
-    ~DevBufs() {
-        if (in) (void)hipFree(in);
-        if (tv) (void)hipFree(tv);
-        if (traj) (void)hipFree(traj);
-        if (status) (void)hipFree(status);
-    }
-};
-}  // namespace
-
-static int run_host(eepacc_handle* h, bool fb, int B, int n_steps, const double* s0, const double* v0,
+// Host-pointer wrappers (what the MEX gateways mex/RunOpt_*MPC.c call): copy in, reset, run, wait, copy out.  The device
+// scratch is freed on every return path.  A target-vehicle run has no lead trace (s_tv, v_tv null).
+enum class Ctl { AB, FB, TV };
+static int run_host(eepacc_handle* h, Ctl ctl, int B, int n_steps, const double* s0, const double* v0,
                     const double* a_minus1, const double* s_tv, const double* v_tv, double* traj, int32_t* status) {
     if (!h) return fail(EEPACC_EINVAL, "NULL handle");
+    const bool lead = ctl != Ctl::TV;
     if (B < 1 || B > h->max_batch || n_steps < 1) return fail(EEPACC_EINVAL, "bad B / n_steps");
-    if (!s0 || !v0 || !a_minus1 || !s_tv || !v_tv || !traj || !status) return fail(EEPACC_EINVAL, "NULL buffer");
+    if (!s0 || !v0 || !a_minus1 || (lead && (!s_tv || !v_tv)) || !traj || !status) return fail(EEPACC_EINVAL, "NULL buffer");
     HIPCHK(hipSetDevice(h->device));
-    DevBufs d;
+    DevMem<double> d_in, d_tv, d_traj;
+    DevMem<int32_t> d_status;
     const size_t nB = (size_t)B, nT = (size_t)n_steps * B;
-    HIPCHK(hipMalloc(&d.in, 3 * nB * sizeof(double)));
-    HIPCHK(hipMalloc(&d.tv, 2 * nT * sizeof(double)));
-    HIPCHK(hipMalloc(&d.traj, nT * EEPACC_OUT_N * sizeof(double)));
-    HIPCHK(hipMalloc(&d.status, nT * sizeof(int32_t)));
-    HIPCHK(hipMemcpy(d.in, s0, nB * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d.in + nB, v0, nB * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d.in + 2 * nB, a_minus1, nB * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d.tv, s_tv, nT * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d.tv + nT, v_tv, nT * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(d_in.alloc(3 * nB));
+    if (lead) HIPCHK(d_tv.alloc(2 * nT));
+    HIPCHK(d_traj.alloc(nT * EEPACC_OUT_N));
+    HIPCHK(d_status.alloc(nT));
+    HIPCHK(hipMemcpy(d_in, s0, nB * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_in + nB, v0, nB * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_in + 2 * nB, a_minus1, nB * sizeof(double), hipMemcpyHostToDevice));
+    if (lead) {
+        HIPCHK(hipMemcpy(d_tv, s_tv, nT * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_tv + nT, v_tv, nT * sizeof(double), hipMemcpyHostToDevice));
+    }
     int rc = eepacc_reset(h);
     if (rc != EEPACC_OK) return rc;
-    rc = fb ? eepacc_run_fbmpc(h, B, n_steps, d.in, d.in + nB, d.in + 2 * nB, d.tv, d.tv + nT, d.traj, d.status, nullptr)
-            : eepacc_run_abmpc(h, B, n_steps, d.in, d.in + nB, d.in + 2 * nB, d.tv, d.tv + nT, d.traj, d.status, nullptr);
+    rc = ctl == Ctl::TV ? eepacc_run_tvmpc(h, B, n_steps, d_in, d_in + nB, d_in + 2 * nB, d_traj, d_status, nullptr)
+       : ctl == Ctl::FB ? eepacc_run_fbmpc(h, B, n_steps, d_in, d_in + nB, d_in + 2 * nB, d_tv, d_tv + nT, d_traj, d_status, nullptr)
+                        : eepacc_run_abmpc(h, B, n_steps, d_in, d_in + nB, d_in + 2 * nB, d_tv, d_tv + nT, d_traj, d_status, nullptr);
     if (rc != EEPACC_OK) return rc;
     rc = eepacc_synchronize(h, nullptr);
-    HIPCHK(hipMemcpy(traj, d.traj, nT * EEPACC_OUT_N * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(status, d.status, nT * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(traj, d_traj, nT * EEPACC_OUT_N * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(status, d_status, nT * sizeof(int32_t), hipMemcpyDeviceToHost));
     return rc;
-}
-
-// RunOpt_BLMPC by name: the ABMPC entry points on a handle that was created as the baseline controller
-static int need_bl(const eepacc_handle* h) {
-    if (!h) return fail(EEPACC_EINVAL, "NULL handle");
-    if (h->cfg.bl_mode != 1) return fail(EEPACC_EINVAL, "this handle was not created with bl_mode = 1 (RunOpt_BLMPC)");
-    return EEPACC_OK;
-}
-extern "C" int eepacc_bl_step(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
-                              const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
-                              double* out, double* s_pred, double* v_pred, int32_t* status, void* stream) {
-    const int rc = need_bl(h);
-    return rc != EEPACC_OK ? rc : eepacc_ab_step(h, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, out, s_pred, v_pred, status, stream);
-}
-extern "C" int eepacc_run_blmpc(eepacc_handle* h, int B, int n_steps, const double* s0, const double* v0,
-                                const double* a_minus1, const double* s_tv, const double* v_tv, double* traj,
-                                int32_t* status, void* stream) {
-    const int rc = need_bl(h);
-    return rc != EEPACC_OK ? rc : eepacc_run_abmpc(h, B, n_steps, s0, v0, a_minus1, s_tv, v_tv, traj, status, stream);
-}
-extern "C" int eepacc_run_blmpc_host(eepacc_handle* h, int B, int n_steps, const double* s0, const double* v0,
-                                     const double* a_minus1, const double* s_tv, const double* v_tv,
-                                     double* traj, int32_t* status) {
-    const int rc = need_bl(h);
-    return rc != EEPACC_OK ? rc : run_host(h, false, B, n_steps, s0, v0, a_minus1, s_tv, v_tv, traj, status);
 }
 
 extern "C" int eepacc_run_abmpc_host(eepacc_handle* h, int B, int n_steps, const double* s0, const double* v0,
                                      const double* a_minus1, const double* s_tv, const double* v_tv,
                                      double* traj, int32_t* status) {
-    return run_host(h, false, B, n_steps, s0, v0, a_minus1, s_tv, v_tv, traj, status);
+    return run_host(h, Ctl::AB, B, n_steps, s0, v0, a_minus1, s_tv, v_tv, traj, status);
 }
-
+extern "C" int eepacc_run_blmpc_host(eepacc_handle* h, int B, int n_steps, const double* s0, const double* v0,
+                                     const double* a_minus1, const double* s_tv, const double* v_tv,
+                                     double* traj, int32_t* status) {
+    const int rc = need_bl(h);
+    return rc != EEPACC_OK ? rc : run_host(h, Ctl::AB, B, n_steps, s0, v0, a_minus1, s_tv, v_tv, traj, status);
+}
 extern "C" int eepacc_run_fbmpc_host(eepacc_handle* h, int B, int n_steps, const double* s0, const double* v0,
                                      const double* a_minus1, const double* s_tv, const double* v_tv,
                                      double* traj, int32_t* status) {
-    return run_host(h, true, B, n_steps, s0, v0, a_minus1, s_tv, v_tv, traj, status);
-}
-
-// RunOpt_TVMPC (ABO/RunOpt_TVMPC.m): the target-vehicle MPC, a handle created with bl_mode = 2.  No lead inputs: the
-// kernels of this variant read none and the launchers get null pointers.
-static int need_tv(const eepacc_handle* h) {
-    if (!h) return fail(EEPACC_EINVAL, "NULL handle");
-    if (h->cfg.bl_mode != 2) return fail(EEPACC_EINVAL, "this handle was not created with bl_mode = 2 (RunOpt_TVMPC)");
-    return EEPACC_OK;
-}
-extern "C" int eepacc_tv_step(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
-                              const double* t0, double* out, double* s_pred, double* v_pred, int32_t* status, void* stream) {
-    const int rc = need_tv(h);
-    if (rc != EEPACC_OK) return rc;
-    if (B < 0 || B > h->max_batch) return fail(EEPACC_EINVAL, "B exceeds max_batch of the handle");
-    if (B == 0) return EEPACC_OK;
-    if (!s || !v || !a_prev || !t0 || !out || !status) return fail(EEPACC_EINVAL, "eepacc_tv_step: NULL buffer");
-    HIPCHK(hipSetDevice(h->device));
-    h->last_B = B;
-    HIPCHK(eepacc::launch_ab_step(h->d_cfg, h->cfg.N, ab_variant(h->cfg), B, s, v, a_prev, t0, nullptr, nullptr, nullptr, h->d_codes,
-                                  out, s_pred, v_pred, status, h->d_iters, (hipStream_t)stream));
-    return EEPACC_OK;
-}
-extern "C" int eepacc_run_tvmpc(eepacc_handle* h, int B, int n_steps, const double* s0, const double* v0,
-                                const double* a_minus1, double* traj, int32_t* status, void* stream) {
-    const int rc = need_tv(h);
-    if (rc != EEPACC_OK) return rc;
-    if (B < 0 || B > h->max_batch || n_steps < 0) return fail(EEPACC_EINVAL, "eepacc_run_tvmpc: bad B / n_steps");
-    if (B == 0 || n_steps == 0) return EEPACC_OK;
-    if (!s0 || !v0 || !a_minus1 || !traj || !status) return fail(EEPACC_EINVAL, "eepacc_run_tvmpc: NULL buffer");
-    HIPCHK(hipSetDevice(h->device));
-    if (h->k_done > 0 && h->carry_B != B)
-        return fail(EEPACC_EINVAL, "eepacc_run_tvmpc: B changed while resuming; call eepacc_reset first");
-    h->last_B = B;
-    HIPCHK(eepacc::launch_run_abmpc(h->d_cfg, h->cfg.N, ab_variant(h->cfg), B, h->k_done, n_steps, s0, v0, a_minus1, nullptr, nullptr,
-                                    h->d_carry, h->d_codes, traj, status, h->d_iters, h->d_counter, h->d_done, h->d_err, h->num_cus,
-                                    (hipStream_t)stream));
-    h->k_done += n_steps; h->carry_B = B;
-    return EEPACC_OK;
+    return run_host(h, Ctl::FB, B, n_steps, s0, v0, a_minus1, s_tv, v_tv, traj, status);
 }
 extern "C" int eepacc_run_tvmpc_host(eepacc_handle* h, int B, int n_steps, const double* s0, const double* v0,
                                      const double* a_minus1, double* traj, int32_t* status) {
-    int rc = need_tv(h);
-    if (rc != EEPACC_OK) return rc;
-    if (B < 1 || B > h->max_batch || n_steps < 1) return fail(EEPACC_EINVAL, "bad B / n_steps");
-    if (!s0 || !v0 || !a_minus1 || !traj || !status) return fail(EEPACC_EINVAL, "NULL buffer");
-    HIPCHK(hipSetDevice(h->device));
-    DevBufs d;
-    const size_t nB = (size_t)B, nT = (size_t)n_steps * B;
-    HIPCHK(hipMalloc(&d.in, 3 * nB * sizeof(double)));
-    HIPCHK(hipMalloc(&d.traj, nT * EEPACC_OUT_N * sizeof(double)));
-    HIPCHK(hipMalloc(&d.status, nT * sizeof(int32_t)));
-    HIPCHK(hipMemcpy(d.in, s0, nB * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d.in + nB, v0, nB * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d.in + 2 * nB, a_minus1, nB * sizeof(double), hipMemcpyHostToDevice));
-    rc = eepacc_reset(h);
-    if (rc != EEPACC_OK) return rc;
-    rc = eepacc_run_tvmpc(h, B, n_steps, d.in, d.in + nB, d.in + 2 * nB, d.traj, d.status, nullptr);
-    if (rc != EEPACC_OK) return rc;
-    rc = eepacc_synchronize(h, nullptr);
-    HIPCHK(hipMemcpy(traj, d.traj, nT * EEPACC_OUT_N * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(status, d.status, nT * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return rc;
+    const int rc = need_tv(h);
+    return rc != EEPACC_OK ? rc : run_host(h, Ctl::TV, B, n_steps, s0, v0, a_minus1, nullptr, nullptr, traj, status);
 }

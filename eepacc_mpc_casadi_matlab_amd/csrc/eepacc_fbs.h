@@ -40,6 +40,11 @@ bool fbs_supported(const DevCfg& C);
 size_t fbs_smem_bytes(int N);
 size_t fbs_hb_doubles(int N, int B, int num_cus);   // scratch a launch for B instances needs
 hipError_t fbs_set_max_smem();
+// Resident waves that eepacc_run_fbmpc sizes its work units for (pick_chunk_steps): the N <= 32 kernel's one block of 7 waves
+// per CU, which is what launch_fbs_run's grid gives there.  The same 7 per CU is used at N > 32, where one-wave blocks share
+// the LDS and fewer waves are resident: the units of a short launch come out shorter there than the rule intends.  Kept as it
+// is, since the unit length enters the results' launch geometry.
+inline int fbs_run_chunking_waves(int /*N*/, int num_cus) { return num_cus * 7; }
 hipError_t launch_fbs_step(const fbs_step_args& a, int N, hipStream_t stream);
 hipError_t launch_fbs_run(fbs_run_args a, int N, int num_cus, hipStream_t stream);
 

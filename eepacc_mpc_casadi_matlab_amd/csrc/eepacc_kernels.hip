@@ -16,57 +16,53 @@
 #include "eepacc_stage.h"
 #include "eepacc_units.h"
 #include "eepacc_schur.h"
+#include "eepacc_ab.h"
 #include "../../include/eepacc.h"
 
-#define EEPACC_IMPL_NS nomb
-#define EEPACC_IMPL_MB false
-#define EEPACC_IMPL_BL false
-#include "eepacc_ab_impl.inc"
-#undef EEPACC_IMPL_NS
-#undef EEPACC_IMPL_MB
-#define EEPACC_IMPL_NS withmb
-#define EEPACC_IMPL_MB true
-#include "eepacc_ab_impl.inc"
-#undef EEPACC_IMPL_NS
-#undef EEPACC_IMPL_MB
-#undef EEPACC_IMPL_BL
-// baseline controller (RunOpt_BLMPC): the same kernels with CreateQP_BL's row grouping
-#define EEPACC_IMPL_NS blc
-#define EEPACC_IMPL_MB false
-#define EEPACC_IMPL_BL true
-#include "eepacc_ab_impl.inc"
-#undef EEPACC_IMPL_NS
-#undef EEPACC_IMPL_MB
-#undef EEPACC_IMPL_BL
-// target-vehicle MPC (RunOpt_TVMPC): the baseline variant with CreateQP_TV's row catalogue (no vehicle-following rows, 0.8
-// of the speed-limit and curve caps, low-speed comfort limits) and no lead inputs
-#define EEPACC_IMPL_NS tvc
-#define EEPACC_IMPL_MB false
-#define EEPACC_IMPL_BL true
-#define EEPACC_IMPL_TV true
-#include "eepacc_ab_impl.inc"
-#undef EEPACC_IMPL_NS
-#undef EEPACC_IMPL_MB
-#undef EEPACC_IMPL_BL
-#undef EEPACC_IMPL_TV
+// The variants of eepacc_ab_impl.inc, each compiled into its own namespace so that the default path carries no register or
+// instruction cost for the others: X(AbVariant, namespace, EEPACC_IMPL_MB, _BL, _TV, _ICE, ...).  A new variant is a line here,
+// its AbVariant (eepacc_ab.h) and its #include below.
+//   blc    baseline controller (RunOpt_BLMPC): the same kernels with CreateQP_BL's row grouping
+//   tvc    target-vehicle MPC (RunOpt_TVMPC): the baseline variant with CreateQP_TV's row catalogue (no vehicle-following
+//          rows, 0.8 of the speed-limit and curve caps, low-speed comfort limits) and no lead inputs
+//   ice*   ICE-map fuel term (CreateQP_AB.m:154-159): step-varying Hessian, built and inverted in LDS every step; icemb
+//          folds the Hessian into E'HE before the inversion.  Two namespaces: compiled into one, the blocking code costs
+//          the small ICE kernel 18 % of its throughput at N = 30 even where the handle has no Mb.
+#define EEPACC_AB_VARIANTS(X, ...)                                       \
+    X(Plain, nomb, false, false, false, false, __VA_ARGS__)              \
+    X(MoveBlocking, withmb, true, false, false, false, __VA_ARGS__)      \
+    X(Baseline, blc, false, true, false, false, __VA_ARGS__)             \
+    X(Ice, ice, false, false, false, true, __VA_ARGS__)                  \
+    X(IceMoveBlocking, icemb, true, false, false, true, __VA_ARGS__)     \
+    X(TargetVehicle, tvc, false, true, true, false, __VA_ARGS__)
 
-// ICE-map fuel term (CreateQP_AB.m:154-159): step-varying Hessian, built and inverted in LDS every step; without and with
-// move blocking (icemb folds the Hessian into E'HE before the inversion).  Two namespaces: compiled into one, the blocking
-// code costs the small ICE kernel 18 % of its throughput at N = 30 even where the handle has no Mb.
-#define EEPACC_IMPL_BL false
-#define EEPACC_IMPL_ICE true
+// an instantiation reads its switches from the list by the name of its namespace
+namespace eepacc { namespace ab_switch {
+#define EEPACC_AB_SWITCHES(E, NSP, MB_, BL_, TV_, ICE_, ...) struct NSP { static constexpr bool MB = MB_, BL = BL_, TV = TV_, ICE = ICE_; };
+EEPACC_AB_VARIANTS(EEPACC_AB_SWITCHES)
+} }
+#define EEPACC_IMPL_MB ab_switch::EEPACC_IMPL_NS::MB
+#define EEPACC_IMPL_BL ab_switch::EEPACC_IMPL_NS::BL
+#define EEPACC_IMPL_TV ab_switch::EEPACC_IMPL_NS::TV
+#define EEPACC_IMPL_ICE ab_switch::EEPACC_IMPL_NS::ICE
+#define EEPACC_IMPL_NS nomb
+#include "eepacc_ab_impl.inc"
+#undef EEPACC_IMPL_NS
+#define EEPACC_IMPL_NS withmb
+#include "eepacc_ab_impl.inc"
+#undef EEPACC_IMPL_NS
+#define EEPACC_IMPL_NS blc
+#include "eepacc_ab_impl.inc"
+#undef EEPACC_IMPL_NS
 #define EEPACC_IMPL_NS ice
-#define EEPACC_IMPL_MB false
 #include "eepacc_ab_impl.inc"
 #undef EEPACC_IMPL_NS
-#undef EEPACC_IMPL_MB
 #define EEPACC_IMPL_NS icemb
-#define EEPACC_IMPL_MB true
 #include "eepacc_ab_impl.inc"
 #undef EEPACC_IMPL_NS
-#undef EEPACC_IMPL_MB
-#undef EEPACC_IMPL_BL
-#undef EEPACC_IMPL_ICE
+#define EEPACC_IMPL_NS tvc
+#include "eepacc_ab_impl.inc"
+#undef EEPACC_IMPL_NS
 
 // ----------------------------------------------------------------------------------------------
 // host-side launchers used by eepacc_capi.cpp
@@ -97,16 +93,11 @@ size_t ab_smem_bytes(int N) {
                          : nomb::wave_bytes(sizeof(nomb::WaveMem<kMMaxLarge, kNSLarge>), kNSLarge) * kWpbLarge;
 }
 
-// the kernel of the namespace with / without move blocking, small or large horizon
-#define EEPACC_LAUNCH_NS(NSP, KERNEL, MM, NSV, WPB, GRID, ...)                                                \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(NSP::KERNEL<MM, NSV, WPB>), dim3(GRID), dim3(64 * WPB), ab_smem_bytes(N), stream, __VA_ARGS__)
+// the kernel of the handle's variant, small or large horizon
+#define EEPACC_LAUNCH_CASE(E, NSP, MB, BL, TV, ICE, KERNEL, MM, NSV, WPB, GRID, ...)                          \
+    case AbVariant::E: hipLaunchKernelGGL(HIP_KERNEL_NAME(NSP::KERNEL<MM, NSV, WPB>), dim3(GRID), dim3(64 * WPB), ab_smem_bytes(N), stream, __VA_ARGS__); break;
 #define EEPACC_LAUNCH(KERNEL, MM, NSV, WPB, GRID, ...)                                                        \
-    do { if (variant == 5) EEPACC_LAUNCH_NS(tvc, KERNEL, MM, NSV, WPB, GRID, __VA_ARGS__);                    \
-         else if (variant == 4) EEPACC_LAUNCH_NS(icemb, KERNEL, MM, NSV, WPB, GRID, __VA_ARGS__);                  \
-         else if (variant == 3) EEPACC_LAUNCH_NS(ice, KERNEL, MM, NSV, WPB, GRID, __VA_ARGS__);               \
-         else if (variant == 2) EEPACC_LAUNCH_NS(blc, KERNEL, MM, NSV, WPB, GRID, __VA_ARGS__);               \
-         else if (variant == 1) EEPACC_LAUNCH_NS(withmb, KERNEL, MM, NSV, WPB, GRID, __VA_ARGS__);            \
-         else EEPACC_LAUNCH_NS(nomb, KERNEL, MM, NSV, WPB, GRID, __VA_ARGS__); } while (0)
+    do { switch (variant) { EEPACC_AB_VARIANTS(EEPACC_LAUNCH_CASE, KERNEL, MM, NSV, WPB, GRID, __VA_ARGS__) } } while (0)
 
 // MPC steps per work unit of the closed-loop kernels: 16 (EEPACC_CHUNK overrides), fewer when the launch is so short
 // that the resident waves would otherwise get fewer than about eight units each (tail imbalance)
@@ -132,7 +123,7 @@ size_t ab_hb_doubles(int N, int B, int num_cus) {
     return (step_waves > run_waves ? step_waves : run_waves) * ns * ns;
 }
 
-hipError_t launch_ab_step(const DevCfg* dC, int N, int variant, int B, const double* s, const double* v, const double* a_prev,
+hipError_t launch_ab_step(const DevCfg* dC, int N, AbVariant variant, int B, const double* s, const double* v, const double* a_prev,
                           const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
                           unsigned long long* codes, double* out, double* s_pred, double* v_pred,
                           int32_t* status, int32_t* iters, hipStream_t stream) {
@@ -141,7 +132,7 @@ hipError_t launch_ab_step(const DevCfg* dC, int N, int variant, int B, const dou
     return hipGetLastError();
 }
 
-hipError_t launch_run_abmpc(const DevCfg* dC, int N, int variant, int B, int k_start, int n_steps, const double* s0,
+hipError_t launch_run_abmpc(const DevCfg* dC, int N, AbVariant variant, int B, int k_start, int n_steps, const double* s0,
                             const double* v0, const double* a_m1, const double* s_tv, const double* v_tv,
                             double* carry, unsigned long long* codes, double* traj,
                             int32_t* status, int32_t* iters_total, int* work_counter, int* done, int* err_word, int num_cus,
@@ -160,45 +151,54 @@ hipError_t launch_run_abmpc(const DevCfg* dC, int N, int variant, int B, int k_s
     return hipGetLastError();
 }
 
+// A10: post-processing (ABO/RunOpt_ABMPC.m:343-349), one thread per instance, sequential in time
+__global__ void k_postprocess(const DevCfg* __restrict__ Cp, int B, int n_steps, const double* __restrict__ traj,
+                              double* __restrict__ rpm, double* __restrict__ Tm, double* __restrict__ P,
+                              double* __restrict__ E) {
+    const DevCfg& C = *Cp;
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const double Ts = C.Tvec[0];
+    double acc = 0.0;
+    const double kr = (30.0 / 3.14159265358979323846);
+    for (int k = 0; k < n_steps; ++k) {
+        const double v = traj[((size_t)k * EEPACC_OUT_N + EEPACC_OUT_V) * B + b];
+        const double x = traj[((size_t)k * EEPACC_OUT_N + EEPACC_OUT_FM) * B + b];
+        const double y = kr * v * C.phi;
+        const double sg = (x > 0.0) ? 1.0 : ((x < 0.0) ? -1.0 : 0.0);
+        const double tm = x / C.phi / pow(C.eta_TF, sg);
+        const double* bb = C.b5;
+        const double x2 = x * x, x3 = x2 * x, x4 = x3 * x, x5 = x4 * x;
+        const double y2 = y * y, y3 = y2 * y, y4 = y3 * y, y5 = y4 * y;
+        const double p = bb[0] + bb[1] * x + bb[2] * y + bb[3] * x2 + bb[4] * x * y + bb[5] * y2 + bb[6] * x3 +
+                         bb[7] * x2 * y + bb[8] * x * y2 + bb[9] * y3 + bb[10] * x4 + bb[11] * x3 * y +
+                         bb[12] * x2 * y2 + bb[13] * x * y3 + bb[14] * y4 + bb[15] * x5 + bb[16] * x4 * y +
+                         bb[17] * x3 * y2 + bb[18] * x2 * y3 + bb[19] * x * y4 + bb[20] * y5;
+        acc += p;
+        const size_t o = (size_t)k * B + b;
+        rpm[o] = y; Tm[o] = tm; P[o] = p; E[o] = Ts * acc;
+    }
+}
+
 hipError_t launch_postprocess(const DevCfg* dC, int B, int n_steps, const double* traj, double* rpm, double* Tm,
                               double* P, double* E, hipStream_t stream) {
-    hipLaunchKernelGGL(nomb::k_postprocess, dim3((B + 127) / 128), dim3(128), 0, stream, dC, B, n_steps, traj, rpm, Tm, P, E);
+    hipLaunchKernelGGL(k_postprocess, dim3((B + 127) / 128), dim3(128), 0, stream, dC, B, n_steps, traj, rpm, Tm, P, E);
     return hipGetLastError();
 }
 
+// 160 KB of LDS per CU minus the kernel's static index table (one ushort per packed entry of P)
+template <int MM, class K>
+static hipError_t raise_smem(hipError_t e, K* kernel) {
+    const int dyn = 160 * 1024 - ((MM * (MM + 1) / 2 * 2 + 255) & ~255);
+    return e != hipSuccess ? e : hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, dyn);
+}
+#define EEPACC_RAISE_SMEM(E, NSP, MB, BL, TV, ICE, MM, NSV, WPB) \
+    e = raise_smem<MM>(e, &NSP::k_ab_step<MM, NSV, WPB>); e = raise_smem<MM>(e, &NSP::k_run_abmpc<MM, NSV, WPB>);
 hipError_t set_max_smem() {
-    const void* fns[24] = {reinterpret_cast<const void*>(&nomb::k_ab_step<kMMaxSmall, kNSSmall, 4>),
-                          reinterpret_cast<const void*>(&nomb::k_ab_step<kMMaxLarge, kNSLarge, kWpbLarge>),
-                          reinterpret_cast<const void*>(&nomb::k_run_abmpc<kMMaxSmall, kNSSmall, 4>),
-                          reinterpret_cast<const void*>(&nomb::k_run_abmpc<kMMaxLarge, kNSLarge, kWpbLarge>),
-                          reinterpret_cast<const void*>(&withmb::k_ab_step<kMMaxSmall, kNSSmall, 4>),
-                          reinterpret_cast<const void*>(&withmb::k_ab_step<kMMaxLarge, kNSLarge, kWpbLarge>),
-                          reinterpret_cast<const void*>(&withmb::k_run_abmpc<kMMaxSmall, kNSSmall, 4>),
-                          reinterpret_cast<const void*>(&withmb::k_run_abmpc<kMMaxLarge, kNSLarge, kWpbLarge>),
-                          reinterpret_cast<const void*>(&blc::k_ab_step<kMMaxSmall, kNSSmall, 4>),
-                          reinterpret_cast<const void*>(&blc::k_ab_step<kMMaxLarge, kNSLarge, kWpbLarge>),
-                          reinterpret_cast<const void*>(&blc::k_run_abmpc<kMMaxSmall, kNSSmall, 4>),
-                          reinterpret_cast<const void*>(&blc::k_run_abmpc<kMMaxLarge, kNSLarge, kWpbLarge>),
-                          reinterpret_cast<const void*>(&ice::k_ab_step<kMMaxSmall, kNSSmall, 4>),
-                          reinterpret_cast<const void*>(&ice::k_ab_step<kMMaxLarge, kNSLarge, kWpbLarge>),
-                          reinterpret_cast<const void*>(&ice::k_run_abmpc<kMMaxSmall, kNSSmall, 4>),
-                          reinterpret_cast<const void*>(&ice::k_run_abmpc<kMMaxLarge, kNSLarge, kWpbLarge>),
-                          reinterpret_cast<const void*>(&icemb::k_ab_step<kMMaxSmall, kNSSmall, 4>),
-                          reinterpret_cast<const void*>(&icemb::k_ab_step<kMMaxLarge, kNSLarge, kWpbLarge>),
-                          reinterpret_cast<const void*>(&icemb::k_run_abmpc<kMMaxSmall, kNSSmall, 4>),
-                          reinterpret_cast<const void*>(&icemb::k_run_abmpc<kMMaxLarge, kNSLarge, kWpbLarge>),
-                          reinterpret_cast<const void*>(&tvc::k_ab_step<kMMaxSmall, kNSSmall, 4>),
-                          reinterpret_cast<const void*>(&tvc::k_ab_step<kMMaxLarge, kNSLarge, kWpbLarge>),
-                          reinterpret_cast<const void*>(&tvc::k_run_abmpc<kMMaxSmall, kNSSmall, 4>),
-                          reinterpret_cast<const void*>(&tvc::k_run_abmpc<kMMaxLarge, kNSLarge, kWpbLarge>)};
-    for (int i = 0; i < 24; ++i) {
-        // 160 KB of LDS per CU minus the kernel's static index table (one ushort per packed entry of P)
-        const int mm = (i & 1) ? kMMaxLarge : kMMaxSmall;
-        const int dyn = 160 * 1024 - ((mm * (mm + 1) / 2 * 2 + 255) & ~255);
-        hipError_t e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, dyn);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    hipError_t e = hipSuccess;
+    EEPACC_AB_VARIANTS(EEPACC_RAISE_SMEM, kMMaxSmall, kNSSmall, 4)
+    EEPACC_AB_VARIANTS(EEPACC_RAISE_SMEM, kMMaxLarge, kNSLarge, kWpbLarge)
+    return e;
 }
 
 }  // namespace eepacc

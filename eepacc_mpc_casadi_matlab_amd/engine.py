@@ -121,42 +121,50 @@ class Engine:
     def reset(self):
         _check(self.lib.eepacc_reset(self.h))
 
-    # B2 ------------------------------------------------------------------------------------
-    def ab_step(self, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, want_pred: bool = True):
+    def _step(self, fn, ins, want_pred):
+        """One MPC step for B instances: ins are the entry point's [B] inputs in the order of its argument list."""
         t = self.torch
-        B = int(t.as_tensor(s).numel())
-        ins = [self._d(x, B) for x in (s, v, a_prev, t0, s_tv, v_tv, a_tv_prev)]
+        B = int(t.as_tensor(ins[0]).numel())
+        ins = [self._d(x, B) for x in ins]
         out = t.empty((OUT_N, B), dtype=t.float64, device=self.device)
         sp = t.empty((self.N + 1, B), dtype=t.float64, device=self.device) if want_pred else None
         vp = t.empty((self.N + 1, B), dtype=t.float64, device=self.device) if want_pred else None
         status = t.empty((B,), dtype=t.int32, device=self.device)
-        _check(self.lib.eepacc_ab_step(self.h, B, *[x.data_ptr() for x in ins], out.data_ptr(),
-                                       sp.data_ptr() if want_pred else None,
-                                       vp.data_ptr() if want_pred else None, status.data_ptr(), self._stream()))
+        _check(fn(self.h, B, *[x.data_ptr() for x in ins], out.data_ptr(), sp.data_ptr() if want_pred else None,
+                  vp.data_ptr() if want_pred else None, status.data_ptr(), self._stream()))
         return out, sp, vp, status
 
-    # B1 ------------------------------------------------------------------------------------
-    def run_abmpc(self, s0, v0, a_minus1, s_tv, v_tv, resume: bool = False, out=None, by_name_bl: bool = False):
-        """s_tv, v_tv: [n_steps, B] lead traces.  Returns traj [n_steps, OUT_N, B], status [n_steps, B].
-        resume=True continues the simulation of the previous call (s_tv/v_tv hold the next rows).
-        out=(traj, status): preallocated output tensors to write into."""
+    def _run(self, fn, ins, lead, n_steps, resume, out):
+        """Closed loop: ins = (s0, v0, a_minus1), lead = (s_tv, v_tv) as [n_steps, B] or None with n_steps given."""
         t = self.torch
         if not resume:
             self.reset()
-        s_tv = t.as_tensor(s_tv, dtype=t.float64, device=self.device).contiguous()
-        v_tv = t.as_tensor(v_tv, dtype=t.float64, device=self.device).contiguous()
-        n_steps, B = s_tv.shape
-        ins = [self._d(x, B) for x in (s0, v0, a_minus1)]
+        if lead is not None:
+            lead = [t.as_tensor(x, dtype=t.float64, device=self.device).contiguous() for x in lead]
+            n_steps, B = lead[0].shape
+        else:
+            n_steps, B, lead = int(n_steps), int(t.as_tensor(ins[0]).numel()), []
+        ins = [self._d(x, B) for x in ins]
         if out is not None:
             traj, status = out[0][:n_steps], out[1][:n_steps]
             assert traj.shape == (n_steps, OUT_N, B) and traj.is_contiguous() and status.is_contiguous()
         else:
             traj = t.empty((n_steps, OUT_N, B), dtype=t.float64, device=self.device)
             status = t.empty((n_steps, B), dtype=t.int32, device=self.device)
-        f = self.lib.eepacc_run_blmpc if by_name_bl else self.lib.eepacc_run_abmpc
-        _check(f(self.h, B, n_steps, *[x.data_ptr() for x in ins], s_tv.data_ptr(),
-                 v_tv.data_ptr(), traj.data_ptr(), status.data_ptr(), self._stream()))
+        _check(fn(self.h, B, n_steps, *[x.data_ptr() for x in ins + lead], traj.data_ptr(), status.data_ptr(), self._stream()))
         return traj, status
+
+    # B2 ------------------------------------------------------------------------------------
+    def ab_step(self, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, want_pred: bool = True):
+        return self._step(self.lib.eepacc_ab_step, (s, v, a_prev, t0, s_tv, v_tv, a_tv_prev), want_pred)
+
+    # B1 ------------------------------------------------------------------------------------
+    def run_abmpc(self, s0, v0, a_minus1, s_tv, v_tv, resume: bool = False, out=None, by_name_bl: bool = False):
+        """s_tv, v_tv: [n_steps, B] lead traces.  Returns traj [n_steps, OUT_N, B], status [n_steps, B].
+        resume=True continues the simulation of the previous call (s_tv/v_tv hold the next rows).
+        out=(traj, status): preallocated output tensors to write into."""
+        fn = self.lib.eepacc_run_blmpc if by_name_bl else self.lib.eepacc_run_abmpc
+        return self._run(fn, (s0, v0, a_minus1), (s_tv, v_tv), None, resume, out)
 
     def run_blmpc(self, s0, v0, a_minus1, s_tv, v_tv, resume: bool = False, out=None):
         """eepacc_run_blmpc: run_abmpc on a handle created from settings.Settings_BL (refused on any other handle)."""
@@ -165,79 +173,20 @@ class Engine:
     # target-vehicle MPC (ABO/RunOpt_TVMPC.m): a handle created from settings.Settings_TV; no lead inputs -----------------
     def tv_step(self, s, v, a_prev, t0, want_pred: bool = True):
         """eepacc_tv_step: one step of RunOpt_TVMPC's loop (:156-277) for B instances; results as ab_step."""
-        t = self.torch
-        B = int(t.as_tensor(s).numel())
-        ins = [self._d(x, B) for x in (s, v, a_prev, t0)]
-        out = t.empty((OUT_N, B), dtype=t.float64, device=self.device)
-        sp = t.empty((self.N + 1, B), dtype=t.float64, device=self.device) if want_pred else None
-        vp = t.empty((self.N + 1, B), dtype=t.float64, device=self.device) if want_pred else None
-        status = t.empty((B,), dtype=t.int32, device=self.device)
-        _check(self.lib.eepacc_tv_step(self.h, B, *[x.data_ptr() for x in ins], out.data_ptr(),
-                                       sp.data_ptr() if want_pred else None,
-                                       vp.data_ptr() if want_pred else None, status.data_ptr(), self._stream()))
-        return out, sp, vp, status
+        return self._step(self.lib.eepacc_tv_step, (s, v, a_prev, t0), want_pred)
 
     def run_tvmpc(self, s0, v0, a_minus1, n_steps: int, resume: bool = False, out=None):
         """eepacc_run_tvmpc: closed loop of n_steps from s0 = TVinitDist, v0 = TVinitVel, a_minus1 (each [B]).
         Returns traj [n_steps, OUT_N, B], status [n_steps, B]; resume / out as run_abmpc."""
-        t = self.torch
-        if not resume:
-            self.reset()
-        B = int(t.as_tensor(s0).numel())
-        n_steps = int(n_steps)
-        ins = [self._d(x, B) for x in (s0, v0, a_minus1)]
-        if out is not None:
-            traj, status = out[0][:n_steps], out[1][:n_steps]
-            assert traj.shape == (n_steps, OUT_N, B) and traj.is_contiguous() and status.is_contiguous()
-        else:
-            traj = t.empty((n_steps, OUT_N, B), dtype=t.float64, device=self.device)
-            status = t.empty((n_steps, B), dtype=t.int32, device=self.device)
-        _check(self.lib.eepacc_run_tvmpc(self.h, B, n_steps, *[x.data_ptr() for x in ins], traj.data_ptr(),
-                                         status.data_ptr(), self._stream()))
-        return traj, status
-
-    def run_tvmpc_host(self, s0, v0, a_minus1, n_steps: int):
-        """eepacc_run_tvmpc_host: host (numpy) buffers in and out -- the entry the MEX gateway calls."""
-        ins = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1)) for x in (s0, v0, a_minus1)]
-        B = ins[0].size
-        assert all(x.size == B for x in ins)
-        traj = np.empty((n_steps, OUT_N, B)); status = np.empty((n_steps, B), dtype=np.int32)
-        _check(self.lib.eepacc_run_tvmpc_host(self.h, B, int(n_steps), *[as_dptr(x) for x in ins], as_dptr(traj),
-                                              status.ctypes.data_as(C.POINTER(C.c_int32))))
-        return traj, status
+        return self._run(self.lib.eepacc_run_tvmpc, (s0, v0, a_minus1), None, n_steps, resume, out)
 
     # FBMPC: same two operators (ABO/RunOpt_FBMPC.m:161-331) -----------------------------------
     def fb_step(self, s, v, v_prev, a_prev, Fm_prev, Fb_prev, t0, s_tv, v_tv, a_tv_prev, want_pred: bool = True):
-        t = self.torch
-        B = int(t.as_tensor(s).numel())
-        ins = [self._d(x, B) for x in (s, v, v_prev, a_prev, Fm_prev, Fb_prev, t0, s_tv, v_tv, a_tv_prev)]
-        out = t.empty((OUT_N, B), dtype=t.float64, device=self.device)
-        sp = t.empty((self.N + 1, B), dtype=t.float64, device=self.device) if want_pred else None
-        vp = t.empty((self.N + 1, B), dtype=t.float64, device=self.device) if want_pred else None
-        status = t.empty((B,), dtype=t.int32, device=self.device)
-        _check(self.lib.eepacc_fb_step(self.h, B, *[x.data_ptr() for x in ins], out.data_ptr(),
-                                       sp.data_ptr() if want_pred else None,
-                                       vp.data_ptr() if want_pred else None, status.data_ptr(), self._stream()))
-        return out, sp, vp, status
+        return self._step(self.lib.eepacc_fb_step, (s, v, v_prev, a_prev, Fm_prev, Fb_prev, t0, s_tv, v_tv, a_tv_prev), want_pred)
 
     def run_fbmpc(self, s0, v0, a_minus1, s_tv, v_tv, resume: bool = False, out=None):
         """Closed-loop FBMPC; arguments and results as run_abmpc."""
-        t = self.torch
-        if not resume:
-            self.reset()
-        s_tv = t.as_tensor(s_tv, dtype=t.float64, device=self.device).contiguous()
-        v_tv = t.as_tensor(v_tv, dtype=t.float64, device=self.device).contiguous()
-        n_steps, B = s_tv.shape
-        ins = [self._d(x, B) for x in (s0, v0, a_minus1)]
-        if out is not None:
-            traj, status = out[0][:n_steps], out[1][:n_steps]
-            assert traj.shape == (n_steps, OUT_N, B) and traj.is_contiguous() and status.is_contiguous()
-        else:
-            traj = t.empty((n_steps, OUT_N, B), dtype=t.float64, device=self.device)
-            status = t.empty((n_steps, B), dtype=t.int32, device=self.device)
-        _check(self.lib.eepacc_run_fbmpc(self.h, B, n_steps, *[x.data_ptr() for x in ins], s_tv.data_ptr(),
-                                         v_tv.data_ptr(), traj.data_ptr(), status.data_ptr(), self._stream()))
-        return traj, status
+        return self._run(self.lib.eepacc_run_fbmpc, (s0, v0, a_minus1), (s_tv, v_tv), None, resume, out)
 
     def postprocess(self, traj):
         t = self.torch
@@ -276,27 +225,60 @@ class Engine:
         """Wait for the engine's stream; raises if a closed-loop launch flagged a device-side failure."""
         _check(self.lib.eepacc_synchronize(self.h, self._stream()))
 
-    def _run_host(self, fn, s0, v0, a_minus1, s_tv, v_tv):
-        s_tv = np.ascontiguousarray(s_tv, dtype=np.float64); v_tv = np.ascontiguousarray(v_tv, dtype=np.float64)
-        n_steps, B = s_tv.shape
+    def _run_host(self, fn, s0, v0, a_minus1, lead, n_steps=None):
+        """Host (numpy) buffers in and out -- the entries the MEX gateways call.  lead = (s_tv, v_tv) or () with n_steps."""
+        lead = [np.ascontiguousarray(x, dtype=np.float64) for x in lead]
         ins = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1)) for x in (s0, v0, a_minus1)]
+        n_steps, B = lead[0].shape if lead else (int(n_steps), ins[0].size)
         assert all(x.size == B for x in ins)
         traj = np.empty((n_steps, OUT_N, B)); status = np.empty((n_steps, B), dtype=np.int32)
-        _check(fn(self.h, B, n_steps, *[as_dptr(x) for x in ins], as_dptr(s_tv), as_dptr(v_tv), as_dptr(traj),
+        _check(fn(self.h, B, n_steps, *[as_dptr(x) for x in ins + lead], as_dptr(traj),
                   status.ctypes.data_as(C.POINTER(C.c_int32))))
         return traj, status
 
     def run_abmpc_host(self, s0, v0, a_minus1, s_tv, v_tv):
         """eepacc_run_abmpc_host: host (numpy) buffers in and out -- the entry a MEX gateway calls."""
-        return self._run_host(self.lib.eepacc_run_abmpc_host, s0, v0, a_minus1, s_tv, v_tv)
+        return self._run_host(self.lib.eepacc_run_abmpc_host, s0, v0, a_minus1, (s_tv, v_tv))
+
+    def run_blmpc_host(self, s0, v0, a_minus1, s_tv, v_tv):
+        return self._run_host(self.lib.eepacc_run_blmpc_host, s0, v0, a_minus1, (s_tv, v_tv))
 
     def run_fbmpc_host(self, s0, v0, a_minus1, s_tv, v_tv):
-        return self._run_host(self.lib.eepacc_run_fbmpc_host, s0, v0, a_minus1, s_tv, v_tv)
+        return self._run_host(self.lib.eepacc_run_fbmpc_host, s0, v0, a_minus1, (s_tv, v_tv))
+
+    def run_tvmpc_host(self, s0, v0, a_minus1, n_steps: int):
+        """eepacc_run_tvmpc_host: host (numpy) buffers in and out -- the entry the MEX gateway calls."""
+        return self._run_host(self.lib.eepacc_run_tvmpc_host, s0, v0, a_minus1, (), n_steps)
 
     def last_iterations(self, B):
         it = np.zeros(B, dtype=np.int32)
         _check(self.lib.eepacc_last_iterations(self.h, B, it.ctypes.data_as(C.POINTER(C.c_int32))))
         return it
+
+
+_FIELDS_AB = ("s", "v", "Fm", "Fb", "xi_v", "xi_h", "xi_s", "xi_f", "a", "DistHor", "cost")      # RunOpt_ABMPC / RunOpt_FBMPC
+_FIELDS_BL = ("s", "v", "Fm", "Fb", "xi_f", "a", "cost")
+
+
+def _opt_sol(eng: "Engine", run, OPTsettings, Ts: float, fields, costs=()) -> Dict[str, Any]:
+    """Single-vehicle closed loop over t_sim and the optSol the three RunOpt_*MPC functions share: the fields of the
+    trajectory, exitMessage, the post-processed series, j_opt and the cumulative cost_* series.
+    costs: (name, weight, series as a function of sol) in the reference's order."""
+    n_steps = int(round(OPTsettings["t_sim"] / Ts)) + 1
+    s_tv = np.asarray(OPTsettings["s_tv"], dtype=np.float64).reshape(-1)[:n_steps].reshape(n_steps, 1)
+    v_tv = np.asarray(OPTsettings["v_tv"], dtype=np.float64).reshape(-1)[:n_steps].reshape(n_steps, 1)
+    traj, status = run([OPTsettings["s_init"]], [OPTsettings["v_init"]], [OPTsettings["a_minus1"]], s_tv, v_tv)
+    post = eng.postprocess(traj)
+    eng.torch.cuda.synchronize()
+    tr = traj.cpu().numpy()[:, :, 0]
+    sol: Dict[str, Any] = {(name if name in ("DistHor", "cost") else name + "_opt"): tr[:, OUT[name]].copy() for name in fields}
+    sol["exitMessage"] = status.cpu().numpy()[:, 0].astype(np.float64)
+    for key, x in zip(("rpm_opt", "Tm_opt", "P_opt", "E_opt"), post):
+        sol[key] = x.cpu().numpy()[:, 0]
+    sol["j_opt"] = np.diff(sol["a_opt"]) / Ts
+    for nm, w, series in costs:
+        sol[nm] = w * np.cumsum(series(sol))[:n_steps - 1]
+    return sol
 
 
 def RunOpt_ABMPC(OPTsettings: Dict[str, Any], V: Optional[Dict[str, float]] = None, device: int = 0) -> Dict[str, Any]:
@@ -308,31 +290,11 @@ def RunOpt_ABMPC(OPTsettings: Dict[str, Any], V: Optional[Dict[str, float]] = No
     if V is None:
         V = SetVehicleParameters(OPTsettings.get("tree", "ABO"))
     eng = Engine(OPTsettings, V, device=device, max_batch=1)
-    t = eng.torch
-    Ts = float(OPTsettings["Tvec"][0])
-    n_steps = int(round(OPTsettings["t_sim"] / Ts)) + 1
-    s_tv = np.asarray(OPTsettings["s_tv"], dtype=np.float64).reshape(-1)[:n_steps].reshape(n_steps, 1)
-    v_tv = np.asarray(OPTsettings["v_tv"], dtype=np.float64).reshape(-1)[:n_steps].reshape(n_steps, 1)
-    traj, status = eng.run_abmpc([OPTsettings["s_init"]], [OPTsettings["v_init"]], [OPTsettings["a_minus1"]], s_tv, v_tv)
-    rpm, Tm, P, E = eng.postprocess(traj)
-    t.cuda.synchronize()
-    tr = traj.cpu().numpy()[:, :, 0]
-    sol: Dict[str, Any] = {}
-    for name, key in (("s", "s_opt"), ("v", "v_opt"), ("Fm", "Fm_opt"), ("Fb", "Fb_opt"), ("xi_v", "xi_v_opt"),
-                      ("xi_h", "xi_h_opt"), ("xi_s", "xi_s_opt"), ("xi_f", "xi_f_opt"), ("a", "a_opt"),
-                      ("DistHor", "DistHor"), ("cost", "cost")):
-        sol[key] = tr[:, OUT[name]].copy()
-    sol["exitMessage"] = status.cpu().numpy()[:, 0].astype(np.float64)
-    sol["rpm_opt"] = rpm.cpu().numpy()[:, 0]; sol["Tm_opt"] = Tm.cpu().numpy()[:, 0]
-    sol["P_opt"] = P.cpu().numpy()[:, 0]; sol["E_opt"] = E.cpu().numpy()[:, 0]
-    sol["j_opt"] = np.diff(sol["a_opt"]) / Ts
     W = np.asarray(OPTsettings["W_AB"]).ravel()      # cost_* use W(1..5) as the reference does (:383-388)
-    N_sim = n_steps - 1
-    for nm, w, arr in (("cost_a", W[0], sol["a_opt"] ** 2), ("cost_j", W[1], sol["j_opt"] ** 2),
-                       ("cost_xi_v", W[2], sol["xi_v_opt"]), ("cost_xi_h", W[3], sol["xi_h_opt"]),
-                       ("cost_xi_s", W[4], sol["xi_s_opt"]), ("cost_xi_f", W[4], sol["xi_f_opt"])):
-        sol[nm] = w * np.cumsum(arr)[:N_sim]
-    return sol
+    return _opt_sol(eng, eng.run_abmpc, OPTsettings, float(OPTsettings["Tvec"][0]), _FIELDS_AB, (
+        ("cost_a", W[0], lambda o: o["a_opt"] ** 2), ("cost_j", W[1], lambda o: o["j_opt"] ** 2),
+        ("cost_xi_v", W[2], lambda o: o["xi_v_opt"]), ("cost_xi_h", W[3], lambda o: o["xi_h_opt"]),
+        ("cost_xi_s", W[4], lambda o: o["xi_s_opt"]), ("cost_xi_f", W[4], lambda o: o["xi_f_opt"])))
 
 
 def RunOpt_BLMPC(OPTsettings: Dict[str, Any], V: Optional[Dict[str, float]] = None, device: int = 0) -> Dict[str, Any]:
@@ -345,24 +307,7 @@ def RunOpt_BLMPC(OPTsettings: Dict[str, Any], V: Optional[Dict[str, float]] = No
         V = SetVehicleParameters(OPTsettings.get("tree", "ABO"))
     BL = Settings_BL(OPTsettings)
     eng = Engine(BL, V, device=device, max_batch=1)
-    t = eng.torch
-    Ts = float(BL["Tvec"][0])
-    n_steps = int(round(OPTsettings["t_sim"] / Ts)) + 1
-    s_tv = np.asarray(OPTsettings["s_tv"], dtype=np.float64).reshape(-1)[:n_steps].reshape(n_steps, 1)
-    v_tv = np.asarray(OPTsettings["v_tv"], dtype=np.float64).reshape(-1)[:n_steps].reshape(n_steps, 1)
-    traj, status = eng.run_blmpc([OPTsettings["s_init"]], [OPTsettings["v_init"]], [OPTsettings["a_minus1"]], s_tv, v_tv)
-    rpm, Tm, P, E = eng.postprocess(traj)
-    t.cuda.synchronize()
-    tr = traj.cpu().numpy()[:, :, 0]
-    sol: Dict[str, Any] = {}
-    for name, key in (("s", "s_opt"), ("v", "v_opt"), ("Fm", "Fm_opt"), ("Fb", "Fb_opt"), ("xi_f", "xi_f_opt"),
-                      ("a", "a_opt"), ("cost", "cost")):
-        sol[key] = tr[:, OUT[name]].copy()
-    sol["exitMessage"] = status.cpu().numpy()[:, 0].astype(np.float64)
-    sol["rpm_opt"] = rpm.cpu().numpy()[:, 0]; sol["Tm_opt"] = Tm.cpu().numpy()[:, 0]
-    sol["P_opt"] = P.cpu().numpy()[:, 0]; sol["E_opt"] = E.cpu().numpy()[:, 0]
-    sol["j_opt"] = np.diff(sol["a_opt"]) / Ts
-    return sol
+    return _opt_sol(eng, eng.run_blmpc, OPTsettings, float(BL["Tvec"][0]), _FIELDS_BL)
 
 
 def RunOpt_TVMPC(OPTsettings: Dict[str, Any], V: Optional[Dict[str, float]] = None, device: int = 0):
@@ -429,29 +374,9 @@ def RunOpt_FBMPC(OPTsettings: Dict[str, Any], V: Optional[Dict[str, float]] = No
     if V is None:
         V = SetVehicleParameters(OPTsettings.get("tree", "ABO"))
     eng = Engine(OPTsettings, V, device=device, max_batch=1)
-    t = eng.torch
-    Ts = float(OPTsettings["Tvec"][0])
-    n_steps = int(round(OPTsettings["t_sim"] / Ts)) + 1
-    s_tv = np.asarray(OPTsettings["s_tv"], dtype=np.float64).reshape(-1)[:n_steps].reshape(n_steps, 1)
-    v_tv = np.asarray(OPTsettings["v_tv"], dtype=np.float64).reshape(-1)[:n_steps].reshape(n_steps, 1)
-    traj, status = eng.run_fbmpc([OPTsettings["s_init"]], [OPTsettings["v_init"]], [OPTsettings["a_minus1"]], s_tv, v_tv)
-    rpm, Tm, P, E = eng.postprocess(traj)
-    t.cuda.synchronize()
-    tr = traj.cpu().numpy()[:, :, 0]
-    sol: Dict[str, Any] = {}
-    for name, key in (("s", "s_opt"), ("v", "v_opt"), ("Fm", "Fm_opt"), ("Fb", "Fb_opt"), ("xi_v", "xi_v_opt"),
-                      ("xi_h", "xi_h_opt"), ("xi_s", "xi_s_opt"), ("xi_f", "xi_f_opt"), ("a", "a_opt"),
-                      ("DistHor", "DistHor"), ("cost", "cost")):
-        sol[key] = tr[:, OUT[name]].copy()
-    sol["exitMessage"] = status.cpu().numpy()[:, 0].astype(np.float64)
-    sol["rpm_opt"] = rpm.cpu().numpy()[:, 0]; sol["Tm_opt"] = Tm.cpu().numpy()[:, 0]
-    sol["P_opt"] = P.cpu().numpy()[:, 0]; sol["E_opt"] = E.cpu().numpy()[:, 0]
-    sol["j_opt"] = np.diff(sol["a_opt"]) / Ts
     W = np.asarray(OPTsettings["W_FB"]).ravel()      # :373-390
-    N_sim = n_steps - 1
-    for nm, w, arr in (("cost_P", W[0], sol["P_opt"] ** 2), ("cost_a", W[1], sol["a_opt"] ** 2),
-                       ("cost_j", W[2], sol["j_opt"] ** 2), ("cost_xi_v", W[3], sol["xi_v_opt"]),
-                       ("cost_xi_h", W[4], sol["xi_h_opt"]), ("cost_xi_s", W[5], sol["xi_s_opt"]),
-                       ("cost_xi_f", W[6], sol["xi_f_opt"])):
-        sol[nm] = w * np.cumsum(arr)[:N_sim]
-    return sol
+    return _opt_sol(eng, eng.run_fbmpc, OPTsettings, float(OPTsettings["Tvec"][0]), _FIELDS_AB, (
+        ("cost_P", W[0], lambda o: o["P_opt"] ** 2), ("cost_a", W[1], lambda o: o["a_opt"] ** 2),
+        ("cost_j", W[2], lambda o: o["j_opt"] ** 2), ("cost_xi_v", W[3], lambda o: o["xi_v_opt"]),
+        ("cost_xi_h", W[4], lambda o: o["xi_h_opt"]), ("cost_xi_s", W[5], lambda o: o["xi_s_opt"]),
+        ("cost_xi_f", W[6], lambda o: o["xi_f_opt"])))

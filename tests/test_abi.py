@@ -85,6 +85,51 @@ def test_settings_validation_messages(lib):
     assert b"Mb[0]" in lib.eepacc_last_error()
 
 
+def test_unsupported_settings_codes_and_messages(lib):
+    """What build_cfg refuses, with the code and the text the callers (tests, MEX gateways) see."""
+    from eepacc_mpc_casadi_matlab_amd.settings import Settings_TV
+    OPT, V, *_ = make_case("ABO", 20)
+    veh = make_vehicle(V)
+    tv = Settings_TV(OPT)
+    tv["Tvec"] = tv["Tvec"].copy(); tv["Tvec"][3] *= 2.0
+    for o, code, msg in (
+            (dict(OPT, solverToUse=2), -4, "solverToUse == 2 (HPIPM formulation, ABO/Settings.m:114) is not built"),
+            (dict(OPT, bl_mode=3), -1, "bl_mode must be 0, 1 (RunOpt_BLMPC) or 2 (RunOpt_TVMPC)"),
+            (dict(OPT, Mb=[1, 0] * 10), -1, "Mb[0] must be 0 (the first stage has no predecessor in the horizon)"),
+            (tv, -1, "bl_mode = 2: Tvec must be uniform (TV_Ts, CreateQP_TV.m:29)")):
+        holder = SettingsHolder(o)
+        h = C.c_void_p()
+        assert lib.eepacc_create(C.byref(h), C.byref(holder.pod), C.byref(veh), 0, 16) == code, o.get("bl_mode")
+        assert lib.eepacc_last_error().decode() == msg
+        assert not h.value
+
+
+def test_any_header_makes_the_library_stale(tmp_path):
+    """Staleness looks at every header under csrc/ and include/, not at a list: a header nobody registered counts."""
+    import importlib.util
+    import shutil
+    pkg = tmp_path / "pkg"
+    (pkg / "csrc").mkdir(parents=True)
+    (tmp_path / "include").mkdir()
+    shutil.copy(eb.__file__, pkg / "build.py")
+    for f in eb.SOURCES:
+        (pkg / "csrc" / f).write_text("")
+    (pkg / "libeepacc.so").write_text("")
+    (pkg / "libeepacc.flags").write_text(eb.extra_flags() + "\n")
+    spec = importlib.util.spec_from_file_location("build_copy", pkg / "build.py")
+    b = importlib.util.module_from_spec(spec); spec.loader.exec_module(b)
+    now = os.path.getmtime(pkg / "libeepacc.so")
+    for f in (pkg / "csrc").iterdir():
+        os.utime(f, (now - 10, now - 10))
+    assert not b.is_stale()
+    for probe in (pkg / "csrc" / "zz_probe.h", pkg / "csrc" / "zz_probe.inc", tmp_path / "include" / "zz_probe.h"):
+        probe.write_text("")
+        os.utime(probe, (now + 10, now + 10))
+        assert b.is_stale(), probe
+        probe.unlink()
+        assert not b.is_stale()
+
+
 def test_nlp_header_symbols_and_layout(lib):
     """include/eepacc_nlp.h (function evaluator of RunOpt_NLP's problem): every declared entry is exported, the
     ctypes mirror of eepacc_nlp_problem has the compiled size, and creation fails loudly without a GPU."""
