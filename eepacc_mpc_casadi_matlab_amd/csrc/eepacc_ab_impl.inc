@@ -144,6 +144,30 @@ __device__ __forceinline__ double mb_expand(const Lane& L, const Cfg& c, double 
     return L.lane < L.N ? y : x;
 }
 
+// the same two maps for a wave whose halves each carry a horizon of their own (eepacc_ab_cols.h): stage k = l & 31
+__device__ __forceinline__ double mb_reduce_half(const Lane& L, const Cfg& c, double x) {
+    if constexpr (!kMoveBlocking) return x;
+    if (c.mb_len == 0) return x;
+    const int hl = L.lane & 31;
+    const int k = hl <= L.N ? hl : L.N;
+    const int end = c.mb_end[k];
+    const bool leader = c.mb_lead[k] == k && hl < L.N;
+    double acc = x;
+    for (int d = 1; d < c.mb_len; ++d) {
+        const double y = __shfl_down(x, d, 64);
+        if (hl + d <= end) acc += y;
+    }
+    return leader ? acc : 0.0;
+}
+__device__ __forceinline__ double mb_expand_half(const Lane& L, const Cfg& c, double x) {
+    if constexpr (!kMoveBlocking) return x;
+    if (c.mb_len == 0) return x;
+    const int hl = L.lane & 31;
+    const int k = hl < L.N ? hl : 0;
+    const double y = __shfl(x, c.mb_lead[k] + (L.lane & 32), 64);
+    return hl < L.N ? y : x;
+}
+
 __device__ __forceinline__ double group_w(const Cfg& c, int g) {
     return g == G_F ? c.wF : (g == G_S ? c.wS : (g == G_V ? c.wV : c.wH));
 }
@@ -192,6 +216,13 @@ __device__ __forceinline__ void hom_traj(const Lane& L, double x, double& sh, do
 template <int NS> constexpr bool kPackedHe = NS > 32;
 template <int NS> constexpr int kHeDoubles = kPackedHe<NS> ? NS * (NS + 1) / 2 : NS * NS;
 
+// out = He yv for the passes of the solve: at NS = 32 the sum of a column is split over the two halves of the wave
+template <int NS>
+__device__ __forceinline__ double he_apply(const double* Hs, const double* yv, int N, int lane) {
+    if constexpr (kPackedHe<NS>) return he_mul<NS, true>(Hs, yv, N, lane);
+    else return he_mul_halves<NS>(Hs, yv, N, lane);
+}
+
 // a-space normal of the row (kq; al,be,ga,de) evaluated at this lane j:
 __device__ __forceinline__ double normal_at(const Lane& L, int kq, double al, double be, double ga, double de, double tau_kq) {
     double c = 0.0;
@@ -238,14 +269,18 @@ __device__ __forceinline__ void he_rank1(const Lane& L, const Cfg& c, WaveMem<MM
     const double nk = mb_reduce(L, c, normal_at(L, k, 1.0, chwk, 0.0, 0.0, tauv[k]));
     if (lane < NS) M.yv[lane] = nk;
     WSYNC();
-    const double y = he_mul<NS, kPackedHe<NS>>(He, M.yv, N, lane);          // in the reduced variables: the table is updated with it
+    const double y = he_apply<NS>(He, M.yv, N, lane);          // in the reduced variables: the table is updated with it
     double sy, vy;
     hom_traj(L, mb_expand(L, c, y), sy, vy);
     const double ny = bcast(sy + chwk * vy, k);                 // n_k' y
     const double kappa = add ? c.qH / (1.0 + c.qH * ny) : -c.qH / (1.0 - c.qH * ny);
     if (lane < NS) M.ub[lane] = y;          // y is zero beyond N
     WSYNC();
-    if (lane < NS) he_sub_outer<NS, kPackedHe<NS>>(He, M.ub, kappa * y, lane);
+    if constexpr (kPackedHe<NS>) {
+        if (lane < NS) he_sub_outer<NS, true>(He, M.ub, kappa * y, lane);
+    } else {
+        he_sub_outer_halves<NS>(He, M.ub, kappa * M.ub[lane & (NS - 1)], lane);      // two lanes per column
+    }
     WSYNC();
 }
 
@@ -356,7 +391,11 @@ __device__ __forceinline__ int rebuild_and_factor(Lane& L, const Cfg& c, WaveMem
     // S columns: u_j = He c_j, two columns per pass: each He element is loaded once for both products,
     // the scan chains of the two trajectories overlap, and row i picks the images at its stage with
     // lane shuffles (no LDS round trip).  Input vectors in yv | lam (free while the factor is rebuilt).
-    {
+    if constexpr (!kPackedHe<NS>) {
+        // four columns per pass, two per half of the wave (eepacc_ab_cols.h); P is the two-column loop's bit for bit
+        ab_schur_columns4<NS>(M, Hs, tauv, m, N, lane, half_lo(L.T), half_lo(L.tau1),
+                              [&](double x) { return mb_reduce_half(L, c, x); }, [&](double x) { return mb_expand_half(L, c, x); });
+    } else {
         const int ki = lane < m ? M.w_k[lane] : 0;
         const int kim1 = ki > 0 ? ki - 1 : 0;
         const double eal = lane < m ? M.e_al[lane] : 0.0, ebe = lane < m ? M.e_be[lane] : 0.0;
@@ -477,7 +516,7 @@ __device__ __forceinline__ void primal_from_multipliers(Lane& L, const Cfg& c, W
     g = mb_reduce(L, c, g);
     if (L.lane < NS) M.yv[L.lane] = g;
     WSYNC();
-    L.a = -mb_expand(L, c, he_mul<NS, kPackedHe<NS>>(Hs, M.yv, L.N, L.lane));
+    L.a = -mb_expand(L, c, he_apply<NS>(Hs, M.yv, L.N, L.lane));
     hom_traj(L, L.a, L.sh, L.vh);
     L.am1 = dpp_zero<0x138, 0xf>(L.a);
     if (L.lane < L.N) M.av[L.lane] = L.a;
@@ -844,7 +883,7 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const Cfg& c, WaveMem<MM
             double g = mb_reduce(L, c, gradient_side(L, c, M, 0, false, lam_q, q.kq, q.al, q.be, q.ga, q.de));
             if (lane < NS) M.yv[lane] = g;
             WSYNC();
-            double h = mb_expand(L, c, he_mul<NS, kPackedHe<NS>>(Hs, M.yv, N, lane));
+            double h = mb_expand(L, c, he_apply<NS>(Hs, M.yv, N, lane));
             double shh, vhh;
             hom_traj(L, h, shh, vhh);
             if (lane < N) M.ub[lane] = h;
@@ -971,7 +1010,7 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const Cfg& c, WaveMem<MM
         double cj = mb_reduce(L, c, normal_at(L, kq, q.al, q.be, q.ga, q.de, tauv[kq]));
         if (lane < NS) M.yv[lane] = cj;
         WSYNC();
-        double u = mb_expand(L, c, he_mul<NS, kPackedHe<NS>>(Hs, M.yv, N, lane));
+        double u = mb_expand(L, c, he_apply<NS>(Hs, M.yv, N, lane));
         double su, vu;
         hom_traj(L, u, su, vu);
         if (lane < N) M.ub[lane] = u;
@@ -1128,7 +1167,7 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const Cfg& c, WaveMem<MM
             const double y = mb_reduce(L, c, direction_side(L, M, m, kq, q.al, q.be, q.ga, q.de));
             if (lane < NS) M.yv[lane] = y;
             WSYNC();
-            const double z = mb_expand(L, c, he_mul<NS, kPackedHe<NS>>(Hs, M.yv, N, lane));
+            const double z = mb_expand(L, c, he_apply<NS>(Hs, M.yv, N, lane));
             double sz, vz;
             hom_traj(L, z, sz, vz);
             L.a = fma(-tstep, z, L.a); L.sh = fma(-tstep, sz, L.sh); L.vh = fma(-tstep, vz, L.vh);

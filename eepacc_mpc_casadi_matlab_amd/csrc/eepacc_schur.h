@@ -98,6 +98,49 @@ __device__ __forceinline__ void he_sub_outer(double* He, const double* yv, doubl
     }
 }
 
+// ---- full layout at NS = 32: a column takes half a wave, so the other half shares the work (the split he_invert_full
+// uses: lane l works on rows [16 (l >> 5), +16) of column l & 31).  The functions above keep serving the packed layout,
+// NS = 64 and the FBMPC kernels.
+
+// He -= yv yj' with all 64 lanes; yj = the scaled second factor's entry l & 31, in both halves.  Every entry is the one
+// fma of he_sub_outer: the table comes out bit for bit the same.
+template <int NS>
+__device__ __forceinline__ void he_sub_outer_halves(double* He, const double* yv, double yj, int lane) {
+    static_assert(NS == 32, "two lanes per column");
+    constexpr int RPL = NS / 2;
+    const int r0 = (lane & NS) / 2;
+    double* col = He + r0 * NS + (lane & (NS - 1));
+    const double* y = yv + r0;
+#pragma unroll
+    for (int i = 0; i < RPL; i += 4) {
+        const double h0 = col[(i + 0) * NS], h1 = col[(i + 1) * NS], h2 = col[(i + 2) * NS], h3 = col[(i + 3) * NS];
+        const double y0 = y[i], y1 = y[i + 1], y2 = y[i + 2], y3 = y[i + 3];
+        col[(i + 0) * NS] = fma(-y0, yj, h0); col[(i + 1) * NS] = fma(-y1, yj, h1);
+        col[(i + 2) * NS] = fma(-y2, yj, h2); col[(i + 3) * NS] = fma(-y3, yj, h3);
+    }
+}
+
+// out_k = sum_i He[i][k] yv[i] with the sum split over the halves: 16 terms per lane, then one cross-half add.  The
+// order of summation differs from he_mul's (rounding-level differences).  Lanes >= N return exactly 0.
+template <int NS>
+__device__ __forceinline__ double he_mul_halves(const double* Hs, const double* yv, int N, int lane) {
+    static_assert(NS == 32, "two lanes per column");
+    constexpr int RPL = NS / 2;
+    const int r0 = (lane & NS) / 2;
+    const double* col = Hs + r0 * NS + (lane & (NS - 1));
+    const double* y = yv + r0;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+#pragma unroll
+    for (int i = 0; i < RPL; i += 4) {
+        a0 = fma(col[(i + 0) * NS], y[i + 0], a0);
+        a1 = fma(col[(i + 1) * NS], y[i + 1], a1);
+        a2 = fma(col[(i + 2) * NS], y[i + 2], a2);
+        a3 = fma(col[(i + 3) * NS], y[i + 3], a3);
+    }
+    const double s = wv::half_sum((a0 + a1) + (a2 + a3));
+    return lane < N ? s : 0.0;
+}
+
 // In-place inverse of the positive definite N x N matrix in the full NS x NS table Hs by symmetric sweeps; afterwards
 // Hs = -H^-1 (the caller negates).  colk: NS doubles of LDS scratch.  Returns non-zero on a non-positive pivot.
 template <int NS>

@@ -66,6 +66,34 @@ __device__ __forceinline__ double scan_incl(double x) {
 }
 __device__ __forceinline__ double wave_sum(double x) { return read_lane63(scan_incl(x)); }
 __device__ __forceinline__ double scan_excl(double x) { return dpp_zero<0x138, 0xf>(scan_incl(x)); }
+// The same scan over each 32-lane half on its own (lanes 0-31 and lanes 32-63 each hold a problem of their own): the
+// steps of scan_incl without row_bcast:31, and lane 32 reads zero.  Lanes 0-31 get what scan_incl / scan_excl give them,
+// bit for bit.
+__device__ __forceinline__ double scan_incl_half(double x) {
+    x += dpp_zero<0x111, 0xf>(x);
+    x += dpp_zero<0x112, 0xf>(x);
+    x += dpp_zero<0x114, 0xf>(x);
+    x += dpp_zero<0x118, 0xf>(x);
+    x += dpp_zero<0x142, 0xa>(x);
+    return x;
+}
+__device__ __forceinline__ double scan_excl_half(double x) {
+    x = dpp_zero<0x138, 0xf>(scan_incl_half(x));
+    return lane_id() == 32 ? 0.0 : x;
+}
+// v_permlane32_swap of a register with itself: lo = the value of lane l & 31, hi = the value of lane (l & 31) + 32, in
+// both halves of the wave (VALU, no LDS round trip)
+__device__ __forceinline__ void half_pair(double x, double& lo, double& hi) {
+    const unsigned xl = (unsigned)__double2loint(x), xh = (unsigned)__double2hiint(x);
+    const auto a = __builtin_amdgcn_permlane32_swap(xl, xl, false, false);
+    const auto b = __builtin_amdgcn_permlane32_swap(xh, xh, false, false);
+    lo = __hiloint2double((int)b[0], (int)a[0]);
+    hi = __hiloint2double((int)b[1], (int)a[1]);
+}
+// the value of lane l & 31, in both halves
+__device__ __forceinline__ double half_lo(double x) { double lo, hi; half_pair(x, lo, hi); return lo; }
+// x of lane l & 31 plus x of lane (l & 31) + 32, in both halves (lower half first in both: the halves agree bit for bit)
+__device__ __forceinline__ double half_sum(double x) { double lo, hi; half_pair(x, lo, hi); return lo + hi; }
 // exclusive prefix product (lane 0 gets 1)
 __device__ __forceinline__ double scan_prod_excl(double x) {
     x *= dpp_fill<0x111, 0xf>(x, 1.0);
