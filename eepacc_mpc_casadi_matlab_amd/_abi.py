@@ -10,6 +10,7 @@ c_double_p = C.POINTER(C.c_double)
 c_int32_p = C.POINTER(C.c_int32)
 
 EEPACC_MAX_HORIZON = 63
+EEPACC_MAX_CLASSES = 4096
 
 OUT_FIELDS = ["s", "v", "Fm", "Fb", "a", "xi_v", "xi_h", "xi_s", "xi_f", "cost", "DistHor", "a_qp"]
 OUT_N = len(OUT_FIELDS)
@@ -146,6 +147,15 @@ class SettingsHolder:
             raise ValueError(f"expected {n} entries, got {a.size}")
         self._keep.append(a)
         return a.ctypes.data_as(c_double_p)
+
+
+def pack_classes(OPT_list, V_list):
+    """The S[n_classes], V[n_classes] arrays of eepacc_create_classes.  Returns (holders, S, V): the holders own the buffers
+    the entries of S point into and must outlive the call."""
+    holders = [SettingsHolder(o) for o in OPT_list]
+    S = (SettingsPOD * len(holders))(*[h.pod for h in holders])
+    V = (Vehicle * len(V_list))(*[make_vehicle(v) for v in V_list])
+    return holders, S, V
 
 
 def as_dptr(a: np.ndarray):

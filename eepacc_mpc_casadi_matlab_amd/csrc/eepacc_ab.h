@@ -10,9 +10,10 @@
 namespace eepacc {
 
 // One instantiation of eepacc_ab_impl.inc each; EEPACC_AB_VARIANTS (eepacc_kernels.hip) gives namespace and switches.
-enum class AbVariant { Plain, MoveBlocking, Baseline, Ice, IceMoveBlocking, TargetVehicle };
+enum class AbVariant { Plain, MoveBlocking, Baseline, Ice, IceMoveBlocking, TargetVehicle, Classes };
 
-// kernel variant of a handle: the baseline controllers (bl_mode) come before the ICE-map fuel term and move blocking
+// kernel variant of a handle: the baseline controllers (bl_mode) come before the ICE-map fuel term and move blocking.
+// AbVariant::Classes cannot be told from a DevCfg: a handle of eepacc_create_classes carries that choice itself.
 inline AbVariant ab_variant(const DevCfg& C) {
     if (C.bl_mode) return C.bl_mode == 2 ? AbVariant::TargetVehicle : AbVariant::Baseline;
     if (C.ab_fuel_term == 2) return C.mb_any ? AbVariant::IceMoveBlocking : AbVariant::Ice;
@@ -23,17 +24,19 @@ size_t ab_smem_bytes(int N);
 size_t ab_hb_doubles(int N, int B, int num_cus);
 hipError_t set_max_smem();
 int pick_chunk_steps(int n_steps, int B, int resident_waves);
-// s_tv, v_tv, a_tv_prev: null for AbVariant::TargetVehicle, whose kernels read no lead inputs
-hipError_t launch_ab_step(const DevCfg* dC, int N, AbVariant variant, int B, const double* s, const double* v,
+// s_tv, v_tv, a_tv_prev: null for AbVariant::TargetVehicle, whose kernels read no lead inputs.
+// AbVariant::Classes: dC is the class array DevCfg[n_classes] and class_of the device map [B] of the launch; every other
+// variant reads dC[0] alone and takes class_of = null (launch_postprocess: null selects the one-config kernel).
+hipError_t launch_ab_step(const DevCfg* dC, const int32_t* class_of, int N, AbVariant variant, int B, const double* s, const double* v,
                           const double* a_prev, const double* t0, const double* s_tv, const double* v_tv,
                           const double* a_tv_prev, unsigned long long* codes, double* out, double* s_pred, double* v_pred,
                           int32_t* status, int32_t* iters, hipStream_t stream);
-hipError_t launch_run_abmpc(const DevCfg* dC, int N, AbVariant variant, int B, int k_start, int n_steps, const double* s0,
+hipError_t launch_run_abmpc(const DevCfg* dC, const int32_t* class_of, int N, AbVariant variant, int B, int k_start, int n_steps, const double* s0,
                             const double* v0, const double* a_m1, const double* s_tv, const double* v_tv,
                             double* carry, unsigned long long* codes, double* traj,
                             int32_t* status, int32_t* iters_total, int* work_counter, int* done, int* err_word, int num_cus,
                             hipStream_t stream);
-hipError_t launch_postprocess(const DevCfg* dC, int B, int n_steps, const double* traj, double* rpm, double* Tm,
+hipError_t launch_postprocess(const DevCfg* dC, const int32_t* class_of, int B, int n_steps, const double* traj, double* rpm, double* Tm,
                               double* P, double* E, hipStream_t stream);
 
 }  // namespace eepacc

@@ -1,9 +1,10 @@
 // eepacc_ab_impl.inc -- device code of the ABMPC kernels.  Included by eepacc_kernels.hip once per entry of its
-// EEPACC_AB_VARIANTS list, each time into its own namespace EEPACC_IMPL_NS with the four switches EEPACC_IMPL_MB (move
+// EEPACC_AB_VARIANTS list, each time into its own namespace EEPACC_IMPL_NS with the five switches EEPACC_IMPL_MB (move
 // blocking compiled out / in), EEPACC_IMPL_BL (the baseline controller's row grouping, CreateQP_BL.m: one slack for all
 // soft rows), EEPACC_IMPL_TV (with _BL: the target-vehicle MPC, CreateQP_TV.m: the baseline QP without its
-// vehicle-following rows and without lead inputs) and EEPACC_IMPL_ICE (the ICE-map fuel term, whose Hessian is built and
-// inverted every step), so that the default path carries no register or instruction cost for the variants.
+// vehicle-following rows and without lead inputs), EEPACC_IMPL_ICE (the ICE-map fuel term, whose Hessian is built and
+// inverted every step) and EEPACC_IMPL_CLS (settings classes: every instance has the DevCfg of its class), so that the
+// default path carries no register or instruction cost for the variants.
 // The tables of the active-set method (the inverse He of the effective Hessian, the inverse Schur block P of the working
 // set) are maintained by eepacc_schur.h, which the FBMPC kernels share; it is included once, outside these namespaces.
 namespace eepacc {
@@ -15,6 +16,8 @@ constexpr bool kBaseline = EEPACC_IMPL_BL;
 constexpr bool kIce = EEPACC_IMPL_ICE;      // ICE-map fuel term (CreateQP_AB.m:154-159): the Hessian changes every step
 constexpr bool kTargetVeh = EEPACC_IMPL_TV;     // RunOpt_TVMPC (CreateQP_TV.m): a baseline variant (kBaseline is set too)
 static_assert(!kTargetVeh || kBaseline, "the target-vehicle MPC is a variant of the baseline controller");
+constexpr bool kClasses = EEPACC_IMPL_CLS;  // a handle of eepacc_create_classes: the kernels' Cp is its array DevCfg[n_classes]
+static_assert(!kClasses || !(kMoveBlocking || kBaseline || kIce), "settings classes are built for the plain ABMPC kernels only");
 
 
 #undef PTIC
@@ -1632,20 +1635,52 @@ __device__ WaveMem<MMAX, NS>* wave_mem(unsigned char* smem, int N, double*& He) 
     return reinterpret_cast<WaveMem<MMAX, NS>*>(base);
 }
 
+// The settings of instance b.  The kernels of a handle with settings classes take one more argument than the others, the
+// class map of the launch (class_of, values checked by eepacc_set_classes), and their Cp is the handle's class array.  One
+// wave serves one instance, and the index is made wave-uniform by construction so that every read of the instance's DevCfg
+// stays a scalar load.  N, Tvec and with them the LDS layout are the same in every class (eepacc_create_classes): what is
+// fixed for the launch comes from C0 = Cp[0], the head of the array.  The other variants have no such argument (the pack is empty) and keep their
+// signature: even an argument they never read moves the kernel's hidden arguments and with them its register allocation.
+// In the closed loop a wave serves another instance in every work unit, so the class kernels bind C once more inside the
+// unit's body.  That line is a macro and empty in the other variants: bound through cfg_of there too, the same machine code
+// comes out for k_ab_step but not for k_run_abmpc (the addresses of the DevCfg arrays are then formed in another order,
+// which moves the spills of the N <= 32 kernel), and those kernels are to stay what they were.
+#undef EEPACC_AB_UNIT_CFG
+#ifdef EEPACC_IMPL_CLASS_MAP
+#define EEPACC_AB_UNIT_CFG const DevCfg& C = cfg_of(*Cp, b, class_of...);
+#else
+#define EEPACC_AB_UNIT_CFG
+#endif
+static_assert(kClasses ==
+#ifdef EEPACC_IMPL_CLASS_MAP
+              true,
+#else
+              false,
+#endif
+              "EEPACC_IMPL_CLASS_MAP is defined for the instantiation whose list entry sets EEPACC_IMPL_CLS, and for no other");
+template <class... ClassOf>
+__device__ __forceinline__ const DevCfg& cfg_of(const DevCfg& C0, int b, ClassOf... class_of) {
+    static_assert(sizeof...(ClassOf) == (kClasses ? 1 : 0), "the class map is an argument of the class kernels, and of them alone");
+    if constexpr (kClasses) {
+        const int32_t* map[] = {class_of...};
+        return (&C0)[__builtin_amdgcn_readfirstlane(map[0][b])];
+    } else return C0;
+}
+
 // B2: one step for B instances.  state: per instance 64 x uint64 codes (instance-major).
-template <int MMAX, int NS, int WPB>
+template <int MMAX, int NS, int WPB, class... ClassOf>
 __global__ void __launch_bounds__(64 * WPB, ((NS <= 32 && WPB >= 4) ? 2 : 1))
 k_ab_step(const DevCfg* __restrict__ Cp, int B,
           const double* __restrict__ s, const double* __restrict__ v, const double* __restrict__ a_prev,
           const double* __restrict__ t0, const double* __restrict__ s_tv, const double* __restrict__ v_tv,
           const double* __restrict__ a_tv_prev, unsigned long long* __restrict__ codes,
           double* __restrict__ out, double* __restrict__ s_pred, double* __restrict__ v_pred,
-          int32_t* __restrict__ status, int32_t* __restrict__ iters) {
+          int32_t* __restrict__ status, int32_t* __restrict__ iters, ClassOf... class_of) {
     extern __shared__ __align__(16) unsigned char smem[];
-    const DevCfg& C = *Cp;
     rc_table_init<MMAX>();
     const int b = blockIdx.x * WPB + (threadIdx.x >> 6);
     if (b >= B) return;
+    const DevCfg& C = cfg_of(*Cp, b, class_of...);
     double* Hs;
     WaveMem<MMAX, NS>& M = *wave_mem<MMAX, NS>(smem, C.N, Hs);
     const int lane = lane_id();
@@ -1666,9 +1701,10 @@ k_ab_step(const DevCfg* __restrict__ Cp, int B,
 }
 
 // B1: closed loop over n_steps for B instances (ABO/RunOpt_ABMPC.m:154-340) in work units (run_units, eepacc_units.h).
+// Ts and the LDS layout are fixed for the launch (Cp[0]); the settings are bound per work unit.
 // k_start > 0 resumes from the carried per-instance state (carry [6][B], see Carry; codes: shifted working set).  The
 // small-horizon kernel is compiled for 2 waves per SIMD (1: 512 registers, no scratch; measured slower).
-template <int MMAX, int NS, int WPB>
+template <int MMAX, int NS, int WPB, class... ClassOf>
 __global__ void __launch_bounds__(64 * WPB, ((NS <= 32 && WPB >= 4) ? 2 : 1))
 k_run_abmpc(const DevCfg* __restrict__ Cp, int B, int k_start, int n_steps,
             const double* __restrict__ s0, const double* __restrict__ v0, const double* __restrict__ a_m1,
@@ -1676,9 +1712,9 @@ k_run_abmpc(const DevCfg* __restrict__ Cp, int B, int k_start, int n_steps,
             double* __restrict__ carry, unsigned long long* __restrict__ codes,
             double* __restrict__ traj, int32_t* __restrict__ status, int32_t* __restrict__ iters_total,
             int* __restrict__ work_counter, int* __restrict__ done, int kChunkSteps,
-            int* __restrict__ err_word, int spin_limit) {
+            int* __restrict__ err_word, int spin_limit, ClassOf... class_of) {
     extern __shared__ __align__(16) unsigned char smem[];
-    const DevCfg& C = *Cp;
+    const DevCfg& C = *Cp;                               // with classes: class 0, for what is fixed for the launch
     rc_table_init<MMAX>();
     double* Hs;
     WaveMem<MMAX, NS>& M = *wave_mem<MMAX, NS>(smem, C.N, Hs);
@@ -1688,6 +1724,7 @@ k_run_abmpc(const DevCfg* __restrict__ Cp, int B, int k_start, int n_steps,
     if (B == 1) g_trace_on = 1;
 #endif
     run_units(B, n_steps, kChunkSteps, work_counter, done, err_word, spin_limit, status, iters_total, [&](int b, int kk0, int kk1) {
+        EEPACC_AB_UNIT_CFG
         unsigned long long code = 0ull;
         Carry cs;
         if (k_start + kk0 > 0) {
@@ -1720,6 +1757,16 @@ k_run_abmpc(const DevCfg* __restrict__ Cp, int B, int k_start, int n_steps,
         if (lane == 0) cs.store(carry, B, b);
         return it_total;
     });
+}
+
+// the kernels of this instantiation as the host launches them: with the class map where the variant has one
+template <int MMAX, int NS, int WPB> constexpr auto step_kernel() {
+    if constexpr (kClasses) return &k_ab_step<MMAX, NS, WPB, const int32_t*>;
+    else return &k_ab_step<MMAX, NS, WPB>;
+}
+template <int MMAX, int NS, int WPB> constexpr auto run_kernel() {
+    if constexpr (kClasses) return &k_run_abmpc<MMAX, NS, WPB, const int32_t*>;
+    else return &k_run_abmpc<MMAX, NS, WPB>;
 }
 
 }  // namespace EEPACC_IMPL_NS

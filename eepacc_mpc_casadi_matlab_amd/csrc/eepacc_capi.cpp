@@ -75,6 +75,13 @@ struct eepacc_handle {
     // structured FBMPC path (eepacc_fbs.hip): per-instance state, closed-loop carry, base-inverse scratch
     bool fbs = false;                        // settings are covered by the structured solver
     DevMem<double> fbs_state, fbs_carry, fbs_hb;
+    // Settings classes (eepacc_create_classes): d_cfg holds DevCfg[n_classes], d_Hinv one N x N block per class and cfg is
+    // class 0, whose N and Tvec every class shares.  n_classes = 0 marks a handle of eepacc_create.
+    int n_classes = 0;
+    DevMem<int32_t> d_class_of;              // [max_batch] class of every instance
+    int classes_B = 0;                       // B of the last eepacc_set_classes (0: none yet)
+    eepacc::AbVariant variant() const { return n_classes ? eepacc::AbVariant::Classes : eepacc::ab_variant(cfg); }
+    const int32_t* class_map() const { return n_classes ? d_class_of.p : nullptr; }
 };
 
 extern "C" const char* eepacc_last_error(void) { return g_err.c_str(); }
@@ -275,14 +282,11 @@ static int build_cfg(const eepacc_settings* S, const eepacc_vehicle* V, DevCfg& 
     return EEPACC_OK;
 }
 
-extern "C" int eepacc_create(eepacc_handle** out, const eepacc_settings* S, const eepacc_vehicle* V,
-                             int device, int max_batch) {
-    if (!out || !S || !V || max_batch < 1) return fail(EEPACC_EINVAL, "eepacc_create: bad arguments");
-    *out = nullptr;
-    DevCfg C;
-    std::vector<double> Hinv;
-    int rc = build_cfg(S, V, C, Hinv);
-    if (rc != EEPACC_OK) return rc;
+// The device side of a handle.  Cs: one validated DevCfg per class with its inverse Hessian in Hinv (N x N each, class after
+// class); classes: the handle of eepacc_create_classes, which keeps a class map and runs AbVariant::Classes, also with one class.
+static int create_on_device(eepacc_handle** out, std::vector<DevCfg>& Cs, const std::vector<double>& Hinv, bool classes,
+                            int device, int max_batch) {
+    DevCfg& C = Cs[0];
     int ndev = 0;
     HIPCHK(hipGetDeviceCount(&ndev));
     if (ndev < 1) return fail(EEPACC_EDEVICE, "no HIP device: libeepacc has no CPU path");
@@ -294,9 +298,11 @@ extern "C" int eepacc_create(eepacc_handle** out, const eepacc_settings* S, cons
     const size_t nB = (size_t)max_batch;
     HIPCHK(h->d_Hinv.alloc(Hinv.size()));
     HIPCHK(hipMemcpy(h->d_Hinv, Hinv.data(), Hinv.size() * sizeof(double), hipMemcpyHostToDevice));
-    C.Hinv = h->d_Hinv;
     HIPCHK(h->d_pred.alloc_zero(nB * 128));
-    C.pred = h->d_pred;
+    for (size_t k = 0; k < Cs.size(); ++k) {                // pred is indexed by instance: one buffer for all classes
+        Cs[k].Hinv = h->d_Hinv + k * (size_t)C.N * C.N;
+        Cs[k].pred = h->d_pred;
+    }
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
     h->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
@@ -305,8 +311,12 @@ extern "C" int eepacc_create(eepacc_handle** out, const eepacc_settings* S, cons
         C.hb = h->d_hb;
     }
     h->cfg = C;
-    HIPCHK(h->d_cfg.alloc(1));
-    HIPCHK(hipMemcpy(h->d_cfg, &C, sizeof(DevCfg), hipMemcpyHostToDevice));
+    HIPCHK(h->d_cfg.alloc(Cs.size()));
+    HIPCHK(hipMemcpy(h->d_cfg, Cs.data(), Cs.size() * sizeof(DevCfg), hipMemcpyHostToDevice));
+    if (classes) {
+        h->n_classes = (int)Cs.size();
+        HIPCHK(h->d_class_of.alloc_zero(nB));
+    }
     HIPCHK(h->d_codes.alloc_zero(nB * 64));
     HIPCHK(h->d_iters.alloc_zero(nB));
     HIPCHK(h->d_carry.alloc_zero(nB * 6));
@@ -316,7 +326,7 @@ extern "C" int eepacc_create(eepacc_handle** out, const eepacc_settings* S, cons
     HIPCHK(h->d_qp_counter.alloc(1));
     HIPCHK(eepacc::set_max_smem());
     // FBMPC: structured kernels unless the settings need the dense path (or EEPACC_FB_DENSE=1 asks for it)
-    h->fbs = eepacc::fbs_supported(C) && eepacc::fbs_smem_bytes(C.N) <= 160 * 1024 - 4608;
+    h->fbs = !classes && eepacc::fbs_supported(C) && eepacc::fbs_smem_bytes(C.N) <= 160 * 1024 - 4608;
     if (const char* e = getenv("EEPACC_FB_DENSE")) if (atoi(e) != 0) h->fbs = false;
     if (h->fbs) {
         HIPCHK(eepacc::fbs_set_max_smem());
@@ -327,6 +337,50 @@ extern "C" int eepacc_create(eepacc_handle** out, const eepacc_settings* S, cons
     *out = h.release();
     return EEPACC_OK;
 }
+
+extern "C" int eepacc_create(eepacc_handle** out, const eepacc_settings* S, const eepacc_vehicle* V,
+                             int device, int max_batch) {
+    if (!out || !S || !V || max_batch < 1) return fail(EEPACC_EINVAL, "eepacc_create: bad arguments");
+    *out = nullptr;
+    std::vector<DevCfg> Cs(1);
+    std::vector<double> Hinv;
+    int rc = build_cfg(S, V, Cs[0], Hinv);
+    if (rc != EEPACC_OK) return rc;
+    return create_on_device(out, Cs, Hinv, false, device, max_batch);
+}
+
+// Every class is checked like the settings of eepacc_create, and against class 0 in what selects the kernel and the launch
+// geometry, before the device is touched.
+extern "C" int eepacc_create_classes(eepacc_handle** out, const eepacc_settings* S, const eepacc_vehicle* V,
+                                     int n_classes, int device, int max_batch) {
+    if (!out || !S || !V || max_batch < 1) return fail(EEPACC_EINVAL, "eepacc_create_classes: bad arguments");
+    *out = nullptr;
+    if (n_classes < 1 || n_classes > EEPACC_MAX_CLASSES)
+        return fail(EEPACC_EINVAL, "eepacc_create_classes: n_classes must be in [1, " + std::to_string(EEPACC_MAX_CLASSES) + "]");
+    const int N = S[0].N_hor;
+    if (N < 2 || N > eepacc::kMaxN) return fail(EEPACC_EINVAL, "eepacc_create_classes: class 0: N_hor must be in [2, 63]");
+    std::vector<DevCfg> Cs((size_t)n_classes);
+    std::vector<double> Hinv, Hk;
+    for (int k = 0; k < n_classes; ++k) {
+        const std::string who = "eepacc_create_classes: class " + std::to_string(k) + ": ";
+        if (S[k].N_hor != N)
+            return fail(EEPACC_EINVAL, who + "N_hor = " + std::to_string(S[k].N_hor) + " differs from class 0 (" + std::to_string(N) + "); the classes of a handle share the horizon");
+        if (S[k].bl_mode != 0) return fail(EEPACC_ENOTSUP, who + "bl_mode != 0: the baseline and target-vehicle controllers have no class variant");
+        if (S[k].ab_fuel_term == 2) return fail(EEPACC_ENOTSUP, who + "ab_fuel_term == 2: the ICE-map fuel term has no class variant");
+        if (S[k].Mb)
+            for (int j = 0; j < N; ++j)
+                if (S[k].Mb[j] != 0) return fail(EEPACC_ENOTSUP, who + "Mb[" + std::to_string(j) + "] != 0: move blocking has no class variant");
+        const int rc = build_cfg(&S[k], &V[k], Cs[(size_t)k], Hk);
+        if (rc != EEPACC_OK) return fail(rc, who + g_err);
+        for (int j = 0; j < N; ++j)
+            if (Cs[(size_t)k].Tvec[j] != Cs[0].Tvec[j])
+                return fail(EEPACC_EINVAL, who + "Tvec[" + std::to_string(j) + "] differs from class 0; the classes of a handle share the time grid");
+        Hinv.insert(Hinv.end(), Hk.begin(), Hk.end());
+    }
+    return create_on_device(out, Cs, Hinv, true, device, max_batch);
+}
+
+extern "C" int eepacc_num_classes(const eepacc_handle* h) { return h && h->n_classes ? h->n_classes : 1; }
 
 extern "C" void eepacc_destroy(eepacc_handle* h) {
     if (!h) return;
@@ -351,6 +405,34 @@ extern "C" int eepacc_reset(eepacc_handle* h) {
     return EEPACC_OK;
 }
 
+extern "C" int eepacc_set_classes(eepacc_handle* h, int B, const int32_t* class_of_host) {
+    if (!h) return fail(EEPACC_EINVAL, "NULL handle");
+    if (!h->n_classes) return fail(EEPACC_EINVAL, "eepacc_set_classes: this handle was not created by eepacc_create_classes");
+    if (B < 1 || B > h->max_batch || !class_of_host) return fail(EEPACC_EINVAL, "eepacc_set_classes: B must be in [1, max_batch] and the map not NULL");
+    for (int i = 0; i < B; ++i)
+        if (class_of_host[i] < 0 || class_of_host[i] >= h->n_classes)
+            return fail(EEPACC_EINVAL, "eepacc_set_classes: class_of[" + std::to_string(i) + "] = " + std::to_string(class_of_host[i]) +
+                                       " is outside [0, " + std::to_string(h->n_classes) + ")");
+    HIPCHK(hipSetDevice(h->device));
+    // a launch in flight may still read the map, and the copy below does not wait for work on other streams
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(h->d_class_of, class_of_host, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice));
+    h->classes_B = B;
+    return eepacc_reset(h);
+}
+
+// A handle of eepacc_create_classes runs the ABMPC entry points only, and only with the B its class map was set for.
+static int not_classes(const eepacc_handle* h, const char* who) {
+    if (h && h->n_classes)
+        return fail(EEPACC_ENOTSUP, std::string(who) + ": a handle of eepacc_create_classes runs ABMPC only (eepacc_ab_step, eepacc_run_abmpc, eepacc_run_abmpc_host)");
+    return EEPACC_OK;
+}
+static int classes_ready(const eepacc_handle* h, const char* who, int B) {
+    if (!h->n_classes || B == h->classes_B) return EEPACC_OK;
+    if (!h->classes_B) return fail(EEPACC_EINVAL, std::string(who) + ": eepacc_set_classes has not been called on this handle");
+    return fail(EEPACC_EINVAL, std::string(who) + ": B = " + std::to_string(B) + " differs from the B = " + std::to_string(h->classes_B) + " of the last eepacc_set_classes");
+}
+
 // The kind of a handle decides which entry points run it.  One created with bl_mode = 2 poses RunOpt_TVMPC's problem and takes
 // no lead inputs: only eepacc_tv_step / eepacc_run_tvmpc* run it (need_tv), every other one refuses it (not_tv).  The
 // eepacc_bl_* names are the ABMPC entry points for a handle that was created as the baseline controller (need_bl).
@@ -366,8 +448,8 @@ static int need_mode(const eepacc_handle* h, int bl_mode, const char* name) {
         return fail(EEPACC_EINVAL, "this handle was not created with bl_mode = " + std::to_string(bl_mode) + " (" + name + ")");
     return EEPACC_OK;
 }
-static int need_bl(const eepacc_handle* h) { return need_mode(h, 1, "RunOpt_BLMPC"); }
-static int need_tv(const eepacc_handle* h) { return need_mode(h, 2, "RunOpt_TVMPC"); }
+static int need_bl(const eepacc_handle* h) { const int rc = not_classes(h, "eepacc_bl_step / eepacc_run_blmpc"); return rc ? rc : need_mode(h, 1, "RunOpt_BLMPC"); }
+static int need_tv(const eepacc_handle* h) { const int rc = not_classes(h, "eepacc_tv_step / eepacc_run_tvmpc"); return rc ? rc : need_mode(h, 2, "RunOpt_TVMPC"); }
 
 // One step of the ABMPC kernels of the handle's variant.  A target-vehicle handle has no lead inputs: its kernels read none
 // and the launcher gets null pointers.
@@ -379,9 +461,10 @@ static int ab_step_impl(eepacc_handle* h, const char* who, int B, const double* 
     if (B == 0) return EEPACC_OK;
     if (!s || !v || !a_prev || !t0 || (!tv && (!s_tv || !v_tv || !a_tv_prev)) || !out || !status)
         return fail(EEPACC_EINVAL, std::string(who) + ": NULL buffer");
+    if (const int rc = classes_ready(h, who, B)) return rc;
     HIPCHK(hipSetDevice(h->device));
     h->last_B = B;
-    HIPCHK(eepacc::launch_ab_step(h->d_cfg, h->cfg.N, eepacc::ab_variant(h->cfg), B, s, v, a_prev, t0, tv ? nullptr : s_tv,
+    HIPCHK(eepacc::launch_ab_step(h->d_cfg, h->class_map(), h->cfg.N, h->variant(), B, s, v, a_prev, t0, tv ? nullptr : s_tv,
                                   tv ? nullptr : v_tv, tv ? nullptr : a_tv_prev, h->d_codes, out, s_pred, v_pred, status,
                                   h->d_iters, (hipStream_t)stream));
     return EEPACC_OK;
@@ -396,11 +479,12 @@ static int ab_run_impl(eepacc_handle* h, const char* who, const char* bad_sizes,
     if (B == 0 || n_steps == 0) return EEPACC_OK;
     if (!s0 || !v0 || !a_minus1 || (!tv && (!s_tv || !v_tv)) || !traj || !status)
         return fail(EEPACC_EINVAL, std::string(who) + ": NULL buffer");
+    if (const int rc = classes_ready(h, who, B)) return rc;
     HIPCHK(hipSetDevice(h->device));
     if (h->k_done > 0 && h->carry_B != B)
         return fail(EEPACC_EINVAL, std::string(who) + ": B changed while resuming; call eepacc_reset first");
     h->last_B = B;
-    HIPCHK(eepacc::launch_run_abmpc(h->d_cfg, h->cfg.N, eepacc::ab_variant(h->cfg), B, h->k_done, n_steps, s0, v0, a_minus1,
+    HIPCHK(eepacc::launch_run_abmpc(h->d_cfg, h->class_map(), h->cfg.N, h->variant(), B, h->k_done, n_steps, s0, v0, a_minus1,
                                     tv ? nullptr : s_tv, tv ? nullptr : v_tv, h->d_carry, h->d_codes, traj, status, h->d_iters,
                                     h->d_counter, h->d_done, h->d_err, h->num_cus, (hipStream_t)stream));
     h->k_done += n_steps; h->carry_B = B;
@@ -448,8 +532,9 @@ extern "C" int eepacc_postprocess(eepacc_handle* h, int B, int n_steps, const do
                                   double* Tm, double* P, double* E, void* stream) {
     if (!h || !traj || !rpm || !Tm || !P || !E) return fail(EEPACC_EINVAL, "eepacc_postprocess: NULL argument");
     if (B < 1 || n_steps < 1) return EEPACC_OK;
+    if (const int rc = classes_ready(h, "eepacc_postprocess", B)) return rc;
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(eepacc::launch_postprocess(h->d_cfg, B, n_steps, traj, rpm, Tm, P, E, (hipStream_t)stream));
+    HIPCHK(eepacc::launch_postprocess(h->d_cfg, h->class_map(), B, n_steps, traj, rpm, Tm, P, E, (hipStream_t)stream));
     return EEPACC_OK;
 }
 
@@ -503,6 +588,7 @@ extern "C" int eepacc_qp_solve_batched(eepacc_handle* h, int B, int nV, int nC, 
                                        const double* ubx, const double* x0, double* x, double* cost,
                                        int32_t* status, void* stream) {
     if (!h) return fail(EEPACC_EINVAL, "NULL handle");
+    if (const int rc = not_classes(h, "eepacc_qp_solve_batched")) return rc;
     if (B < 0 || nV < 1 || nC < 0) return fail(EEPACC_EINVAL, "eepacc_qp_solve_batched: bad sizes");
     if (B == 0) return EEPACC_OK;
     if (nV > EEPACC_QP_MAX_NV || nC > EEPACC_QP_MAX_NC)
@@ -608,6 +694,7 @@ extern "C" int eepacc_fb_step(eepacc_handle* h, int B, const double* s, const do
                               double* out, double* s_pred, double* v_pred, int32_t* status, void* stream) {
     (void)v_prev; (void)Fm_prev; (void)Fb_prev;   // accepted and unused, as in CreateQP_FB.m:1 (inputs v_minus1, Fm_minus1, Fb_minus1)
     if (const int rc = not_tv(h, "eepacc_fb_step")) return rc;
+    if (const int rc = not_classes(h, "eepacc_fb_step")) return rc;
     if (B < 0 || B > h->max_batch) return fail(EEPACC_EINVAL, "B exceeds max_batch of the handle");
     if (B == 0) return EEPACC_OK;
     if (!s || !v || !a_prev || !t0 || !s_tv || !v_tv || !a_tv_prev || !out || !status)
@@ -633,6 +720,7 @@ extern "C" int eepacc_run_fbmpc(eepacc_handle* h, int B, int n_steps, const doub
                                 const double* a_minus1, const double* s_tv, const double* v_tv,
                                 double* traj, int32_t* status, void* stream) {
     if (const int rc = not_tv(h, "eepacc_run_fbmpc")) return rc;
+    if (const int rc = not_classes(h, "eepacc_run_fbmpc")) return rc;
     if (B < 0 || B > h->max_batch || n_steps < 0) return fail(EEPACC_EINVAL, "eepacc_run_fbmpc: bad B / n_steps");
     if (B == 0 || n_steps == 0) return EEPACC_OK;
     if (!s0 || !v0 || !a_minus1 || !s_tv || !v_tv || !traj || !status)
@@ -677,6 +765,8 @@ static int run_host(eepacc_handle* h, Ctl ctl, int B, int n_steps, const double*
     const bool lead = ctl != Ctl::TV;
     if (B < 1 || B > h->max_batch || n_steps < 1) return fail(EEPACC_EINVAL, "bad B / n_steps");
     if (!s0 || !v0 || !a_minus1 || (lead && (!s_tv || !v_tv)) || !traj || !status) return fail(EEPACC_EINVAL, "NULL buffer");
+    if (ctl == Ctl::FB) { if (const int rc = not_classes(h, "eepacc_run_fbmpc_host")) return rc; }
+    if (const int rc = classes_ready(h, "eepacc_run_abmpc_host", B)) return rc;
     HIPCHK(hipSetDevice(h->device));
     DevMem<double> d_in, d_tv, d_traj;
     DevMem<int32_t> d_status;

@@ -21,7 +21,7 @@
 #include "../../include/eepacc.h"
 
 // The variants of eepacc_ab_impl.inc, each compiled into its own namespace so that the default path carries no register or
-// instruction cost for the others: X(AbVariant, namespace, EEPACC_IMPL_MB, _BL, _TV, _ICE, ...).  A new variant is a line here,
+// instruction cost for the others: X(AbVariant, namespace, EEPACC_IMPL_MB, _BL, _TV, _ICE, _CLS, ...).  A new variant is a line here,
 // its AbVariant (eepacc_ab.h) and its #include below.
 //   blc    baseline controller (RunOpt_BLMPC): the same kernels with CreateQP_BL's row grouping
 //   tvc    target-vehicle MPC (RunOpt_TVMPC): the baseline variant with CreateQP_TV's row catalogue (no vehicle-following
@@ -29,23 +29,27 @@
 //   ice*   ICE-map fuel term (CreateQP_AB.m:154-159): step-varying Hessian, built and inverted in LDS every step; icemb
 //          folds the Hessian into E'HE before the inversion.  Two namespaces: compiled into one, the blocking code costs
 //          the small ICE kernel 18 % of its throughput at N = 30 even where the handle has no Mb.
-#define EEPACC_AB_VARIANTS(X, ...)                                       \
-    X(Plain, nomb, false, false, false, false, __VA_ARGS__)              \
-    X(MoveBlocking, withmb, true, false, false, false, __VA_ARGS__)      \
-    X(Baseline, blc, false, true, false, false, __VA_ARGS__)             \
-    X(Ice, ice, false, false, false, true, __VA_ARGS__)                  \
-    X(IceMoveBlocking, icemb, true, false, false, true, __VA_ARGS__)     \
-    X(TargetVehicle, tvc, false, true, true, false, __VA_ARGS__)
+//   cls    settings classes (eepacc_create_classes): the plain kernels with the DevCfg bound per instance, through the
+//          class map that its kernels alone take as one more argument
+#define EEPACC_AB_VARIANTS(X, ...)                                              \
+    X(Plain, nomb, false, false, false, false, false, __VA_ARGS__)              \
+    X(MoveBlocking, withmb, true, false, false, false, false, __VA_ARGS__)      \
+    X(Baseline, blc, false, true, false, false, false, __VA_ARGS__)             \
+    X(Ice, ice, false, false, false, true, false, __VA_ARGS__)                  \
+    X(IceMoveBlocking, icemb, true, false, false, true, false, __VA_ARGS__)     \
+    X(TargetVehicle, tvc, false, true, true, false, false, __VA_ARGS__)         \
+    X(Classes, cls, false, false, false, false, true, __VA_ARGS__)
 
 // an instantiation reads its switches from the list by the name of its namespace
 namespace eepacc { namespace ab_switch {
-#define EEPACC_AB_SWITCHES(E, NSP, MB_, BL_, TV_, ICE_, ...) struct NSP { static constexpr bool MB = MB_, BL = BL_, TV = TV_, ICE = ICE_; };
+#define EEPACC_AB_SWITCHES(E, NSP, MB_, BL_, TV_, ICE_, CLS_, ...) struct NSP { static constexpr bool MB = MB_, BL = BL_, TV = TV_, ICE = ICE_, CLS = CLS_; };
 EEPACC_AB_VARIANTS(EEPACC_AB_SWITCHES)
 } }
 #define EEPACC_IMPL_MB ab_switch::EEPACC_IMPL_NS::MB
 #define EEPACC_IMPL_BL ab_switch::EEPACC_IMPL_NS::BL
 #define EEPACC_IMPL_TV ab_switch::EEPACC_IMPL_NS::TV
 #define EEPACC_IMPL_ICE ab_switch::EEPACC_IMPL_NS::ICE
+#define EEPACC_IMPL_CLS ab_switch::EEPACC_IMPL_NS::CLS
 #define EEPACC_IMPL_NS nomb
 #include "eepacc_ab_impl.inc"
 #undef EEPACC_IMPL_NS
@@ -63,6 +67,11 @@ EEPACC_AB_VARIANTS(EEPACC_AB_SWITCHES)
 #undef EEPACC_IMPL_NS
 #define EEPACC_IMPL_NS tvc
 #include "eepacc_ab_impl.inc"
+#undef EEPACC_IMPL_NS
+#define EEPACC_IMPL_NS cls
+#define EEPACC_IMPL_CLASS_MAP       // the preprocessor's copy of the list's CLS switch (eepacc_ab_impl.inc checks that they agree)
+#include "eepacc_ab_impl.inc"
+#undef EEPACC_IMPL_CLASS_MAP
 #undef EEPACC_IMPL_NS
 
 // ----------------------------------------------------------------------------------------------
@@ -94,9 +103,15 @@ size_t ab_smem_bytes(int N) {
                          : nomb::wave_bytes(sizeof(nomb::WaveMem<kMMaxLarge, kNSLarge>), kNSLarge) * kWpbLarge;
 }
 
-// the kernel of the handle's variant, small or large horizon
-#define EEPACC_LAUNCH_CASE(E, NSP, MB, BL, TV, ICE, KERNEL, MM, NSV, WPB, GRID, ...)                          \
-    case AbVariant::E: hipLaunchKernelGGL(HIP_KERNEL_NAME(NSP::KERNEL<MM, NSV, WPB>), dim3(GRID), dim3(64 * WPB), ab_smem_bytes(N), stream, __VA_ARGS__); break;
+// the kernel of the handle's variant, small or large horizon; a kernel with one parameter more than the launch has
+// arguments is a class kernel (eepacc_ab_impl.inc, cfg_of) and gets the class map as its last
+template <class... P, class... A>
+static void launch_ab(void (*kernel)(P...), int grid, int block, size_t smem, hipStream_t stream, const int32_t* class_of, A... args) {
+    if constexpr (sizeof...(P) == sizeof...(A) + 1) hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), smem, stream, args..., class_of);
+    else hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), smem, stream, args...);
+}
+#define EEPACC_LAUNCH_CASE(E, NSP, MB, BL, TV, ICE, CLS, KERNEL, MM, NSV, WPB, GRID, ...)                          \
+    case AbVariant::E: launch_ab(NSP::KERNEL<MM, NSV, WPB>(), GRID, 64 * WPB, ab_smem_bytes(N), stream, class_of, __VA_ARGS__); break;
 #define EEPACC_LAUNCH(KERNEL, MM, NSV, WPB, GRID, ...)                                                        \
     do { switch (variant) { EEPACC_AB_VARIANTS(EEPACC_LAUNCH_CASE, KERNEL, MM, NSV, WPB, GRID, __VA_ARGS__) } } while (0)
 
@@ -124,17 +139,17 @@ size_t ab_hb_doubles(int N, int B, int num_cus) {
     return (step_waves > run_waves ? step_waves : run_waves) * ns * ns;
 }
 
-hipError_t launch_ab_step(const DevCfg* dC, int N, AbVariant variant, int B, const double* s, const double* v, const double* a_prev,
-                          const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
+hipError_t launch_ab_step(const DevCfg* dC, const int32_t* class_of, int N, AbVariant variant, int B, const double* s, const double* v,
+                          const double* a_prev, const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
                           unsigned long long* codes, double* out, double* s_pred, double* v_pred,
                           int32_t* status, int32_t* iters, hipStream_t stream) {
-    if (N > kNSSmall) EEPACC_LAUNCH(k_ab_step, kMMaxLarge, kNSLarge, kWpbLarge, (B + kWpbLarge - 1) / kWpbLarge, dC, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, codes, out, s_pred, v_pred, status, iters);
-    else EEPACC_LAUNCH(k_ab_step, kMMaxSmall, kNSSmall, 4, (B + 3) / 4, dC, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, codes, out, s_pred, v_pred, status, iters);
+    if (N > kNSSmall) EEPACC_LAUNCH(step_kernel, kMMaxLarge, kNSLarge, kWpbLarge, (B + kWpbLarge - 1) / kWpbLarge, dC, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, codes, out, s_pred, v_pred, status, iters);
+    else EEPACC_LAUNCH(step_kernel, kMMaxSmall, kNSSmall, 4, (B + 3) / 4, dC, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, codes, out, s_pred, v_pred, status, iters);
     return hipGetLastError();
 }
 
-hipError_t launch_run_abmpc(const DevCfg* dC, int N, AbVariant variant, int B, int k_start, int n_steps, const double* s0,
-                            const double* v0, const double* a_m1, const double* s_tv, const double* v_tv,
+hipError_t launch_run_abmpc(const DevCfg* dC, const int32_t* class_of, int N, AbVariant variant, int B, int k_start, int n_steps,
+                            const double* s0, const double* v0, const double* a_m1, const double* s_tv, const double* v_tv,
                             double* carry, unsigned long long* codes, double* traj,
                             int32_t* status, int32_t* iters_total, int* work_counter, int* done, int* err_word, int num_cus,
                             hipStream_t stream) {
@@ -146,19 +161,21 @@ hipError_t launch_run_abmpc(const DevCfg* dC, int N, AbVariant variant, int B, i
                                num_cus * (large ? 1 : kBlocksSmall), stream, ul);
     if (e != hipSuccess) return e;
     if (large)
-        EEPACC_LAUNCH(k_run_abmpc, kMMaxLarge, kNSLarge, kWpbLarge, ul.grid, dC, B, k_start, n_steps, s0, v0, a_m1, s_tv, v_tv, carry, codes, traj, status, iters_total, work_counter, done, kChunkSteps, err_word, ul.spin_limit);
+        EEPACC_LAUNCH(run_kernel, kMMaxLarge, kNSLarge, kWpbLarge, ul.grid, dC, B, k_start, n_steps, s0, v0, a_m1, s_tv, v_tv, carry, codes, traj, status, iters_total, work_counter, done, kChunkSteps, err_word, ul.spin_limit);
     else
-        EEPACC_LAUNCH(k_run_abmpc, kMMaxSmall, kNSSmall, 4, ul.grid, dC, B, k_start, n_steps, s0, v0, a_m1, s_tv, v_tv, carry, codes, traj, status, iters_total, work_counter, done, kChunkSteps, err_word, ul.spin_limit);
+        EEPACC_LAUNCH(run_kernel, kMMaxSmall, kNSSmall, 4, ul.grid, dC, B, k_start, n_steps, s0, v0, a_m1, s_tv, v_tv, carry, codes, traj, status, iters_total, work_counter, done, kChunkSteps, err_word, ul.spin_limit);
     return hipGetLastError();
 }
 
-// A10: post-processing (ABO/RunOpt_ABMPC.m:343-349), one thread per instance, sequential in time
+// A10: post-processing (ABO/RunOpt_ABMPC.m:343-349), one thread per instance, sequential in time.  kClasses: Cp is the
+// class array of the handle and every instance reads the vehicle and the power fit of its own class.
+template <bool kClasses>
 __global__ void k_postprocess(const DevCfg* __restrict__ Cp, int B, int n_steps, const double* __restrict__ traj,
                               double* __restrict__ rpm, double* __restrict__ Tm, double* __restrict__ P,
-                              double* __restrict__ E) {
-    const DevCfg& C = *Cp;
+                              double* __restrict__ E, const int32_t* __restrict__ class_of) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
+    const DevCfg& C = kClasses ? Cp[class_of[b]] : *Cp;
     const double Ts = C.Tvec[0];
     double acc = 0.0;
     const double kr = (30.0 / 3.14159265358979323846);
@@ -181,9 +198,10 @@ __global__ void k_postprocess(const DevCfg* __restrict__ Cp, int B, int n_steps,
     }
 }
 
-hipError_t launch_postprocess(const DevCfg* dC, int B, int n_steps, const double* traj, double* rpm, double* Tm,
-                              double* P, double* E, hipStream_t stream) {
-    hipLaunchKernelGGL(k_postprocess, dim3((B + 127) / 128), dim3(128), 0, stream, dC, B, n_steps, traj, rpm, Tm, P, E);
+hipError_t launch_postprocess(const DevCfg* dC, const int32_t* class_of, int B, int n_steps, const double* traj, double* rpm,
+                              double* Tm, double* P, double* E, hipStream_t stream) {
+    if (class_of) hipLaunchKernelGGL(k_postprocess<true>, dim3((B + 127) / 128), dim3(128), 0, stream, dC, B, n_steps, traj, rpm, Tm, P, E, class_of);
+    else hipLaunchKernelGGL(k_postprocess<false>, dim3((B + 127) / 128), dim3(128), 0, stream, dC, B, n_steps, traj, rpm, Tm, P, E, class_of);
     return hipGetLastError();
 }
 
@@ -193,8 +211,8 @@ static hipError_t raise_smem(hipError_t e, K* kernel) {
     const int dyn = 160 * 1024 - ((MM * (MM + 1) / 2 * 2 + 255) & ~255);
     return e != hipSuccess ? e : hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, dyn);
 }
-#define EEPACC_RAISE_SMEM(E, NSP, MB, BL, TV, ICE, MM, NSV, WPB) \
-    e = raise_smem<MM>(e, &NSP::k_ab_step<MM, NSV, WPB>); e = raise_smem<MM>(e, &NSP::k_run_abmpc<MM, NSV, WPB>);
+#define EEPACC_RAISE_SMEM(E, NSP, MB, BL, TV, ICE, CLS, MM, NSV, WPB) \
+    e = raise_smem<MM>(e, NSP::step_kernel<MM, NSV, WPB>()); e = raise_smem<MM>(e, NSP::run_kernel<MM, NSV, WPB>());
 hipError_t set_max_smem() {
     hipError_t e = hipSuccess;
     EEPACC_AB_VARIANTS(EEPACC_RAISE_SMEM, kMMaxSmall, kNSSmall, 4)

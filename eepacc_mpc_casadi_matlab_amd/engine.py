@@ -13,7 +13,8 @@ from typing import Any, Dict, Optional
 
 import numpy as np
 
-from ._abi import SettingsHolder, SettingsPOD, Vehicle, make_vehicle, OUT, OUT_N, OUT_FIELDS, c_double_p, as_dptr
+from ._abi import (SettingsHolder, SettingsPOD, Vehicle, make_vehicle, pack_classes, OUT, OUT_N, OUT_FIELDS, c_double_p,
+                   as_dptr, as_iptr)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIBPATH = os.path.join(_HERE, "libeepacc.so")
@@ -45,6 +46,9 @@ def load_library() -> C.CDLL:
     if lib.eepacc_sizeof_settings() != C.sizeof(SettingsPOD) or lib.eepacc_sizeof_vehicle() != C.sizeof(Vehicle):
         raise EepaccError("ctypes mirror of include/eepacc.h is out of date (struct size mismatch)")
     lib.eepacc_create.argtypes = [C.POINTER(vp), C.POINTER(SettingsPOD), C.POINTER(Vehicle), C.c_int, C.c_int]
+    lib.eepacc_create_classes.argtypes = [C.POINTER(vp), C.POINTER(SettingsPOD), C.POINTER(Vehicle), C.c_int, C.c_int, C.c_int]
+    lib.eepacc_set_classes.argtypes = [vp, C.c_int, ip]
+    lib.eepacc_num_classes.argtypes = [vp]
     lib.eepacc_destroy.argtypes = [vp]
     lib.eepacc_destroy.restype = None
     lib.eepacc_reset.argtypes = [vp]
@@ -70,6 +74,7 @@ def load_library() -> C.CDLL:
 
 
 ABI_SYMBOLS = ["eepacc_last_error", "eepacc_version", "eepacc_sizeof_settings", "eepacc_sizeof_vehicle", "eepacc_create", "eepacc_destroy", "eepacc_reset",
+               "eepacc_create_classes", "eepacc_set_classes", "eepacc_num_classes",
                "eepacc_ab_step", "eepacc_run_abmpc", "eepacc_fb_step", "eepacc_run_fbmpc",
                "eepacc_run_abmpc_host", "eepacc_run_fbmpc_host", "eepacc_bl_step", "eepacc_run_blmpc", "eepacc_run_blmpc_host",
                "eepacc_tv_step", "eepacc_run_tvmpc", "eepacc_run_tvmpc_host", "eepacc_postprocess",
@@ -99,6 +104,40 @@ class Engine:
         h = C.c_void_p()
         _check(self.lib.eepacc_create(C.byref(h), C.byref(self.holder.pod), C.byref(self.veh), device, max_batch))
         self.h = h
+
+    @classmethod
+    def from_classes(cls, OPT_list, V_list, device: int = 0, max_batch: int = 4096) -> "Engine":
+        """eepacc_create_classes: one engine for instances of several settings classes (ABMPC only).  OPT_list[k], V_list[k]
+        are the settings and the vehicle of class k; N_hor and Tvec must agree.  set_classes() says which class every
+        instance of the next launches belongs to; ab_step, run_abmpc, run_abmpc_host and postprocess then work as on an
+        ordinary engine, every other controller is refused."""
+        import torch
+        if not torch.cuda.is_available():
+            raise EepaccError("no GPU visible: the EEPACC engine has no CPU path")
+        if len(OPT_list) != len(V_list) or len(OPT_list) < 1:
+            raise ValueError("from_classes needs one vehicle per settings class and at least one class")
+        self = cls.__new__(cls)
+        self.torch = torch
+        self.lib = load_library()
+        self.OPT = OPT_list[0]
+        self.holder, S, self.veh = pack_classes(OPT_list, V_list)
+        self.N = int(OPT_list[0]["N_hor"])
+        self.device = torch.device("cuda", device)
+        self.max_batch = int(max_batch)
+        h = C.c_void_p()
+        _check(self.lib.eepacc_create_classes(C.byref(h), S, self.veh, len(OPT_list), device, max_batch))
+        self.h = h
+        return self
+
+    def set_classes(self, class_of):
+        """eepacc_set_classes: class_of[i] is the settings class of instance i in the launches that follow (their B must be
+        len(class_of)).  Resets the carried loop state like reset()."""
+        m = np.ascontiguousarray(np.asarray(class_of).reshape(-1), dtype=np.int32)
+        _check(self.lib.eepacc_set_classes(self.h, int(m.size), as_iptr(m)))
+
+    @property
+    def num_classes(self) -> int:
+        return int(self.lib.eepacc_num_classes(self.h))
 
     def __del__(self):
         try:

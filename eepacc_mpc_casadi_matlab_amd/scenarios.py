@@ -47,3 +47,42 @@ def make_s1(B: int, golden: dict, s_tv: np.ndarray, v_tv: np.ndarray, Ts: float 
     vtv_prev = np.where(k > 1, v_tv[np.maximum(k - 1, 0)], 0.0)
     return dict(s=s, v=v, a_prev=a_prev, t0=k * Ts, s_tv=s_tv[k] + dgap, v_tv=vtv,
                 a_tv_prev=np.where(k > 0, (vtv - vtv_prev) / Ts, 0.0), k=k)
+
+
+def make_use_case_mix(cases, per_case: int, tree: str, N_hor: int, n_steps=None, argonne_lead=None):
+    """Several GetUseCase scenarios as the settings classes of one launch (Engine.from_classes): class k is cases[k], every
+    class has per_case instances, interleaved (class_of = 0, 1, 2, ..., 0, 1, 2, ...).  Each instance starts from its use
+    case's own s_init, v_init, a_minus1 and follows its use case's lead: the recorded one of 8 and 9 (argonne_lead =
+    (t, v_mph), the two columns of the measurement file), the cut-in of 10, none otherwise (s_tv = inf, v_tv = 0,
+    Main.m:77-80).  n_steps defaults to the shortest simulated time of the chosen cases (t_sim / Ts + 1).
+
+    Returns a dict: OPT (settings per class), V (vehicle per class), class_of [B], s0, v0, a_minus1 [B],
+    s_tv, v_tv [n_steps][B], n_steps."""
+    from .settings import Settings, SetVehicleParameters, default_opt
+    cases = [int(c) for c in cases]
+    if not cases or per_case < 1:
+        raise ValueError("make_use_case_mix needs at least one use case and per_case >= 1")
+    OPTs, Vs = [], []
+    for c in cases:
+        o = default_opt(); o["useCaseNum"] = c
+        if argonne_lead is not None:
+            o["argonne_lead"] = argonne_lead
+        OPTs.append(Settings(o, tree=tree, N_hor=N_hor))
+        Vs.append(SetVehicleParameters(tree))
+    full = [int(round(o["t_sim"] / o["Tvec"][0])) + 1 for o in OPTs]
+    if n_steps is None:
+        n_steps = min(full)
+    n_steps = int(n_steps)
+    if n_steps < 1 or n_steps > min(full):
+        raise ValueError("n_steps must be in [1, %d], the shortest simulated time of the chosen cases" % min(full))
+    K, B = len(cases), len(cases) * int(per_case)
+    class_of = (np.arange(B) % K).astype(np.int32)
+    s_tv = np.full((n_steps, B), np.inf)
+    v_tv = np.zeros((n_steps, B))
+    for k, (c, o) in enumerate(zip(cases, OPTs)):
+        if c in (8, 9, 10):
+            s_tv[:, class_of == k] = np.asarray(o["s_tv"], dtype=np.float64)[:n_steps, None]
+            v_tv[:, class_of == k] = np.asarray(o["v_tv"], dtype=np.float64)[:n_steps, None]
+    pick = lambda key: np.array([float(OPTs[k][key]) for k in class_of])
+    return dict(OPT=OPTs, V=Vs, class_of=class_of, s0=pick("s_init"), v0=pick("v_init"), a_minus1=pick("a_minus1"),
+                s_tv=s_tv, v_tv=v_tv, n_steps=n_steps)

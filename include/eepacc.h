@@ -169,6 +169,36 @@ int  eepacc_create(eepacc_handle** out, const eepacc_settings* S, const eepacc_v
                    int device, int max_batch);
 void eepacc_destroy(eepacc_handle* h);
 
+/* Settings classes: one handle for instances that differ in route, weights, estimator or vehicle, ABMPC only.  The
+ * reference runs one OPTsettings per call (ABO/Main.m:44-99, one useCaseNum of ABO/Functions/Settings/GetUseCase.m or one
+ * point of a Settings.m sweep at a time); here S[n_classes], V[n_classes] hold the settings and the vehicle of every class
+ * and each instance of a launch belongs to one of them, so the twelve use cases or a sweep over W_AB or the vehicle mass
+ * run in one launch.  Every class is validated like the settings of eepacc_create, before the device is touched.  What
+ * selects the kernel and the launch geometry must agree: N_hor and every entry of Tvec equal those of class 0
+ * (EEPACC_EINVAL otherwise), and no class may have move blocking (Mb all zero or NULL), ab_fuel_term = 2 or bl_mode != 0
+ * (EEPACC_ENOTSUP); the message names the class and the field.  Everything else may differ per class: the route tables,
+ * ab_route_rows, ab_fuel_term 0 or 1, W_AB, tau_min, h_min, s_goal, the estimator modes and time constants,
+ * N_integratePlant, state_bound_tol, b_fifthOrder and the whole vehicle.  n_classes must be in [1, EEPACC_MAX_CLASSES].
+ *
+ * Such a handle runs eepacc_ab_step, eepacc_run_abmpc (also resumed in chunks), eepacc_run_abmpc_host and
+ * eepacc_postprocess (each instance with the settings of its class) and eepacc_reset, eepacc_synchronize,
+ * eepacc_last_iterations; the FBMPC, BLMPC, TVMPC and dense-QP entry points return EEPACC_ENOTSUP on it.  It runs the
+ * class kernels also with n_classes = 1; the results of an instance are bit for bit those of a handle created by
+ * eepacc_create from the settings of its class. */
+#define EEPACC_MAX_CLASSES 4096
+int  eepacc_create_classes(eepacc_handle** out, const eepacc_settings* S, const eepacc_vehicle* V,
+                           int n_classes, int device, int max_batch);
+
+/* class_of_host [B], host, values in [0, n_classes): the class of instance i in the launches that follow.  The map is
+ * copied to the device (after waiting for the device's pending work) and the carried loop state is reset like
+ * eepacc_reset, since a change of the map in mid-simulation has no meaning.  B > max_batch or a value out of range:
+ * EEPACC_EINVAL, and the previous map stays.  A launch on a handle of eepacc_create_classes whose B differs from the last
+ * eepacc_set_classes, or with none made, returns EEPACC_EINVAL.  eepacc_reset keeps the map. */
+int  eepacc_set_classes(eepacc_handle* h, int B, const int32_t* class_of_host);
+
+/* Number of settings classes of a handle; 1 for a handle from eepacc_create. */
+int  eepacc_num_classes(const eepacc_handle* h);
+
 /* Reset the per-instance carried state (warm start, previous lead speed, FB A/D freeze,
  * step counter): the "kk == 0" branch of ABO/RunOpt_ABMPC.m:159-172. */
 int  eepacc_reset(eepacc_handle* h);
