@@ -1051,7 +1051,17 @@ __global__ void __launch_bounds__(QT, 2) k_qp_dense(eepacc_qp_args a) {     // t
                     TIC(t_k2);
                     int prc2 = kkt_solve(P, W, S, rho2, S.gr, S.act, q, S.xp, S.up, kk2);
                     TOC(t_k2, 7);
-                    if (prc2 == 0 && kk2[0] < 1e-9 && kk2[1] < 1e-9 && kk2[2] < 1e-9) {
+                    // that solve is stationary for the problem WITH its proximal term; for the problem itself the
+                    // gradient is off by rho2 (xp - x), which has to vanish too (it does not on an unbounded LP,
+                    // where every round moves by -g/rho)
+                    double prox_res = 0.0, pscale = 1.0;
+                    for (int i = threadIdx.x; i < n; i += QT) {
+                        prox_res = fmax(prox_res, rho2 * fabs(S.xp[i] - S.x[i]));
+                        pscale = fmax(pscale, fabs(P.g[i]));
+                    }
+                    for (int c = threadIdx.x; c < q; c += QT) pscale = fmax(pscale, fabs(S.up[c]));
+                    prox_res = block_max(prox_res, S); pscale = block_max(pscale, S);
+                    if (prc2 == 0 && kk2[0] < 1e-9 && kk2[1] < 1e-9 && kk2[2] < 1e-9 && prox_res < 1e-9 * pscale) {
                         for (int i = threadIdx.x; i < n; i += QT) S.x[i] = S.xp[i];
                         __syncthreads();
                         status = 0;

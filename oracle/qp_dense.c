@@ -739,7 +739,16 @@ int orc_qp_solve_dense(int nV, int nC, const double* H, const double* g, const d
                 int prc2 = kkt_polish(nV, Hr, gr2, A, &C, act, q, xp, up, kk2);
                 free(Hr); free(gr2);
                 if (getenv("ORC_DEBUG")) fprintf(stderr, "   face solve rc=%d kkt=%g %g %g\n", prc2, kk2[0], kk2[1], kk2[2]);
-                if (prc2 == 0 && kk2[0] < 1e-9 && kk2[1] < 1e-9 && kk2[2] < 1e-9) {
+                /* the face solve is stationary for the problem WITH its proximal term; for the problem itself the
+                 * gradient is off by rho2 (xp - x), which has to vanish too (it does not on an unbounded LP, where
+                 * every round moves by -g/rho) */
+                double prox_res = 0.0, pscale = 1.0;
+                for (int i = 0; i < nV; ++i) {
+                    prox_res = fmax(prox_res, rho2 * fabs(xp[i] - x[i]));
+                    pscale = fmax(pscale, fabs(g[i]));
+                }
+                for (int c2 = 0; c2 < q; ++c2) pscale = fmax(pscale, fabs(up[c2]));
+                if (prc2 == 0 && kk2[0] < 1e-9 && kk2[1] < 1e-9 && kk2[2] < 1e-9 && prox_res < 1e-9 * pscale) {
                     memcpy(x, xp, sizeof(double) * nV);
                     memcpy(u, up, sizeof(double) * q);
                     kkt[0] = kk2[0]; kkt[1] = kk2[1]; kkt[2] = kk2[2];
