@@ -16,6 +16,14 @@ OUT_FIELDS = ["s", "v", "Fm", "Fb", "a", "xi_v", "xi_h", "xi_s", "xi_f", "cost",
 OUT_N = len(OUT_FIELDS)
 OUT = {name: i for i, name in enumerate(OUT_FIELDS)}
 
+# enum EEPACC_KPI_*: rows of the table of eepacc_kpis, raw SI units
+KPI_FIELDS = ["bad_exits", "distance_m", "energy_J", "cutoff_index", "reached", "vlim_err", "energy_cutoff_J", "time_cutoff_s",
+              "a_max", "a_min", "a_rms", "j_max", "j_min", "j_rms", "fuel_kg", "FE_L_per_100km"]
+KPI_N = len(KPI_FIELDS)
+KPI = {name: i for i, name in enumerate(KPI_FIELDS)}
+KPI_WAVES = 16        # EEPACC_KPI_WAVES
+KPI_MIN_SLICE = 8     # EEPACC_KPI_MIN_SLICE
+
 _VEH_FIELDS = ["m", "A_f", "c_d", "L", "h_g", "WD_s_F", "L_f", "L_r", "F0", "F1", "F2",
                "p00", "p10", "p01", "P_m_max", "T_m_max", "omega_m_r", "omega_m_max",
                "c_r", "R_w", "beta_gb", "beta_fd", "phi", "v_max", "eta_TF",

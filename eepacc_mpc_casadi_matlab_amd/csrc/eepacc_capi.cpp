@@ -13,9 +13,11 @@
 #include "eepacc_qp_dense.h"
 #include "eepacc_fb.h"
 #include "eepacc_fbs.h"
+#include "eepacc_kpis.h"
 #include "../../include/eepacc.h"
 
 using eepacc::DevCfg;
+using eepacc::KpiCfg;
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) { g_err = msg; return code; }
@@ -80,6 +82,9 @@ struct eepacc_handle {
     int n_classes = 0;
     DevMem<int32_t> d_class_of;              // [max_batch] class of every instance
     int classes_B = 0;                       // B of the last eepacc_set_classes (0: none yet)
+    // key figures (eepacc_kpis): what they read of every class, and the cut-off distances of the call in flight
+    DevMem<KpiCfg> d_kpi;                    // [max(n_classes, 1)]
+    DevMem<double> d_kpi_cut;                // [max(n_classes, 1)]
     eepacc::AbVariant variant() const { return n_classes ? eepacc::AbVariant::Classes : eepacc::ab_variant(cfg); }
     const int32_t* class_map() const { return n_classes ? d_class_of.p : nullptr; }
 };
@@ -282,10 +287,24 @@ static int build_cfg(const eepacc_settings* S, const eepacc_vehicle* V, DevCfg& 
     return EEPACC_OK;
 }
 
+// What eepacc_kpis reads of a class (validated by build_cfg before): the power fit and driveline of the energy, the fuel
+// map and coast-down terms of ABO/Custom_plots.m:73-107 and the speed-limit table of ABO/Main.m:133.
+static KpiCfg build_kpi_cfg(const eepacc_settings* S, const eepacc_vehicle* V) {
+    KpiCfg K;
+    memset(&K, 0, sizeof(K));
+    K.Ts = S->Tvec[0]; K.phi = V->phi;
+    for (int i = 0; i < 21; ++i) K.b5[i] = S->b_fifthOrder[i];
+    K.lm = V->lambda * V->m; K.F0 = V->F0; K.F2 = V->F2; K.R_w = V->R_w;
+    K.p00 = V->p00; K.p10 = V->p10; K.p01 = V->p01;
+    K.n_speedLim = S->n_speedLim;
+    for (int i = 0; i < S->n_speedLim; ++i) { K.s_speedLim[i] = S->s_speedLim[i]; K.v_speedLim[i] = S->v_speedLim[i]; }
+    return K;
+}
+
 // The device side of a handle.  Cs: one validated DevCfg per class with its inverse Hessian in Hinv (N x N each, class after
 // class); classes: the handle of eepacc_create_classes, which keeps a class map and runs AbVariant::Classes, also with one class.
-static int create_on_device(eepacc_handle** out, std::vector<DevCfg>& Cs, const std::vector<double>& Hinv, bool classes,
-                            int device, int max_batch) {
+static int create_on_device(eepacc_handle** out, std::vector<DevCfg>& Cs, const std::vector<double>& Hinv,
+                            const std::vector<KpiCfg>& Ks, bool classes, int device, int max_batch) {
     DevCfg& C = Cs[0];
     int ndev = 0;
     HIPCHK(hipGetDeviceCount(&ndev));
@@ -313,6 +332,9 @@ static int create_on_device(eepacc_handle** out, std::vector<DevCfg>& Cs, const 
     h->cfg = C;
     HIPCHK(h->d_cfg.alloc(Cs.size()));
     HIPCHK(hipMemcpy(h->d_cfg, Cs.data(), Cs.size() * sizeof(DevCfg), hipMemcpyHostToDevice));
+    HIPCHK(h->d_kpi.alloc(Ks.size()));
+    HIPCHK(hipMemcpy(h->d_kpi, Ks.data(), Ks.size() * sizeof(KpiCfg), hipMemcpyHostToDevice));
+    HIPCHK(h->d_kpi_cut.alloc_zero(Ks.size()));
     if (classes) {
         h->n_classes = (int)Cs.size();
         HIPCHK(h->d_class_of.alloc_zero(nB));
@@ -346,7 +368,7 @@ extern "C" int eepacc_create(eepacc_handle** out, const eepacc_settings* S, cons
     std::vector<double> Hinv;
     int rc = build_cfg(S, V, Cs[0], Hinv);
     if (rc != EEPACC_OK) return rc;
-    return create_on_device(out, Cs, Hinv, false, device, max_batch);
+    return create_on_device(out, Cs, Hinv, {build_kpi_cfg(S, V)}, false, device, max_batch);
 }
 
 // Every class is checked like the settings of eepacc_create, and against class 0 in what selects the kernel and the launch
@@ -361,6 +383,7 @@ extern "C" int eepacc_create_classes(eepacc_handle** out, const eepacc_settings*
     if (N < 2 || N > eepacc::kMaxN) return fail(EEPACC_EINVAL, "eepacc_create_classes: class 0: N_hor must be in [2, 63]");
     std::vector<DevCfg> Cs((size_t)n_classes);
     std::vector<double> Hinv, Hk;
+    std::vector<KpiCfg> Ks;
     for (int k = 0; k < n_classes; ++k) {
         const std::string who = "eepacc_create_classes: class " + std::to_string(k) + ": ";
         if (S[k].N_hor != N)
@@ -376,8 +399,9 @@ extern "C" int eepacc_create_classes(eepacc_handle** out, const eepacc_settings*
             if (Cs[(size_t)k].Tvec[j] != Cs[0].Tvec[j])
                 return fail(EEPACC_EINVAL, who + "Tvec[" + std::to_string(j) + "] differs from class 0; the classes of a handle share the time grid");
         Hinv.insert(Hinv.end(), Hk.begin(), Hk.end());
+        Ks.push_back(build_kpi_cfg(&S[k], &V[k]));
     }
-    return create_on_device(out, Cs, Hinv, true, device, max_batch);
+    return create_on_device(out, Cs, Hinv, Ks, true, device, max_batch);
 }
 
 extern "C" int eepacc_num_classes(const eepacc_handle* h) { return h && h->n_classes ? h->n_classes : 1; }
@@ -535,6 +559,30 @@ extern "C" int eepacc_postprocess(eepacc_handle* h, int B, int n_steps, const do
     if (const int rc = classes_ready(h, "eepacc_postprocess", B)) return rc;
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(eepacc::launch_postprocess(h->d_cfg, h->class_map(), B, n_steps, traj, rpm, Tm, P, E, (hipStream_t)stream));
+    return EEPACC_OK;
+}
+
+// Key figures of a closed-loop trajectory (ABO/Main.m:131-263, ABO/Custom_plots.m:73-107), per instance, on the device.
+// Reads the trajectory and the handle's KpiCfg table only: no carried state, so it may follow a launch of any controller.
+extern "C" int eepacc_kpis(eepacc_handle* h, int B, int n_steps, const double* traj, const int32_t* status,
+                           const double* cutoff_dist_host, double* kpi, void* stream) {
+    if (!h) return fail(EEPACC_EINVAL, "NULL handle");
+    if (B < 0 || B > h->max_batch) return fail(EEPACC_EINVAL, "eepacc_kpis: B = " + std::to_string(B) + " is outside [0, max_batch = " + std::to_string(h->max_batch) + "]");
+    if (n_steps < 1) return fail(EEPACC_EINVAL, "eepacc_kpis: n_steps = " + std::to_string(n_steps) + " must be at least 1");
+    if (!traj) return fail(EEPACC_EINVAL, "eepacc_kpis: traj is NULL");
+    if (!status) return fail(EEPACC_EINVAL, "eepacc_kpis: status is NULL");
+    if (!cutoff_dist_host) return fail(EEPACC_EINVAL, "eepacc_kpis: cutoff_dist_host is NULL");
+    if (!kpi) return fail(EEPACC_EINVAL, "eepacc_kpis: kpi is NULL");
+    const int nc = h->n_classes ? h->n_classes : 1;
+    for (int k = 0; k < nc; ++k)
+        if (!isfinite(cutoff_dist_host[k]))
+            return fail(EEPACC_EINVAL, "eepacc_kpis: cutoff_dist_host[" + std::to_string(k) + "] is not finite");
+    if (B == 0) return EEPACC_OK;
+    if (const int rc = classes_ready(h, "eepacc_kpis", B)) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    // stream ordered behind an earlier call's kernel; the host array may be reused when this returns (pageable source)
+    HIPCHK(hipMemcpyAsync(h->d_kpi_cut, cutoff_dist_host, (size_t)nc * sizeof(double), hipMemcpyHostToDevice, (hipStream_t)stream));
+    HIPCHK(eepacc::launch_kpis(h->d_kpi, h->class_map(), h->d_kpi_cut, B, n_steps, traj, status, kpi, (hipStream_t)stream));
     return EEPACC_OK;
 }
 

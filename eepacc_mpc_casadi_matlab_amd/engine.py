@@ -13,7 +13,7 @@ from typing import Any, Dict, Optional
 
 import numpy as np
 
-from ._abi import (SettingsHolder, SettingsPOD, Vehicle, make_vehicle, pack_classes, OUT, OUT_N, OUT_FIELDS, c_double_p,
+from ._abi import (SettingsHolder, SettingsPOD, Vehicle, make_vehicle, pack_classes, OUT, OUT_N, OUT_FIELDS, KPI_N, c_double_p,
                    as_dptr, as_iptr)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -62,6 +62,7 @@ def load_library() -> C.CDLL:
     lib.eepacc_run_tvmpc.argtypes = [vp, C.c_int, C.c_int] + [dp] * 3 + [dp, dp, vp]
     lib.eepacc_run_tvmpc_host.argtypes = [vp, C.c_int, C.c_int] + [c_double_p] * 3 + [c_double_p, ip]
     lib.eepacc_postprocess.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, dp, vp]
+    lib.eepacc_kpis.argtypes = [vp, C.c_int, C.c_int, dp, dp, c_double_p, dp, vp]
     lib.eepacc_last_iterations.argtypes = [vp, C.c_int, ip]
     lib.eepacc_fb_step.argtypes = [vp, C.c_int] + [dp] * 10 + [dp, dp, dp, dp, vp]
     lib.eepacc_run_fbmpc.argtypes = [vp, C.c_int, C.c_int] + [dp] * 5 + [dp, dp, vp]
@@ -77,7 +78,7 @@ ABI_SYMBOLS = ["eepacc_last_error", "eepacc_version", "eepacc_sizeof_settings", 
                "eepacc_create_classes", "eepacc_set_classes", "eepacc_num_classes",
                "eepacc_ab_step", "eepacc_run_abmpc", "eepacc_fb_step", "eepacc_run_fbmpc",
                "eepacc_run_abmpc_host", "eepacc_run_fbmpc_host", "eepacc_bl_step", "eepacc_run_blmpc", "eepacc_run_blmpc_host",
-               "eepacc_tv_step", "eepacc_run_tvmpc", "eepacc_run_tvmpc_host", "eepacc_postprocess",
+               "eepacc_tv_step", "eepacc_run_tvmpc", "eepacc_run_tvmpc_host", "eepacc_postprocess", "eepacc_kpis",
                "eepacc_last_iterations", "eepacc_qp_solve_batched", "eepacc_synchronize", "eepacc_build_flags"]
 
 
@@ -234,6 +235,28 @@ class Engine:
         _check(self.lib.eepacc_postprocess(self.h, B, n_steps, traj.data_ptr(), *[o.data_ptr() for o in outs],
                                            self._stream()))
         return outs   # rpm, Tm, P, E
+
+    def kpis(self, traj, status, cutoff_dist):
+        """eepacc_kpis: the key figures of ABO/Main.m:131-263 and ABO/Custom_plots.m:73-107 for every instance of a
+        closed-loop run, reduced on the device.  traj [n_steps, OUT_N, B] and status [n_steps, B] as the run_* methods
+        return them; cutoff_dist: cutOffDist as a scalar or with one value per settings class.  Returns the device tensor
+        [KPI_N, B] (rows: _abi.KPI_FIELDS, raw SI units); report.table_to_reports turns it into the dicts of kpi_report."""
+        t = self.torch
+        traj = t.as_tensor(traj, dtype=t.float64, device=self.device).contiguous()
+        status = t.as_tensor(status, dtype=t.int32, device=self.device).contiguous()
+        if traj.dim() != 3 or traj.shape[1] != OUT_N or status.shape != (traj.shape[0], traj.shape[2]):
+            raise ValueError("kpis needs traj [n_steps, %d, B] and status [n_steps, B]" % OUT_N)
+        n_steps, _, B = traj.shape
+        cut = np.asarray(cutoff_dist, dtype=np.float64).reshape(-1)
+        if cut.size == 1:
+            cut = np.full(self.num_classes, cut[0])
+        if cut.size != self.num_classes:
+            raise ValueError(f"cutoff_dist needs one value or one per class ({self.num_classes}), got {cut.size}")
+        cut = np.ascontiguousarray(cut)
+        kpi = t.empty((KPI_N, B), dtype=t.float64, device=self.device)
+        _check(self.lib.eepacc_kpis(self.h, B, n_steps, traj.data_ptr(), status.data_ptr(), as_dptr(cut), kpi.data_ptr(),
+                                    self._stream()))
+        return kpi
 
     # B3 ------------------------------------------------------------------------------------
     def qp_solve_batched(self, H, g, A, lba=None, uba=None, lbx=None, ubx=None, x0=None):

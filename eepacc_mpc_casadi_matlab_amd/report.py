@@ -2,7 +2,9 @@
 
 ``kpi_report(optSol, OPTsettings)`` takes the struct returned by ``RunOpt_ABMPC`` / ``RunOpt_FBMPC``
 (or a saved solution with the same fields) and returns them as a dict; ``format_report`` renders the
-text block of Main.m for one controller.  Host-side numpy only.
+text block of Main.m for one controller.  ``kpi_table`` is the same for a batch, as a table: the specification of the
+device operator eepacc_kpis (``Engine.kpis``); ``table_to_reports`` and ``summarise_table`` read such a table.
+Host-side numpy only.
 """
 from __future__ import annotations
 
@@ -58,6 +60,151 @@ def kpi_report(sol: Dict[str, Any], OPT: Dict[str, Any]) -> Dict[str, float]:
         "a_max": float(a[:ind].max()), "a_min": float(a[:ind].min()), "a_rms": _rms(a[:ind]),       # :257
         "j_max": float(j[:ind].max()), "j_min": float(j[:ind].min()), "j_rms": _rms(j[:ind]),       # :261
     }
+
+
+def _two_sum(a, b):
+    s = a + b
+    t = s - a
+    return s, (a - (s - t)) + (b - t)
+
+
+def _split(x):
+    t = 134217729.0 * x                      # 2^27 + 1 (Veltkamp): x = hi + lo with 26-bit halves
+    hi = t - (t - x)
+    return hi, x - hi
+
+
+def _fma(a, b, c):
+    """The correctly rounded a * b + c of a fused multiply-add, for float64 arrays, in numpy: the exact product as a pair
+    (Dekker / Veltkamp), the exact sum of c and its high part, the two low parts added with rounding to odd, one final
+    rounding (Boldo and Melquiond, "Emulation of a FMA and correctly rounded sums", IEEE Trans. Computers 57, 2008).
+    Exact away from overflow and from underflow of the product's low part, where the power surface stays."""
+    a, b, c = [np.ascontiguousarray(x) for x in np.broadcast_arrays(*[np.atleast_1d(np.asarray(x, dtype=np.float64)) for x in (a, b, c)])]
+    (ah, al), (bh, bl) = _split(a), _split(b)
+    uh = a * b
+    ul = ((ah * bh - uh) + ah * bl + al * bh) + al * bl
+    th, tl = _two_sum(c, uh)
+    v, e = _two_sum(tl, ul)
+    # to odd: an inexact sum whose last bit is even moves one step towards the part that was rounded off
+    to_odd = (e != 0.0) & ((v.view(np.int64) & 1) == 0)
+    v = np.where(to_odd, np.nextafter(v, np.where(e > 0.0, np.inf, -np.inf)), v)
+    return th + v
+
+
+def power_surface(b5, Fm, rpm):
+    """The fifth-order battery-power surface of ABO/RunOpt_ABMPC.m:343-349 with the roundings of the device function of the
+    same name (csrc/eepacc_power.h), which are those of eepacc_postprocess: plain products for the monomials, and every
+    term added by one fused multiply-add, fma(c, m, acc) or fma(c * m1, m2, acc), in the order of the coefficient list."""
+    bb = np.asarray(b5, dtype=np.float64).ravel()
+    x = np.asarray(Fm, dtype=np.float64); y = np.asarray(rpm, dtype=np.float64)
+    x2 = x * x; x3 = x2 * x; x4 = x3 * x; x5 = x4 * x
+    y2 = y * y; y3 = y2 * y; y4 = y3 * y; y5 = y4 * y
+    p = _fma(bb[1], x, bb[0])
+    for c, m in ((bb[2], y), (bb[3], x2), (bb[4] * x, y), (bb[5], y2), (bb[6], x3), (bb[7] * x2, y), (bb[8] * x, y2),
+                 (bb[9], y3), (bb[10], x4), (bb[11] * x3, y), (bb[12] * x2, y2), (bb[13] * x, y3), (bb[14], y4),
+                 (bb[15], x5), (bb[16] * x4, y), (bb[17] * x3, y2), (bb[18] * x2, y3), (bb[19] * x, y4), (bb[20], y5)):
+        p = _fma(c, m, p)
+    return p
+
+
+def kpi_table(s, v, Fm, a, status, Ts, cut, s_speedLim, v_speedLim, b5, phi, V) -> np.ndarray:
+    """The key figures of kpi_report and fuel_economy for a batch, as a table [KPI_N, B] (rows: _abi.KPI_FIELDS) in raw SI
+    units without rounding: the specification of eepacc_kpis (include/eepacc.h) in executable form, numpy on the host.
+
+    s, v, Fm, a, status: [n, B] rows of a closed-loop trajectory; Ts = Tvec[0]; cut: cutOffDist, a scalar or [B]; the
+    speed-limit table, the power fit b5, phi and the vehicle V are those of the instances' settings class (one class
+    per call).  With P = power_surface(b5, Fm, 30/pi v phi) and E = Ts cumsum(P):
+
+        bad_exits        count of status != 0                                            Main.m:210
+        distance_m       s[n-1]                                                          :220
+        energy_J         E[n-1]                                                          :226
+        cutoff_index     ind: the first i >= 1 with s[i-1] < cut < s[i], else n-1        :150-161
+        reached          1.0 where such an i exists, else 0.0
+        vlim_err         InterpPWA(cut, s_speedLim, v_speedLim) - v[ind-2]               :133,232
+        energy_cutoff_J  E[ind-2]                                                        :245
+        time_cutoff_s    ind Ts                                                          :238
+        a_max a_min a_rms   of a[0:ind]                                                  :257
+        j_max j_min j_rms   of j[0:ind], j = diff(a) / Ts (n-1 entries)                  :261
+        fuel_kg          last value of FC_tot of fuel_economy (first sample zero)        Custom_plots.m:81-90
+        FE_L_per_100km   fuel_kg / 0.835 / (max(s) / 1000) * 100                         :100-107
+
+    Two conventions where kpi_report is undefined: for ind < 2 the sample index ind-2 is taken as 0 (kpi_report's
+    negative index wraps to the last sample); for n = 1 (ind = 0) the jerk figures are 0 and the acceleration figures
+    are those of a[0]."""
+    from ._abi import KPI, KPI_N
+    s, v, Fm, a = [np.asarray(x, dtype=np.float64) for x in (s, v, Fm, a)]
+    n, B = s.shape
+    Ts = float(Ts)
+    cut = np.broadcast_to(np.asarray(cut, dtype=np.float64).reshape(-1), (B,))
+    cols = np.arange(B)
+    cross = (s[:-1] < cut) & (s[1:] > cut)                                           # row i-1: the pair (i-1, i)
+    reached = cross.any(axis=0)
+    ind = np.where(reached, cross.argmax(axis=0) + 1, n - 1) if n > 1 else np.zeros(B, dtype=np.int64)
+    k2 = np.maximum(ind - 2, 0)
+    P = power_surface(b5, Fm, 30.0 / np.pi * v * phi)
+    E = Ts * np.cumsum(P, axis=0)
+    vlim = np.array([InterpPWA(float(c), s_speedLim, v_speedLim) for c in cut])
+    k = np.arange(n)[:, None]
+    in_a = k < np.maximum(ind, 1)[None, :]
+    cnt = np.maximum(ind, 1).astype(np.float64)
+    T = np.zeros((KPI_N, B))
+    T[KPI["bad_exits"]] = (np.asarray(status) != 0).sum(axis=0)
+    T[KPI["distance_m"]] = s[-1]
+    T[KPI["energy_J"]] = E[-1]
+    T[KPI["cutoff_index"]] = ind
+    T[KPI["reached"]] = reached
+    T[KPI["vlim_err"]] = vlim - v[k2, cols]
+    T[KPI["energy_cutoff_J"]] = E[k2, cols]
+    T[KPI["time_cutoff_s"]] = ind * Ts
+    T[KPI["a_max"]] = np.where(in_a, a, -np.inf).max(axis=0)
+    T[KPI["a_min"]] = np.where(in_a, a, np.inf).min(axis=0)
+    T[KPI["a_rms"]] = np.sqrt(np.where(in_a, a * a, 0.0).sum(axis=0) / cnt)
+    if n > 1:
+        j = np.diff(a, axis=0) / Ts
+        in_j = k[:-1] < ind[None, :]
+        T[KPI["j_max"]] = np.where(in_j, j, -np.inf).max(axis=0)
+        T[KPI["j_min"]] = np.where(in_j, j, np.inf).min(axis=0)
+        T[KPI["j_rms"]] = np.sqrt(np.where(in_j, j * j, 0.0).sum(axis=0) / cnt)
+    TW = np.maximum(0.0, (V["lambda"] * V["m"] * a + V["F0"] + V["F2"] * v * v) * V["R_w"])
+    FC = np.maximum(0.25, V["p00"] + V["p10"] * v + V["p01"] * TW)
+    FC[0] = 0.0
+    T[KPI["fuel_kg"]] = np.cumsum(FC / 1000.0 * Ts, axis=0)[-1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        T[KPI["FE_L_per_100km"]] = T[KPI["fuel_kg"]] / 0.835 / (s.max(axis=0) / 1000.0) * 100.0
+    return T
+
+
+def table_to_reports(table) -> list:
+    """The dicts of kpi_report, one per column of a table of kpi_table / Engine.kpis: km and kWh, the 0.1 s rounding of
+    the travel time (Main.m:238), plus reached, fuel_kg and FE_L_per_100km.  format_report renders each."""
+    from ._abi import KPI
+    T = np.asarray(table.cpu() if hasattr(table, "cpu") else table, dtype=np.float64)
+    out = []
+    for i in range(T.shape[1]):
+        c = {name: float(T[row, i]) for name, row in KPI.items()}
+        out.append({
+            "bad_exit_messages": c["bad_exits"], "distance_km": c["distance_m"] / 1e3, "energy_kWh": c["energy_J"] / 3.6e6,
+            "cutoff_index": c["cutoff_index"], "speed_limit_error_at_cutoff": c["vlim_err"],
+            "energy_at_cutoff_kWh": c["energy_cutoff_J"] / 3.6e6,
+            "travel_time_at_cutoff_s": 0.1 * round(c["time_cutoff_s"] * 10),
+            "a_max": c["a_max"], "a_min": c["a_min"], "a_rms": c["a_rms"],
+            "j_max": c["j_max"], "j_min": c["j_min"], "j_rms": c["j_rms"],
+            "reached": c["reached"], "fuel_kg": c["fuel_kg"], "FE_L_per_100km": c["FE_L_per_100km"]})
+    return out
+
+
+def summarise_table(table, class_of) -> Dict[str, np.ndarray]:
+    """Per-class mean, minimum and maximum of every row of a table: {"classes": the class ids that occur, ascending [K],
+    "count" [K], "mean" / "min" / "max" [K, KPI_N]} (rows of the three in the order of _abi.KPI_FIELDS)."""
+    T = np.asarray(table.cpu() if hasattr(table, "cpu") else table, dtype=np.float64)
+    class_of = np.asarray(class_of).reshape(-1)
+    if class_of.size != T.shape[1]:
+        raise ValueError(f"class_of needs one entry per column of the table ({T.shape[1]}), got {class_of.size}")
+    classes = np.unique(class_of)
+    cols = [T[:, class_of == c] for c in classes]
+    return {"classes": classes, "count": np.array([x.shape[1] for x in cols]),
+            "mean": np.array([x.mean(axis=1) for x in cols]), "min": np.array([x.min(axis=1) for x in cols]),
+            "max": np.array([x.max(axis=1) for x in cols])}
 
 
 def format_report(name: str, k: Dict[str, float], OPT: Dict[str, Any]) -> str:

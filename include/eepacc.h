@@ -314,6 +314,53 @@ int  eepacc_run_tvmpc_host(eepacc_handle* h, int B, int n_steps,
 int  eepacc_postprocess(eepacc_handle* h, int B, int n_steps, const double* traj,
                         double* rpm, double* Tm, double* P, double* E, void* stream);
 
+/* Key figures of a closed-loop run, per instance, on the device: what the reference prints for every run in the report of
+ * ABO/Main.m:131-263 and the fuel economy of ABO/Custom_plots.m:73-107.  Inputs, device: traj [n_steps][EEPACC_OUT_N][B] and
+ * status [n_steps][B] as every eepacc_run_* entry point writes them; rows S, V, FM and A of traj are read, the other eight
+ * are not.  Output, device: kpi [EEPACC_KPI_N][B], batch-major, raw SI units without rounding (km, kWh and the
+ * 0.1*round(10 t) of the travel time are left to the caller).  cutoff_dist_host, host, [the handle's number of classes]:
+ * cutOffDist of every class, `cut` below; it may be reused when the call returns.  With n = n_steps, Ts = Tvec[0],
+ * P_k the fifth-order surface b_fifthOrder at (Fm_k, 30/pi v_k phi) (ABO/RunOpt_ABMPC.m:343-349, as eepacc_postprocess)
+ * and E_k = Ts sum_{i<=k} P_i: */
+enum {
+    EEPACC_KPI_BAD_EXITS = 0,    /* Main.m:210  count of status != 0 over all steps                                       */
+    EEPACC_KPI_DISTANCE_M,       /* Main.m:220  s[n-1]                                                                    */
+    EEPACC_KPI_ENERGY_J,         /* Main.m:226  E[n-1]                                                                    */
+    EEPACC_KPI_CUTOFF_INDEX,     /* Main.m:150-161  ind: the first i >= 1 with s[i-1] < cut < s[i], else n-1 (0-based i;  */
+                                 /*             the reference's 1-based index of the sample before)                       */
+    EEPACC_KPI_REACHED,          /* 1.0 if such an i exists, else 0.0                                                     */
+    EEPACC_KPI_VLIM_ERR,         /* Main.m:133,232  InterpPWA(cut, s_speedLim, v_speedLim) - v[ind-2]                     */
+    EEPACC_KPI_ENERGY_CUTOFF_J,  /* Main.m:245  E[ind-2]                                                                  */
+    EEPACC_KPI_TIME_CUTOFF_S,    /* Main.m:238  ind * Ts                                                                  */
+    EEPACC_KPI_A_MAX,            /* Main.m:257  max, min and root mean square of a[0 .. ind-1]                            */
+    EEPACC_KPI_A_MIN,
+    EEPACC_KPI_A_RMS,
+    EEPACC_KPI_J_MAX,            /* Main.m:261  the same of j[0 .. ind-1], j[k] = (a[k+1] - a[k]) / Ts (n-1 entries)      */
+    EEPACC_KPI_J_MIN,
+    EEPACC_KPI_J_RMS,
+    EEPACC_KPI_FUEL_KG,          /* Custom_plots.m:81-90  Ts/1000 sum_{k>=1} FC_k, FC = max(0.25, p00 + p10 v + p01 TW),  */
+                                 /*             TW = max(0, (lambda m a + F0 + F2 v^2) R_w); the first sample counts zero */
+    EEPACC_KPI_FE_L_PER_100KM,   /* Custom_plots.m:100-107  FUEL_KG / 0.835 / (max_k s[k] / 1000) * 100                   */
+    EEPACC_KPI_N
+};
+/* Two cases the reference leaves open are fixed here.  Where ind < 2 the sample index ind-2 is taken as 0 (MATLAB would
+ * stop with an index error, a 0-based host port wraps to the last sample).  Where n_steps = 1 there is no jerk and no
+ * sample before the cut-off: ind = 0, the three jerk figures are 0 and the acceleration figures are those of a[0].
+ *
+ * Works on every kind of handle (ABMPC in all variants, BLMPC, TVMPC, FBMPC); on a handle of eepacc_create_classes every
+ * instance is evaluated with the constants and the cut-off of its class (eepacc_set_classes must have been called for
+ * this B).  Asynchronous on stream; reads and writes no carried state of the handle, and a result does not depend on
+ * timing: the same input gives the same bits.  EEPACC_EINVAL, with a message that names the argument: a NULL buffer,
+ * n_steps < 1, B > max_batch, a class map that is not set or was set for another B, a cut-off that is not finite.
+ * B = 0 returns EEPACC_OK.
+ *
+ * Launch geometry, for callers who choose sizes: a workgroup of EEPACC_KPI_WAVES waves serves 64 instances and each
+ * wave reduces max(EEPACC_KPI_MIN_SLICE, ceil(n_steps / EEPACC_KPI_WAVES)) consecutive steps. */
+#define EEPACC_KPI_WAVES      16
+#define EEPACC_KPI_MIN_SLICE   8
+int  eepacc_kpis(eepacc_handle* h, int B, int n_steps, const double* traj, const int32_t* status,
+                 const double* cutoff_dist_host, double* kpi, void* stream);
+
 /* Solver statistics of the last launch, device [B]: active-set iterations used. */
 int  eepacc_last_iterations(eepacc_handle* h, int B, int32_t* iters_host);
 
