@@ -24,6 +24,13 @@ KPI = {name: i for i, name in enumerate(KPI_FIELDS)}
 KPI_WAVES = 16        # EEPACC_KPI_WAVES
 KPI_MIN_SLICE = 8     # EEPACC_KPI_MIN_SLICE
 
+# enum EEPACC_FKPI_*: rows of the table of eepacc_follow_kpis, raw SI units, and the values of its `weights` argument
+FKPI_FIELDS = ["lead_samples", "h_min_m", "h_min_index", "thw_min_s", "margin_min_m", "margin_viol_steps", "ttc_min_s", "xi_h_max",
+               "cost_P", "cost_a", "cost_j", "cost_xi_v", "cost_xi_h", "cost_xi_s", "cost_xi_f"]
+FKPI_N = len(FKPI_FIELDS)
+FKPI = {name: i for i, name in enumerate(FKPI_FIELDS)}
+FKPI_WEIGHTS = {"ab": 0, "fb": 1, "none": 2}      # EEPACC_FKPI_W_AB, _W_FB, _W_NONE
+
 _VEH_FIELDS = ["m", "A_f", "c_d", "L", "h_g", "WD_s_F", "L_f", "L_r", "F0", "F1", "F2",
                "p00", "p10", "p01", "P_m_max", "T_m_max", "omega_m_r", "omega_m_max",
                "c_r", "R_w", "beta_gb", "beta_fd", "phi", "v_max", "eta_TF",

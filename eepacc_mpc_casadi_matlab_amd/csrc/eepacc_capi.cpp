@@ -14,10 +14,12 @@
 #include "eepacc_fb.h"
 #include "eepacc_fbs.h"
 #include "eepacc_kpis.h"
+#include "eepacc_follow.h"
 #include "../../include/eepacc.h"
 
 using eepacc::DevCfg;
 using eepacc::KpiCfg;
+using eepacc::FollowCfg;
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) { g_err = msg; return code; }
@@ -85,6 +87,7 @@ struct eepacc_handle {
     // key figures (eepacc_kpis): what they read of every class, and the cut-off distances of the call in flight
     DevMem<KpiCfg> d_kpi;                    // [max(n_classes, 1)]
     DevMem<double> d_kpi_cut;                // [max(n_classes, 1)]
+    DevMem<FollowCfg> d_follow;              // [max(n_classes, 1)] what eepacc_follow_kpis reads of every class
     eepacc::AbVariant variant() const { return n_classes ? eepacc::AbVariant::Classes : eepacc::ab_variant(cfg); }
     const int32_t* class_map() const { return n_classes ? d_class_of.p : nullptr; }
 };
@@ -301,10 +304,28 @@ static KpiCfg build_kpi_cfg(const eepacc_settings* S, const eepacc_vehicle* V) {
     return K;
 }
 
+// What eepacc_follow_kpis reads of a class: the minimum-headway policy of ABO/Main.m:687, the power surface of cost_P and
+// the weights of the reference's cost_* series, one row per EEPACC_FKPI_W_*, in the order w_P, w_a, w_j, w_v, w_h, w_s, w_f.
+// RunOpt_ABMPC.m:383-388 takes W(1..5) of the user's W_AB with w_f = W(5); ORIG's six entries are stored behind a leading
+// zero (ab_fuel_term = 0), ABO's seven as they are, so that W(1) is w_FC there, as in the reference's own cost_a.
+static FollowCfg build_follow_cfg(const eepacc_settings* S, const eepacc_vehicle* V) {
+    FollowCfg F;
+    memset(&F, 0, sizeof(F));
+    F.Ts = S->Tvec[0]; F.h_min = S->h_min; F.tau_min = S->tau_min; F.phi = V->phi;
+    for (int i = 0; i < 21; ++i) F.b5[i] = S->b_fifthOrder[i];
+    const double* W = S->W_AB + (S->ab_fuel_term ? 0 : 1);
+    for (int i = 0; i < 5; ++i) F.w[EEPACC_FKPI_W_AB][1 + i] = W[i];
+    F.w[EEPACC_FKPI_W_AB][6] = W[4];
+    for (int i = 0; i < 7; ++i) F.w[EEPACC_FKPI_W_FB][i] = S->W_FB[i];
+    for (int i = 1; i < 7; ++i) F.w[EEPACC_FKPI_W_NONE][i] = 1.0;
+    return F;
+}
+
 // The device side of a handle.  Cs: one validated DevCfg per class with its inverse Hessian in Hinv (N x N each, class after
 // class); classes: the handle of eepacc_create_classes, which keeps a class map and runs AbVariant::Classes, also with one class.
 static int create_on_device(eepacc_handle** out, std::vector<DevCfg>& Cs, const std::vector<double>& Hinv,
-                            const std::vector<KpiCfg>& Ks, bool classes, int device, int max_batch) {
+                            const std::vector<KpiCfg>& Ks, const std::vector<FollowCfg>& Fs, bool classes, int device,
+                            int max_batch) {
     DevCfg& C = Cs[0];
     int ndev = 0;
     HIPCHK(hipGetDeviceCount(&ndev));
@@ -335,6 +356,8 @@ static int create_on_device(eepacc_handle** out, std::vector<DevCfg>& Cs, const 
     HIPCHK(h->d_kpi.alloc(Ks.size()));
     HIPCHK(hipMemcpy(h->d_kpi, Ks.data(), Ks.size() * sizeof(KpiCfg), hipMemcpyHostToDevice));
     HIPCHK(h->d_kpi_cut.alloc_zero(Ks.size()));
+    HIPCHK(h->d_follow.alloc(Fs.size()));
+    HIPCHK(hipMemcpy(h->d_follow, Fs.data(), Fs.size() * sizeof(FollowCfg), hipMemcpyHostToDevice));
     if (classes) {
         h->n_classes = (int)Cs.size();
         HIPCHK(h->d_class_of.alloc_zero(nB));
@@ -368,7 +391,7 @@ extern "C" int eepacc_create(eepacc_handle** out, const eepacc_settings* S, cons
     std::vector<double> Hinv;
     int rc = build_cfg(S, V, Cs[0], Hinv);
     if (rc != EEPACC_OK) return rc;
-    return create_on_device(out, Cs, Hinv, {build_kpi_cfg(S, V)}, false, device, max_batch);
+    return create_on_device(out, Cs, Hinv, {build_kpi_cfg(S, V)}, {build_follow_cfg(S, V)}, false, device, max_batch);
 }
 
 // Every class is checked like the settings of eepacc_create, and against class 0 in what selects the kernel and the launch
@@ -384,6 +407,7 @@ extern "C" int eepacc_create_classes(eepacc_handle** out, const eepacc_settings*
     std::vector<DevCfg> Cs((size_t)n_classes);
     std::vector<double> Hinv, Hk;
     std::vector<KpiCfg> Ks;
+    std::vector<FollowCfg> Fs;
     for (int k = 0; k < n_classes; ++k) {
         const std::string who = "eepacc_create_classes: class " + std::to_string(k) + ": ";
         if (S[k].N_hor != N)
@@ -400,8 +424,9 @@ extern "C" int eepacc_create_classes(eepacc_handle** out, const eepacc_settings*
                 return fail(EEPACC_EINVAL, who + "Tvec[" + std::to_string(j) + "] differs from class 0; the classes of a handle share the time grid");
         Hinv.insert(Hinv.end(), Hk.begin(), Hk.end());
         Ks.push_back(build_kpi_cfg(&S[k], &V[k]));
+        Fs.push_back(build_follow_cfg(&S[k], &V[k]));
     }
-    return create_on_device(out, Cs, Hinv, Ks, true, device, max_batch);
+    return create_on_device(out, Cs, Hinv, Ks, Fs, true, device, max_batch);
 }
 
 extern "C" int eepacc_num_classes(const eepacc_handle* h) { return h && h->n_classes ? h->n_classes : 1; }
@@ -583,6 +608,28 @@ extern "C" int eepacc_kpis(eepacc_handle* h, int B, int n_steps, const double* t
     // stream ordered behind an earlier call's kernel; the host array may be reused when this returns (pageable source)
     HIPCHK(hipMemcpyAsync(h->d_kpi_cut, cutoff_dist_host, (size_t)nc * sizeof(double), hipMemcpyHostToDevice, (hipStream_t)stream));
     HIPCHK(eepacc::launch_kpis(h->d_kpi, h->class_map(), h->d_kpi_cut, B, n_steps, traj, status, kpi, (hipStream_t)stream));
+    return EEPACC_OK;
+}
+
+// Vehicle-following and cost key figures (ABO/Main.m:679-771, RunOpt_ABMPC.m:382-404, RunOpt_FBMPC.m:373-397), per instance, on
+// the device.  Reads the trajectory, the lead traces and the handle's FollowCfg table only: no carried state.  What does not
+// need the handle is checked first.
+extern "C" int eepacc_follow_kpis(eepacc_handle* h, int B, int n_steps, int weights, const double* traj, const int32_t* status,
+                                  const double* s_tv, const double* v_tv, double* fkpi, void* stream) {
+    if (weights != EEPACC_FKPI_W_AB && weights != EEPACC_FKPI_W_FB && weights != EEPACC_FKPI_W_NONE)
+        return fail(EEPACC_EINVAL, "eepacc_follow_kpis: weights = " + std::to_string(weights) + " is none of EEPACC_FKPI_W_AB, _W_FB, _W_NONE");
+    if (n_steps < 1) return fail(EEPACC_EINVAL, "eepacc_follow_kpis: n_steps = " + std::to_string(n_steps) + " must be at least 1");
+    if (!traj) return fail(EEPACC_EINVAL, "eepacc_follow_kpis: traj is NULL");
+    if (!status) return fail(EEPACC_EINVAL, "eepacc_follow_kpis: status is NULL");
+    if (!s_tv) return fail(EEPACC_EINVAL, "eepacc_follow_kpis: s_tv is NULL");
+    if (!v_tv) return fail(EEPACC_EINVAL, "eepacc_follow_kpis: v_tv is NULL");
+    if (!fkpi) return fail(EEPACC_EINVAL, "eepacc_follow_kpis: fkpi is NULL");
+    if (!h) return fail(EEPACC_EINVAL, "eepacc_follow_kpis: NULL handle");
+    if (B < 0 || B > h->max_batch) return fail(EEPACC_EINVAL, "eepacc_follow_kpis: B = " + std::to_string(B) + " is outside [0, max_batch = " + std::to_string(h->max_batch) + "]");
+    if (B == 0) return EEPACC_OK;
+    if (const int rc = classes_ready(h, "eepacc_follow_kpis", B)) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(eepacc::launch_follow_kpis(h->d_follow, h->class_map(), weights, B, n_steps, traj, s_tv, v_tv, fkpi, (hipStream_t)stream));
     return EEPACC_OK;
 }
 

@@ -13,7 +13,7 @@ from typing import Any, Dict, Optional
 
 import numpy as np
 
-from ._abi import (SettingsHolder, SettingsPOD, Vehicle, make_vehicle, pack_classes, OUT, OUT_N, OUT_FIELDS, KPI_N, c_double_p,
+from ._abi import (SettingsHolder, SettingsPOD, Vehicle, make_vehicle, pack_classes, OUT, OUT_N, OUT_FIELDS, KPI_N, FKPI_N, FKPI_WEIGHTS, c_double_p,
                    as_dptr, as_iptr)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -63,6 +63,7 @@ def load_library() -> C.CDLL:
     lib.eepacc_run_tvmpc_host.argtypes = [vp, C.c_int, C.c_int] + [c_double_p] * 3 + [c_double_p, ip]
     lib.eepacc_postprocess.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, dp, vp]
     lib.eepacc_kpis.argtypes = [vp, C.c_int, C.c_int, dp, dp, c_double_p, dp, vp]
+    lib.eepacc_follow_kpis.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, vp]
     lib.eepacc_last_iterations.argtypes = [vp, C.c_int, ip]
     lib.eepacc_fb_step.argtypes = [vp, C.c_int] + [dp] * 10 + [dp, dp, dp, dp, vp]
     lib.eepacc_run_fbmpc.argtypes = [vp, C.c_int, C.c_int] + [dp] * 5 + [dp, dp, vp]
@@ -79,6 +80,7 @@ ABI_SYMBOLS = ["eepacc_last_error", "eepacc_version", "eepacc_sizeof_settings", 
                "eepacc_ab_step", "eepacc_run_abmpc", "eepacc_fb_step", "eepacc_run_fbmpc",
                "eepacc_run_abmpc_host", "eepacc_run_fbmpc_host", "eepacc_bl_step", "eepacc_run_blmpc", "eepacc_run_blmpc_host",
                "eepacc_tv_step", "eepacc_run_tvmpc", "eepacc_run_tvmpc_host", "eepacc_postprocess", "eepacc_kpis",
+               "eepacc_follow_kpis",
                "eepacc_last_iterations", "eepacc_qp_solve_batched", "eepacc_synchronize", "eepacc_build_flags"]
 
 
@@ -257,6 +259,31 @@ class Engine:
         _check(self.lib.eepacc_kpis(self.h, B, n_steps, traj.data_ptr(), status.data_ptr(), as_dptr(cut), kpi.data_ptr(),
                                     self._stream()))
         return kpi
+
+    def follow_kpis(self, traj, status, s_tv, v_tv, weights="ab"):
+        """eepacc_follow_kpis: how every instance kept its distance to the lead (ABO/Main.m:679-771 against the policy of
+        :687) and what every term of the objective cost over the run (the last entries of cost_* of RunOpt_ABMPC.m:382-404 /
+        RunOpt_FBMPC.m:373-397), reduced on the device.  traj [n_steps, OUT_N, B] and status [n_steps, B] as the run_*
+        methods return them, s_tv and v_tv [n_steps, B] as they take them; weights: "ab" (W_AB as RunOpt_ABMPC applies it),
+        "fb" (W_FB) or "none" (raw sums).  Returns the device tensor [FKPI_N, B] (rows: _abi.FKPI_FIELDS, raw SI units);
+        report.follow_table is the same in numpy."""
+        t = self.torch
+        if weights not in FKPI_WEIGHTS:
+            raise ValueError("weights must be one of %s, got %r" % (sorted(FKPI_WEIGHTS), weights))
+        traj = t.as_tensor(traj, dtype=t.float64, device=self.device).contiguous()
+        status = t.as_tensor(status, dtype=t.int32, device=self.device).contiguous()
+        s_tv = t.as_tensor(s_tv, dtype=t.float64, device=self.device).contiguous()
+        v_tv = t.as_tensor(v_tv, dtype=t.float64, device=self.device).contiguous()
+        if traj.dim() != 3 or traj.shape[1] != OUT_N:
+            raise ValueError("follow_kpis needs traj [n_steps, %d, B]" % OUT_N)
+        n_steps, _, B = traj.shape
+        for name, x in (("status", status), ("s_tv", s_tv), ("v_tv", v_tv)):
+            if tuple(x.shape) != (n_steps, B):
+                raise ValueError("follow_kpis needs %s [n_steps, B] = [%d, %d], got %s" % (name, n_steps, B, list(x.shape)))
+        fkpi = t.empty((FKPI_N, B), dtype=t.float64, device=self.device)
+        _check(self.lib.eepacc_follow_kpis(self.h, B, n_steps, FKPI_WEIGHTS[weights], traj.data_ptr(), status.data_ptr(),
+                                           s_tv.data_ptr(), v_tv.data_ptr(), fkpi.data_ptr(), self._stream()))
+        return fkpi
 
     # B3 ------------------------------------------------------------------------------------
     def qp_solve_batched(self, H, g, A, lba=None, uba=None, lbx=None, ubx=None, x0=None):

@@ -4,6 +4,8 @@
 (or a saved solution with the same fields) and returns them as a dict; ``format_report`` renders the
 text block of Main.m for one controller.  ``kpi_table`` is the same for a batch, as a table: the specification of the
 device operator eepacc_kpis (``Engine.kpis``); ``table_to_reports`` and ``summarise_table`` read such a table.
+``follow_table`` is the specification of eepacc_follow_kpis (``Engine.follow_kpis``): the vehicle-following figures of
+Main.m:679-771 and the final cost_* of RunOpt_ABMPC.m:382-404 / RunOpt_FBMPC.m:373-397, per instance.
 Host-side numpy only.
 """
 from __future__ import annotations
@@ -193,9 +195,100 @@ def table_to_reports(table) -> list:
     return out
 
 
+def follow_weights(OPT: Dict[str, Any], weights: str = "ab") -> np.ndarray:
+    """The seven weights [w_P, w_a, w_j, w_v, w_h, w_s, w_f] of follow_table's cost fields, as eepacc_follow_kpis selects
+    them: "ab": W(1..5) of OPTsettings.W_AB with w_f = W(5) and w_P = 0 (RunOpt_ABMPC.m:383-388 -- in the ABO tree W(1) is
+    w_FC, and the reference's cost_a uses it all the same); "fb": W_FB(1..7) (RunOpt_FBMPC.m:373-379); "none": ones, w_P = 0."""
+    if weights == "ab":
+        W = np.asarray(OPT["W_AB"], dtype=np.float64).ravel()
+        return np.array([0.0, W[0], W[1], W[2], W[3], W[4], W[4]])
+    if weights == "fb":
+        return np.asarray(OPT["W_FB"], dtype=np.float64).ravel()[:7].copy()
+    if weights == "none":
+        return np.array([0.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0])
+    raise ValueError("weights must be 'ab', 'fb' or 'none', got %r" % (weights,))
+
+
+def follow_table(s, v, Fm, a, xi_v, xi_h, xi_s, xi_f, s_tv, v_tv, Ts, h_min, tau_min, W, b5, phi) -> np.ndarray:
+    """The vehicle-following and cost key figures of a batch, as a table [FKPI_N, B] (rows: _abi.FKPI_FIELDS) in raw SI
+    units: the specification of eepacc_follow_kpis (include/eepacc.h) in executable form, numpy on the host, serial over the
+    steps with the operator's order of operations.
+
+    s .. xi_f: [n, B] rows of a closed-loop trajectory; s_tv, v_tv: [n, B] the lead traces it was run on (TVlength
+    subtracted, Main.m:88); Ts = Tvec[0]; h_min, tau_min: scalars or [B]; W: the seven weights [w_P, w_a, w_j, w_v, w_h,
+    w_s, w_f] (follow_weights), [7] or [7, B]; b5, phi: the power fit and driveline of cost_P (one class per call).  With
+    the gap h_k = s_tv[k] - s[k], the jerk j_k = (a[k+1] - a[k]) / Ts and a lead sample a k with s_tv[k] < 1e6 (Main.m:288):
+
+        lead_samples       number of lead samples
+        h_min_m            min h_k over the lead samples; +inf if none                               Main.m:692-739
+        h_min_index        the first k that attains it; -1 if none
+        thw_min_s          min h_k / v_k over the lead samples with v_k > 0; +inf if none            :752-764
+        margin_min_m       min (h_k - max(h_min, v_k tau_min)) over the lead samples; +inf if none   :687
+        margin_viol_steps  number of lead samples with that margin < 0
+        ttc_min_s          min h_k / (v_k - v_tv[k]) over the lead samples that close in; +inf if none (not in the reference)
+        xi_h_max           max xi_h[k] over all steps
+        cost_P             w_P sum_{k<=n-2} P_k^2, P = power_surface(b5, Fm, 30/pi v phi); 0 where w_P = 0   RunOpt_FBMPC.m:383
+        cost_a cost_j      w_a sum_{k<=n-2} a_k^2, w_j sum_{k<=n-2} j_k^2                            RunOpt_ABMPC.m:392-393
+        cost_xi_v .. _f    w sum_{k<=n-2} xi[k]                                                      :394-397
+
+    The minima, the maximum and the index are kept by `<` and `>` alone, so the first of equal gaps wins and a NaN is
+    never taken; the sums are added in the order of k (the device adds slice by slice: they differ by rounding)."""
+    from ._abi import FKPI, FKPI_N
+    s, v, Fm, a, xi_v, xi_h, xi_s, xi_f, s_tv, v_tv = [np.asarray(x, dtype=np.float64) for x in (s, v, Fm, a, xi_v, xi_h, xi_s, xi_f, s_tv, v_tv)]
+    n, B = s.shape
+    Ts = float(Ts)
+    h_min = np.broadcast_to(np.asarray(h_min, dtype=np.float64).reshape(-1), (B,))
+    tau_min = np.broadcast_to(np.asarray(tau_min, dtype=np.float64).reshape(-1), (B,))
+    W = np.broadcast_to(np.asarray(W, dtype=np.float64).reshape(7, -1), (7, B))
+    hmin, thw, margin, ttc = [np.full(B, np.inf) for _ in range(4)]
+    ximax = np.full(B, -np.inf)
+    index = np.full(B, -1.0)
+    lead, viol = np.zeros(B), np.zeros(B)
+    sums = np.zeros((7, B))
+    P = power_surface(b5, Fm, 30.0 / np.pi * v * phi) if (W[0] != 0.0).any() else np.zeros((n, B))
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        for k in range(n):
+            ximax = np.where(xi_h[k] > ximax, xi_h[k], ximax)
+            is_lead = s_tv[k] < 1e6
+            h = s_tv[k] - s[k]
+            lead += is_lead
+            take = is_lead & (h < hmin)
+            hmin = np.where(take, h, hmin); index = np.where(take, float(k), index)
+            t = h / v[k]
+            thw = np.where(is_lead & (v[k] > 0.0) & (t < thw), t, thw)
+            vt = v[k] * tau_min
+            m = h - np.where(vt > h_min, vt, h_min)
+            margin = np.where(is_lead & (m < margin), m, margin)
+            viol += is_lead & (m < 0.0)
+            dv = v[k] - v_tv[k]
+            c = h / dv
+            ttc = np.where(is_lead & (dv > 0.0) & (c < ttc), c, ttc)
+            if k + 1 < n:                                      # k = 1:N_sim of the reference, N_sim = n - 1
+                j = (a[k + 1] - a[k]) / Ts
+                sums += np.stack([P[k] * P[k], a[k] * a[k], j * j, xi_v[k], xi_h[k], xi_s[k], xi_f[k]])
+    T = np.zeros((FKPI_N, B))
+    T[FKPI["lead_samples"]] = lead
+    T[FKPI["h_min_m"]] = hmin
+    T[FKPI["h_min_index"]] = index
+    T[FKPI["thw_min_s"]] = thw
+    T[FKPI["margin_min_m"]] = margin
+    T[FKPI["margin_viol_steps"]] = viol
+    T[FKPI["ttc_min_s"]] = ttc
+    T[FKPI["xi_h_max"]] = ximax
+    cost = W * sums
+    cost[0] = np.where(W[0] != 0.0, cost[0], 0.0)
+    T[FKPI["cost_P"]:FKPI["cost_xi_f"] + 1] = cost
+    return T
+
+
 def summarise_table(table, class_of) -> Dict[str, np.ndarray]:
     """Per-class mean, minimum and maximum of every row of a table: {"classes": the class ids that occur, ascending [K],
-    "count" [K], "mean" / "min" / "max" [K, KPI_N]} (rows of the three in the order of _abi.KPI_FIELDS)."""
+    "count" [K], "mean" / "min" / "max" [K, rows]} (rows of the three in the table's order: _abi.KPI_FIELDS for a table
+    of kpi_table / Engine.kpis, _abi.FKPI_FIELDS for one of follow_table / Engine.follow_kpis).
+
+    A table of follow_table holds +inf where an instance has no sample to take a minimum over (no lead, never closing).
+    Such entries are kept as they are: the class's "max", and its "mean", are then +inf (never NaN: the fields that can
+    be infinite are +inf only), and "min" is taken over the class's other instances.  Read "lead_samples" beside them."""
     T = np.asarray(table.cpu() if hasattr(table, "cpu") else table, dtype=np.float64)
     class_of = np.asarray(class_of).reshape(-1)
     if class_of.size != T.shape[1]:

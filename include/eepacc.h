@@ -361,6 +361,61 @@ enum {
 int  eepacc_kpis(eepacc_handle* h, int B, int n_steps, const double* traj, const int32_t* status,
                  const double* cutoff_dist_host, double* kpi, void* stream);
 
+/* Vehicle-following and cost key figures of a closed-loop run, per instance, on the device: how the ego kept its distance
+ * to the lead (the headway distance s_tv - s_opt and headway time (s_tv - s_opt)./v_opt of ABO/Main.m:679-771 against the
+ * minimum-headway policy max(h_min, v tau_min) of :687) and what every term of the objective cost over the run (the last
+ * entries of the cumulative series cost_a .. cost_xi_f of ABO/RunOpt_ABMPC.m:382-404 and cost_P of
+ * ABO/RunOpt_FBMPC.m:373-397, which Main.m:1043-1151 plots).  Inputs, device: traj [n_steps][EEPACC_OUT_N][B] and status
+ * [n_steps][B] as every eepacc_run_* entry point writes them, s_tv and v_tv [n_steps][B] as it reads them.  Rows S, V, A,
+ * XI_V, XI_H, XI_S, XI_F of traj are read, row FM where the weight of COST_P is not zero; status is not read.  Output,
+ * device: fkpi [EEPACC_FKPI_N][B], batch-major, raw SI units.  With n = n_steps, Ts = Tvec[0], the gap h_k = s_tv[k] - s[k],
+ * the jerk j_k = (a[k+1] - a[k]) / Ts, and a "lead sample" a k with s_tv[k] < 1e6 (the reference's "no lead" is a lead
+ * at 1e6 m or more, Main.m:288; a NaN is no lead sample): */
+enum {
+    EEPACC_FKPI_LEAD_SAMPLES = 0,  /* number of lead samples                                                              */
+    EEPACC_FKPI_H_MIN_M,           /* min h_k over the lead samples; +inf if there is none                                */
+    EEPACC_FKPI_H_MIN_INDEX,       /* the first k that attains it; -1.0 if there is none                                  */
+    EEPACC_FKPI_THW_MIN_S,         /* Main.m:752-764  min h_k / v_k over the lead samples with v_k > 0; +inf if none      */
+    EEPACC_FKPI_MARGIN_MIN_M,      /* Main.m:687  min (h_k - max(h_min, v_k tau_min)) over the lead samples; +inf if none */
+    EEPACC_FKPI_MARGIN_VIOL_STEPS, /* number of lead samples with that margin < 0                                         */
+    EEPACC_FKPI_TTC_MIN_S,         /* time to collision: min h_k / (v_k - v_tv[k]) over the lead samples with             */
+                                   /* v_k - v_tv[k] > 0; +inf if none.  Not in the reference.                             */
+    EEPACC_FKPI_XI_H_MAX,          /* max_k xi_h[k] over all n steps                                                      */
+    EEPACC_FKPI_COST_P,            /* RunOpt_FBMPC.m:383  w_P sum_{k<=n-2} P_k^2, P_k the fifth-order surface of          */
+                                   /* eepacc_kpis; 0 where w_P = 0, without evaluating the surface                        */
+    EEPACC_FKPI_COST_A,            /* RunOpt_ABMPC.m:392  w_a sum_{k<=n-2} a_k^2                                          */
+    EEPACC_FKPI_COST_J,            /* :393  w_j sum_{k<=n-2} j_k^2, all n-1 jerks                                         */
+    EEPACC_FKPI_COST_XI_V,         /* :394  w_v sum_{k<=n-2} xi_v[k]                                                      */
+    EEPACC_FKPI_COST_XI_H,         /* :395  w_h sum_{k<=n-2} xi_h[k]                                                      */
+    EEPACC_FKPI_COST_XI_S,         /* :396  w_s sum_{k<=n-2} xi_s[k]                                                      */
+    EEPACC_FKPI_COST_XI_F,         /* :397  w_f sum_{k<=n-2} xi_f[k]                                                      */
+    EEPACC_FKPI_N
+};
+/* The cost sums run over k = 1:N_sim of the reference, N_sim = n - 1: the last sample is in none of them, and n_steps = 1
+ * gives seven zeros.  The minima, the maximum and the index come from comparisons alone (`<`, `>`; the first of equal gaps
+ * wins), v_k tau_min, h_k / v_k and a_k a_k are each rounded once: these fields and the two counts are exact.
+ *
+ * A handle of eepacc_create serves eepacc_run_abmpc and eepacc_run_fbmpc alike, so `weights` says whose weights apply: */
+enum {
+    EEPACC_FKPI_W_AB = 0,   /* W(1..5) of RunOpt_ABMPC.m:383-388 for w_a, w_j, w_v, w_h, w_s and w_f = W(5) again; COST_P = 0.   */
+                            /* W is OPTsettings.W_AB as the reference's user wrote it: with ab_fuel_term = 0 (ORIG, six entries, */
+                            /* stored here behind a leading 0) that is W_AB[1..5] of eepacc_settings, otherwise (ABO, seven      */
+                            /* entries) W_AB[0..4], where W(1) is w_FC -- the reference's cost_a uses it all the same, so does   */
+                            /* this                                                                                              */
+    EEPACC_FKPI_W_FB,       /* W_FB[0..6] = w_P, w_a, w_j, w_v, w_h, w_s, w_f (RunOpt_FBMPC.m:373-379)                           */
+    EEPACC_FKPI_W_NONE      /* all weights 1: the raw sums, and COST_P = 0 (RunOpt_BLMPC and RunOpt_TVMPC define no cost_*)      */
+};
+/* Works on every kind of handle; h_min, tau_min, the weights and the power surface come from a table of the operator's own
+ * with one entry per class, built at creation.  On a handle of eepacc_create_classes every instance is evaluated with the
+ * constants of its class (eepacc_set_classes must have been called for this B).  Asynchronous on stream; reads and writes
+ * no carried state of the handle.  The geometry is that of eepacc_kpis (EEPACC_KPI_WAVES, EEPACC_KPI_MIN_SLICE), the
+ * slices are joined by one wave in slice order without atomics: a result depends on n_steps and on nothing else, not on B,
+ * not on timing, not on the kind of handle.  EEPACC_EINVAL, with a message that names the argument: another value of
+ * weights, n_steps < 1, a NULL buffer, B < 0 or B > max_batch, a class map that is not set or was set for another B.
+ * B = 0 returns EEPACC_OK.  Throughput: not measured. */
+int  eepacc_follow_kpis(eepacc_handle* h, int B, int n_steps, int weights, const double* traj, const int32_t* status,
+                        const double* s_tv, const double* v_tv, double* fkpi, void* stream);
+
 /* Solver statistics of the last launch, device [B]: active-set iterations used. */
 int  eepacc_last_iterations(eepacc_handle* h, int B, int32_t* iters_host);
 
