@@ -678,18 +678,26 @@ static int qp_workspace(eepacc_handle* h, int grid, int nV) {
     return EEPACC_OK;
 }
 
-extern "C" int eepacc_qp_solve_batched(eepacc_handle* h, int B, int nV, int nC, const double* H, const double* g,
-                                       const double* A, const double* lba, const double* uba, const double* lbx,
-                                       const double* ubx, const double* x0, double* x, double* cost,
-                                       int32_t* status, void* stream) {
+// both entry points of the operator; dual = nullptr: eepacc_qp_solve_batched
+struct QpDual {
+    const int8_t *ws0_a, *ws0_x;
+    double *lam_a, *lam_x;
+    int8_t *ws_a, *ws_x;
+    int32_t* iters;
+};
+
+static int qp_solve(eepacc_handle* h, const char* name, int B, int nV, int nC, const double* H, const double* g,
+                    const double* A, const double* lba, const double* uba, const double* lbx, const double* ubx,
+                    const double* x0, double* x, double* cost, int32_t* status, const QpDual* dual, void* stream) {
+    const std::string who = std::string(name) + ": ";
     if (!h) return fail(EEPACC_EINVAL, "NULL handle");
-    if (const int rc = not_classes(h, "eepacc_qp_solve_batched")) return rc;
-    if (B < 0 || nV < 1 || nC < 0) return fail(EEPACC_EINVAL, "eepacc_qp_solve_batched: bad sizes");
+    if (const int rc = not_classes(h, name)) return rc;
+    if (B < 0 || nV < 1 || nC < 0) return fail(EEPACC_EINVAL, who + "bad sizes");
     if (B == 0) return EEPACC_OK;
     if (nV > EEPACC_QP_MAX_NV || nC > EEPACC_QP_MAX_NC)
-        return fail(EEPACC_EINVAL, "eepacc_qp_solve_batched: nV/nC above EEPACC_QP_MAX_NV/NC");
-    if (!H || !g || !x || (nC > 0 && !A)) return fail(EEPACC_EINVAL, "eepacc_qp_solve_batched: NULL buffer");
-    if (eepacc_qp_dense_lds_bytes(nV, nC) > 160 * 1024) return fail(EEPACC_EINVAL, "eepacc_qp_solve_batched: problem does not fit LDS");
+        return fail(EEPACC_EINVAL, who + "nV/nC above EEPACC_QP_MAX_NV/NC");
+    if (!H || !g || !x || (nC > 0 && !A)) return fail(EEPACC_EINVAL, who + "NULL buffer");
+    if (eepacc_qp_dense_lds_bytes(nV, nC) > 160 * 1024) return fail(EEPACC_EINVAL, who + "problem does not fit LDS");
     HIPCHK(hipSetDevice(h->device));
     int grid = qp_grid(h, B);
     int rc = qp_workspace(h, grid, nV);
@@ -699,9 +707,29 @@ extern "C" int eepacc_qp_solve_batched(eepacc_handle* h, int B, int nV, int nC, 
     a.x0 = x0; a.x = x; a.cost = cost; a.status = status; a.iters = (B <= h->max_batch) ? h->d_iters : nullptr;
     a.ws = h->d_qp_ws; a.ws_stride = eepacc_qp_dense_ws_doubles(nV); a.rho_rel = 0.0; a.max_prox = 0;
     a.counter = h->d_qp_counter; a.rho_k = nullptr;
+    if (dual) {
+        a.ws0_a = dual->ws0_a; a.ws0_x = dual->ws0_x; a.lam_a = dual->lam_a; a.lam_x = dual->lam_x;
+        a.ws_a = dual->ws_a; a.ws_x = dual->ws_x; a.iters = dual->iters;
+    }
     HIPCHK(hipMemsetAsync(h->d_qp_counter, 0, sizeof(int), (hipStream_t)stream));
-    HIPCHK(eepacc_qp_dense_launch(a, grid, (hipStream_t)stream));
+    HIPCHK(dual ? eepacc_qp_dense_launch_dual(a, grid, (hipStream_t)stream) : eepacc_qp_dense_launch(a, grid, (hipStream_t)stream));
     return EEPACC_OK;
+}
+
+extern "C" int eepacc_qp_solve_batched(eepacc_handle* h, int B, int nV, int nC, const double* H, const double* g,
+                                       const double* A, const double* lba, const double* uba, const double* lbx,
+                                       const double* ubx, const double* x0, double* x, double* cost,
+                                       int32_t* status, void* stream) {
+    return qp_solve(h, "eepacc_qp_solve_batched", B, nV, nC, H, g, A, lba, uba, lbx, ubx, x0, x, cost, status, nullptr, stream);
+}
+
+extern "C" int eepacc_qp_solve_batched_dual(eepacc_handle* h, int B, int nV, int nC, const double* H, const double* g,
+                                            const double* A, const double* lba, const double* uba, const double* lbx,
+                                            const double* ubx, const double* x0, const int8_t* ws0_a, const int8_t* ws0_x,
+                                            double* x, double* cost, int32_t* status, double* lam_a, double* lam_x,
+                                            int8_t* ws_a, int8_t* ws_x, int32_t* iters, void* stream) {
+    const QpDual d = {ws0_a, ws0_x, lam_a, lam_x, ws_a, ws_x, iters};
+    return qp_solve(h, "eepacc_qp_solve_batched_dual", B, nV, nC, H, g, A, lba, uba, lbx, ubx, x0, x, cost, status, &d, stream);
 }
 
 // FBMPC (ABO/RunOpt_FBMPC.m:161-331): build kernel -> dense QP operator -> extraction, per step.

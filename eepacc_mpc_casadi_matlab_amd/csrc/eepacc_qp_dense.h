@@ -17,10 +17,16 @@ struct eepacc_qp_args {
     size_t ws_stride;
     double rho_rel;        // <= 0: 1e-7
     int max_prox;          // <= 0: 8
+    // read and written by the dual instantiation only (eepacc_qp_dense_launch_dual); each may be NULL
+    const int8_t *ws0_a = nullptr, *ws0_x = nullptr;   // [B][nC], [B][nV] warm start: -1 lower side, +1 upper side, else none
+    double *lam_a = nullptr, *lam_x = nullptr;         // [B][nC], [B][nV] multipliers, CasADi's sign
+    int8_t *ws_a = nullptr, *ws_x = nullptr;           // [B][nC], [B][nV] final working set, coded like ws0
 };
 
 size_t eepacc_qp_dense_ws_doubles(int nV);
 size_t eepacc_qp_dense_lds_bytes(int nV, int nC);
 hipError_t eepacc_qp_dense_launch(const eepacc_qp_args& a, int grid, hipStream_t stream);
+// the instantiation with multipliers, working set and warm start (same workspace, same LDS)
+hipError_t eepacc_qp_dense_launch_dual(const eepacc_qp_args& a, int grid, hipStream_t stream);
 
 #endif

@@ -872,6 +872,43 @@ done:
     return status;
 }
 
+// Warm start of the dual instantiation: the requested sides (wa[i], wx[j] = -1 lower, +1 upper; anything else, and a
+// side without a finite bound, is no request) are installed in ascending order of the one-sided list on the cold
+// factors (JT = J0T, empty R), one reflector each as in the iteration; a dependent row is skipped, n rows end it.
+// Leaves S.act, S.is_act and (JT, R, T) as gi_solve(warm) expects them from a previous round.  Returns q (uniform).
+__device__ int warm_install(const Prob& P, const Ws& W, const Lds& S, const int8_t* wa, const int8_t* wx) {
+    const int n = P.n;
+    for (int c = threadIdx.x; c < P.m1; c += QT) S.is_act[c] = 0;
+    for (int r = wave_id(); r < n; r += QW) {
+        const double* src = W.J0T + (size_t)r * n;
+        double* dst = W.JT + (size_t)r * n;
+        for (int k = lane_id(); k < n; k += 64) dst[k] = src[k];
+    }
+    __syncthreads();
+    int q = 0;
+    for (int i = 0; i < P.nC + n && q < n; ++i) {
+        const int v = i < P.nC ? (wa ? (int)wa[i] : 0) : (wx ? (int)wx[i - P.nC] : 0);
+        if (v != 1 && v != -1) continue;
+        const int c = 2 * i + (v > 0 ? 1 : 0);
+        int row; double sgn, b;
+        if (!os_get(P, c, row, sgn, b)) continue;
+        get_normal(P, c, S.np);
+        rowdot(W.JT, n, S.np, S.d);
+        for (int j = threadIdx.x; j < q; j += QT) {          // r = R^-1 d1 = T d1, what gi_add extends T with
+            double acc = 0.0;
+            for (int k = j; k < q; ++k) acc += W.T[(size_t)k * n + j] * S.d[k];
+            S.r[j] = acc;
+        }
+        __syncthreads();
+        if (gi_add(W, S, n, q) == 0) {
+            if (threadIdx.x == 0) { S.act[q] = c; S.is_act[c] = 1; }
+            ++q;
+        }
+        __syncthreads();
+    }
+    return q;
+}
+
 __device__ void carve(Lds& S, unsigned char* base, int n, int nC) {
     double* p = (double*)base;
     const int n2 = 2 * n + 2;
@@ -888,7 +925,10 @@ __device__ void carve(Lds& S, unsigned char* base, int n, int nC) {
     S.is_act = (unsigned char*)ip;
 }
 
-__global__ void __launch_bounds__(QT, 2) k_qp_dense(eepacc_qp_args a) {     // two workgroups per CU: 256 VGPRs, no scratch
+// DUAL: also the multipliers and the working set of the accepted point, the iteration from a given working set
+// (eepacc_qp_solve_batched_dual).  Everything it adds sits behind `if constexpr (DUAL)`.
+template <bool DUAL>
+__global__ void __launch_bounds__(QT, 2) k_qp_dense(eepacc_qp_args a) {     // two workgroups per CU
     extern __shared__ __align__(16) unsigned char smem[];
     const int n = a.nV, nC = a.nC;
     Lds S;
@@ -973,6 +1013,7 @@ __global__ void __launch_bounds__(QT, 2) k_qp_dense(eepacc_qp_args a) {     // t
             if (a.rho_k && threadIdx.x == 0) a.rho_k[b] = kfound;
         }
         int status = 1, tot_iters = 0, q = 0;
+        int lam_ok = 0;        // DUAL: S.up holds the multipliers of a verified KKT solve on S.act[0..q)
         if (chol_ok) {
             tri_inverse(L, W.J0T, n, S);
             TOC(t_ch, 8);
@@ -1017,12 +1058,16 @@ __global__ void __launch_bounds__(QT, 2) k_qp_dense(eepacc_qp_args a) {     // t
             n_crash = S.ired[4];
             for (int i = threadIdx.x; i < n; i += QT) S.xc[i] = a.x0 ? a.x0[(size_t)b * n + i] : 0.0;
             __syncthreads();
+            if constexpr (DUAL) {
+                if (a.ws0_a || a.ws0_x)
+                    q = warm_install(P, W, S, a.ws0_a ? a.ws0_a + (size_t)b * nC : nullptr, a.ws0_x ? a.ws0_x + (size_t)b * n : nullptr);
+            }
             for (int it = 0; it < max_prox; ++it) {
                 for (int i = threadIdx.x; i < n; i += QT) S.gr[i] = P.g[i] - rho * S.xc[i];
                 __syncthreads();
                 int iters = 0;
                 TIC(t_gi);
-                int rc = gi_solve(P, W, S, rho, n_crash, q, iters, 20 * (n + P.m1) + 100, it > 0);
+                int rc = gi_solve(P, W, S, rho, n_crash, q, iters, 20 * (n + P.m1) + 100, it > 0 || (DUAL && q > 0));
                 TOC(t_gi, 10);
                 if (blockIdx.x == 0 && threadIdx.x == 0) { TOC(t_gi, 15); }
                 tot_iters += iters;
@@ -1038,6 +1083,7 @@ __global__ void __launch_bounds__(QT, 2) k_qp_dense(eepacc_qp_args a) {     // t
                     for (int i = threadIdx.x; i < n; i += QT) S.x[i] = S.xp[i];
                     __syncthreads();
                     status = 0;
+                    lam_ok = 1;
                     break;
                 }
                 // Degenerate optimal face (singular KKT matrix, e.g. the FB force split): the proximal
@@ -1065,6 +1111,7 @@ __global__ void __launch_bounds__(QT, 2) k_qp_dense(eepacc_qp_args a) {     // t
                         for (int i = threadIdx.x; i < n; i += QT) S.x[i] = S.xp[i];
                         __syncthreads();
                         status = 0;
+                        lam_ok = 1;
                         break;
                     }
                 }
@@ -1076,7 +1123,17 @@ __global__ void __launch_bounds__(QT, 2) k_qp_dense(eepacc_qp_args a) {     // t
                 double dx = block_sum(pdx, S), nx = block_sum(pnx, S);
                 for (int i = threadIdx.x; i < n; i += QT) S.xc[i] = S.x[i];
                 __syncthreads();
-                if (it > 0 && sqrt(dx) <= 1e-13 * (1.0 + sqrt(nx))) { status = 0; break; }
+                if (it > 0 && sqrt(dx) <= 1e-13 * (1.0 + sqrt(nx))) {
+                    status = 0;
+                    if constexpr (DUAL) {
+                        // the stalled proximal step has no verified solve behind it: the multipliers of the working set
+                        // for the problem itself (x stays the proximal point).  A singular system, or multipliers that miss
+                        // stationarity or sign at the threshold of the other two exits, leave them NaN.
+                        double kk3[3];
+                        lam_ok = kkt_solve(P, W, S, 0.0, P.g, S.act, q, S.xp, S.up, kk3) == 0 && kk3[0] < 1e-9 && kk3[2] < 1e-9;
+                    }
+                    break;
+                }
             }
         } else {
             for (int i = threadIdx.x; i < n; i += QT) S.x[i] = 0.0;
@@ -1095,6 +1152,34 @@ __global__ void __launch_bounds__(QT, 2) k_qp_dense(eepacc_qp_args a) {     // t
             if (a.cost) a.cost[b] = cost;
             if (a.status) a.status[b] = status;
             if (a.iters) a.iters[b] = tot_iters;
+        }
+        if constexpr (DUAL) {
+            // CasADi's sign: Hs x + g + A' lam_a + lam_x = 0.  A working-set row sgn * (row) >= b with multiplier u >= 0
+            // enters stationarity as -sgn u, so lam = -sgn u: <= 0 on a lower side, >= 0 on an upper side, exactly 0
+            // elsewhere.  A multiplier the verification let pass below zero (by less than 1e-9 relative) is returned as 0.
+            // Staged in LDS (S.ax for the rows, S.rhs for the variables), then one vector store per entry.
+            const bool ok = status == 0;
+            const double fill = (ok && lam_ok) ? 0.0 : NAN;
+            __syncthreads();
+            for (int i = threadIdx.x; i < nC; i += QT) S.ax[i] = fill;
+            for (int j = threadIdx.x; j < n; j += QT) S.rhs[j] = fill;
+            __syncthreads();
+            if (ok && lam_ok)
+                for (int c = threadIdx.x; c < q; c += QT) {
+                    const int id = S.act[c];
+                    const double u = S.up[c];
+                    const double lam = u > 0.0 ? ((id & 1) ? u : -u) : 0.0;
+                    if (id < 2 * nC) S.ax[id >> 1] = lam; else S.rhs[(id - 2 * nC) >> 1] = lam;
+                }
+            __syncthreads();
+            for (int i = threadIdx.x; i < nC; i += QT) {
+                if (a.lam_a) a.lam_a[(size_t)b * nC + i] = S.ax[i];
+                if (a.ws_a) a.ws_a[(size_t)b * nC + i] = !ok ? 0 : S.is_act[2 * i] ? -1 : S.is_act[2 * i + 1] ? 1 : 0;
+            }
+            for (int j = threadIdx.x; j < n; j += QT) {
+                if (a.lam_x) a.lam_x[(size_t)b * n + j] = S.rhs[j];
+                if (a.ws_x) a.ws_x[(size_t)b * n + j] = !ok ? 0 : S.is_act[2 * (nC + j)] ? -1 : S.is_act[2 * (nC + j) + 1] ? 1 : 0;
+            }
         }
     }
 }
@@ -1123,10 +1208,14 @@ extern "C" int eepacc_debug_qp_prof(long long* out, int reset) {
 }
 #endif
 
-hipError_t eepacc_qp_dense_launch(const eepacc_qp_args& a, int grid, hipStream_t stream) {
+template <bool DUAL>
+static hipError_t launch(const eepacc_qp_args& a, int grid, hipStream_t stream) {
     size_t lds = eepacc_qp_dense_lds_bytes(a.nV, a.nC);
-    hipError_t e = hipFuncSetAttribute((const void*)k_qp_dense, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute((const void*)k_qp_dense<DUAL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_qp_dense, dim3(grid), dim3(QT), lds, stream, a);
+    hipLaunchKernelGGL(k_qp_dense<DUAL>, dim3(grid), dim3(QT), lds, stream, a);
     return hipGetLastError();
 }
+
+hipError_t eepacc_qp_dense_launch(const eepacc_qp_args& a, int grid, hipStream_t stream) { return launch<false>(a, grid, stream); }
+hipError_t eepacc_qp_dense_launch_dual(const eepacc_qp_args& a, int grid, hipStream_t stream) { return launch<true>(a, grid, stream); }

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Any, Dict, Optional
+from typing import Any, Dict, NamedTuple, Optional
 
 import numpy as np
 
@@ -69,6 +69,7 @@ def load_library() -> C.CDLL:
     lib.eepacc_run_fbmpc.argtypes = [vp, C.c_int, C.c_int] + [dp] * 5 + [dp, dp, vp]
     lib.eepacc_run_fbmpc_host.argtypes = [vp, C.c_int, C.c_int] + [c_double_p] * 5 + [c_double_p, ip]
     lib.eepacc_qp_solve_batched.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [dp] * 8 + [dp, dp, dp, vp]
+    lib.eepacc_qp_solve_batched_dual.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [dp] * 8 + [dp, dp] + [dp] * 3 + [dp] * 5 + [vp]
     lib.eepacc_synchronize.argtypes = [vp, vp]
     lib.eepacc_build_flags.restype = C.c_char_p
     _lib = lib
@@ -81,12 +82,28 @@ ABI_SYMBOLS = ["eepacc_last_error", "eepacc_version", "eepacc_sizeof_settings", 
                "eepacc_run_abmpc_host", "eepacc_run_fbmpc_host", "eepacc_bl_step", "eepacc_run_blmpc", "eepacc_run_blmpc_host",
                "eepacc_tv_step", "eepacc_run_tvmpc", "eepacc_run_tvmpc_host", "eepacc_postprocess", "eepacc_kpis",
                "eepacc_follow_kpis",
-               "eepacc_last_iterations", "eepacc_qp_solve_batched", "eepacc_synchronize", "eepacc_build_flags"]
+               "eepacc_last_iterations", "eepacc_qp_solve_batched", "eepacc_qp_solve_batched_dual", "eepacc_synchronize", "eepacc_build_flags"]
+
+
+def _ptr(v):
+    return None if v is None else v.data_ptr()
 
 
 def _check(rc: int):
     if rc != 0:
         raise EepaccError(f"libeepacc error {rc}: {load_library().eepacc_last_error().decode()}")
+
+
+class QpDualResult(NamedTuple):
+    """What Engine.qp_solve_batched_dual returns (device tensors); ws0 = (r.ws_a, r.ws_x) warm-starts the next call."""
+    x: Any
+    cost: Any
+    status: Any
+    lam_a: Any
+    lam_x: Any
+    ws_a: Any
+    ws_x: Any
+    iters: Any
 
 
 class Engine:
@@ -286,11 +303,9 @@ class Engine:
         return fkpi
 
     # B3 ------------------------------------------------------------------------------------
-    def qp_solve_batched(self, H, g, A, lba=None, uba=None, lbx=None, ubx=None, x0=None):
-        """sol = QPsolver('h',H,'g',g,'a',A,'lba',..,'uba',..,'lbx',..,'ubx',..) (ABO/RunOpt_ABMPC.m:252)
-        for a batch.  H [B,nV,nV], g [B,nV], A [B,nC,nV] (row-major rows as in numpy; transposed
-        here to the column-major layout of the C-ABI), bounds [B,nC] / [B,nV] or None.
-        Returns x [B,nV], cost [B], status [B] as device tensors."""
+    def _qp_inputs(self, H, g, A, lba, uba, lbx, ubx, x0):
+        """Device tensors of the dense QP operator's inputs in the layout of the C-ABI: (B, nV, nC, [H, g, A, lba, uba, lbx,
+        ubx, x0]) with A transposed to column-major and absent bound arrays / x0 as None."""
         t = self.torch
         f64 = dict(dtype=t.float64, device=self.device)
         H = t.as_tensor(H, **f64).contiguous()
@@ -300,15 +315,53 @@ class Engine:
         nC = A.shape[1]
         A_cm = A.transpose(1, 2).contiguous()          # [B][nV][nC] = column-major nC x nV
         opt = lambda v, n: None if v is None else self._d(t.as_tensor(v, **f64).reshape(-1), B * n)
-        lba, uba, lbx, ubx, x0 = opt(lba, nC), opt(uba, nC), opt(lbx, nV), opt(ubx, nV), opt(x0, nV)
-        ptr = lambda v: None if v is None else v.data_ptr()
+        return B, nV, nC, [H, g, A_cm, opt(lba, nC), opt(uba, nC), opt(lbx, nV), opt(ubx, nV), opt(x0, nV)]
+
+    def qp_solve_batched(self, H, g, A, lba=None, uba=None, lbx=None, ubx=None, x0=None):
+        """sol = QPsolver('h',H,'g',g,'a',A,'lba',..,'uba',..,'lbx',..,'ubx',..) (ABO/RunOpt_ABMPC.m:252)
+        for a batch.  H [B,nV,nV], g [B,nV], A [B,nC,nV] (row-major rows as in numpy; transposed
+        here to the column-major layout of the C-ABI), bounds [B,nC] / [B,nV] or None.
+        Returns x [B,nV], cost [B], status [B] as device tensors."""
+        t = self.torch
+        f64 = dict(dtype=t.float64, device=self.device)
+        B, nV, nC, ins = self._qp_inputs(H, g, A, lba, uba, lbx, ubx, x0)
         x = t.empty((B, nV), **f64)
         cost = t.empty((B,), **f64)
         status = t.empty((B,), dtype=t.int32, device=self.device)
-        _check(self.lib.eepacc_qp_solve_batched(self.h, B, nV, nC, H.data_ptr(), g.data_ptr(), A_cm.data_ptr(),
-                                                ptr(lba), ptr(uba), ptr(lbx), ptr(ubx), ptr(x0), x.data_ptr(),
+        _check(self.lib.eepacc_qp_solve_batched(self.h, B, nV, nC, *[_ptr(v) for v in ins], x.data_ptr(),
                                                 cost.data_ptr(), status.data_ptr(), self._stream()))
         return x, cost, status
+
+    def qp_solve_batched_dual(self, H, g, A, lba=None, uba=None, lbx=None, ubx=None, x0=None, ws0=None):
+        """eepacc_qp_solve_batched_dual: qp_solve_batched with the other outputs of the conic call and a warm start.
+        Arguments as qp_solve_batched; ws0 = (ws_a, ws_x) as an earlier call returned them ([B,nC], [B,nV] int8: -1 lower
+        side, +1 upper side, 0 none; either may be None) or None for a cold start.  Returns a QpDualResult with x [B,nV],
+        cost [B], status [B], lam_a [B,nC], lam_x [B,nV] (CasADi's sign: Hs x + g + A'lam_a + lam_x = 0, <= 0 on a lower
+        side, >= 0 on an upper side; NaN where status != 0), ws_a [B,nC], ws_x [B,nV] (int8) and iters [B] (int32), all
+        device tensors."""
+        t = self.torch
+        f64 = dict(dtype=t.float64, device=self.device)
+        B, nV, nC, ins = self._qp_inputs(H, g, A, lba, uba, lbx, ubx, x0)
+
+        def side(v, n):
+            if v is None:
+                return None
+            v = t.as_tensor(v, dtype=t.int8, device=self.device).contiguous()
+            if v.numel() != B * n:
+                raise ValueError(f"ws0 needs {B * n} entries, got {v.numel()}")
+            return v
+        w0a, w0x = (None, None) if ws0 is None else (side(ws0[0], nC), side(ws0[1], nV))
+        r = QpDualResult(x=t.empty((B, nV), **f64), cost=t.empty((B,), **f64),
+                         status=t.empty((B,), dtype=t.int32, device=self.device),
+                         lam_a=t.empty((B, nC), **f64), lam_x=t.empty((B, nV), **f64),
+                         ws_a=t.empty((B, nC), dtype=t.int8, device=self.device),
+                         ws_x=t.empty((B, nV), dtype=t.int8, device=self.device),
+                         iters=t.empty((B,), dtype=t.int32, device=self.device))
+        _check(self.lib.eepacc_qp_solve_batched_dual(self.h, B, nV, nC, *[_ptr(v) for v in ins], _ptr(w0a), _ptr(w0x),
+                                                     r.x.data_ptr(), r.cost.data_ptr(), r.status.data_ptr(),
+                                                     r.lam_a.data_ptr(), r.lam_x.data_ptr(), r.ws_a.data_ptr(),
+                                                     r.ws_x.data_ptr(), r.iters.data_ptr(), self._stream()))
+        return r
 
     def synchronize(self):
         """Wait for the engine's stream; raises if a closed-loop launch flagged a device-side failure."""

@@ -246,6 +246,38 @@ int  eepacc_qp_solve_batched(eepacc_handle* h, int B, int nV, int nC,
                              const double* lbx, const double* ubx, const double* x0,
                              double* x, double* cost, int32_t* status, void* stream);
 
+/* The same operator with the remaining outputs of the conic call (lam_a, lam_x: CAS/include/casadi/core/conic.hpp:199-208),
+ * the final working set, and a warm start from one.  Layout, bound conventions, limits and refusals as above; x, cost and
+ * status are those of eepacc_qp_solve_batched on the same inputs when no warm start is given.
+ * lam_a [B][nC], lam_x [B][nV] (each may be NULL), CasADi's sign:  Hs x + g + A' lam_a + lam_x = 0 with Hs = (H+H')/2,
+ * lam <= 0 where the lower side holds, lam >= 0 where the upper side holds, exactly 0.0 outside the final working set.
+ * They are the multipliers of the verified KKT solve that accepted x; one that the verification let pass on the wrong
+ * side of zero (by less than 1e-9 relative) is returned as 0.
+ * ws_a [B][nC], ws_x [B][nV] (each may be NULL): -1 lower side in the final working set, +1 upper side, 0 neither; an
+ * equality (lb == ub) shows the side the solver holds.  Where status != 0: lam_* are NaN and ws_* are 0.  Where the
+ * proximal iteration ended by standing still (status 0 without a verified solve; x is the proximal point, feasible to
+ * the iteration's tolerance), the multipliers come from one more exact solve on the working set.  They are stationary
+ * and of the right sign to 1e-9 AT THAT SOLVE'S POINT, which is not the returned x and need not coincide with it: that
+ * solve had just missed acceptance in the same round.  They are NaN (status stays 0, ws_* still name the working set)
+ * if the system is singular or its multipliers miss stationarity or sign at 1e-9.  x and status are unaffected.
+ * ws0_a [B][nC], ws0_x [B][nV], each may be NULL (both NULL, or all entries 0 for an instance: cold start): the sides
+ * to start from, coded like ws_*.  Ignored per entry: any other value, a side without a finite bound, rows that depend
+ * on the ones before them, everything beyond nV installed rows.  The set is kept only if all its multipliers are
+ * non-negative for this problem, otherwise the solve starts cold; iteration, exact solve and verification are those of
+ * the cold solve, so a status 0 means the same with and without a warm start.  There is no second attempt: a kept set
+ * that is badly conditioned (dependence is refused only at 1e-14) can end an instance with status 1 that a cold solve
+ * verifies -- a caller who needs the cold solve's status repeats the instances with status != 0 without ws0.
+ * iters [B] (device, may be NULL): working-set iterations of the solve.  eepacc_last_iterations is not updated by this
+ * entry point: it keeps the figures of the last call that wrote them. */
+int  eepacc_qp_solve_batched_dual(eepacc_handle* h, int B, int nV, int nC,
+                                  const double* H, const double* g, const double* A,
+                                  const double* lba, const double* uba,
+                                  const double* lbx, const double* ubx, const double* x0,
+                                  const int8_t* ws0_a, const int8_t* ws0_x,
+                                  double* x, double* cost, int32_t* status,
+                                  double* lam_a, double* lam_x, int8_t* ws_a, int8_t* ws_x,
+                                  int32_t* iters, void* stream);
+
 /* Same two operators for the force-based MPC (ABO/RunOpt_FBMPC.m:161-331).  v_prev, Fm_prev,
  * Fb_prev are the previous step's state/controls (ABO/RunOpt_FBMPC.m:188-191). */
 int  eepacc_fb_step(eepacc_handle* h, int B,
