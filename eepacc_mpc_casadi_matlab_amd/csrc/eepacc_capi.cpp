@@ -732,6 +732,33 @@ extern "C" int eepacc_qp_solve_batched_dual(eepacc_handle* h, int B, int nV, int
     return qp_solve(h, "eepacc_qp_solve_batched_dual", B, nV, nC, H, g, A, lba, uba, lbx, ubx, x0, x, cost, status, &d, stream);
 }
 
+extern "C" int eepacc_qp_kkt_solve_batched(eepacc_handle* h, int B, int nV, int nC, int nR, const double* H, const double* A,
+                                           const int8_t* ws_a, const int8_t* ws_x, const double* r_p, const double* r_a,
+                                           const double* r_x, double* p, double* q_a, double* q_x, int32_t* status,
+                                           void* stream) {
+    const char* name = "eepacc_qp_kkt_solve_batched";
+    const std::string who = std::string(name) + ": ";
+    if (!h) return fail(EEPACC_EINVAL, "NULL handle");
+    if (const int rc = not_classes(h, name)) return rc;
+    if (B < 0 || nV < 1 || nC < 0 || nR < 1) return fail(EEPACC_EINVAL, who + "bad sizes");
+    if (B == 0) return EEPACC_OK;
+    if (nV > EEPACC_QP_MAX_NV || nC > EEPACC_QP_MAX_NC)
+        return fail(EEPACC_EINVAL, who + "nV/nC above EEPACC_QP_MAX_NV/NC");
+    if (!H || !r_p || !p || (nC > 0 && !A)) return fail(EEPACC_EINVAL, who + "NULL buffer");
+    if (eepacc_qp_dense_lds_bytes(nV, nC) > 160 * 1024) return fail(EEPACC_EINVAL, who + "problem does not fit LDS");
+    HIPCHK(hipSetDevice(h->device));
+    const int grid = qp_grid(h, B);
+    const int rc = qp_workspace(h, grid, nV);
+    if (rc != EEPACC_OK) return rc;
+    eepacc_qp_kkt_args a;
+    a.B = B; a.nV = nV; a.nC = nC; a.nR = nR; a.H = H; a.A = A; a.ws_a = nC > 0 ? ws_a : nullptr; a.ws_x = ws_x;
+    a.r_p = r_p; a.r_a = nC > 0 ? r_a : nullptr; a.r_x = r_x; a.p = p; a.q_a = nC > 0 ? q_a : nullptr; a.q_x = q_x;
+    a.status = status; a.counter = h->d_qp_counter; a.ws = h->d_qp_ws; a.ws_stride = eepacc_qp_dense_ws_doubles(nV);
+    HIPCHK(hipMemsetAsync(h->d_qp_counter, 0, sizeof(int), (hipStream_t)stream));
+    HIPCHK(eepacc_qp_kkt_launch(a, grid, (hipStream_t)stream));
+    return EEPACC_OK;
+}
+
 // FBMPC (ABO/RunOpt_FBMPC.m:161-331): build kernel -> dense QP operator -> extraction, per step.
 static int fb_prepare(eepacc_handle* h, int B) {
     const int N = h->cfg.N;

@@ -29,4 +29,19 @@ hipError_t eepacc_qp_dense_launch(const eepacc_qp_args& a, int grid, hipStream_t
 // the instantiation with multipliers, working set and warm start (same workspace, same LDS)
 hipError_t eepacc_qp_dense_launch_dual(const eepacc_qp_args& a, int grid, hipStream_t stream);
 
+// k_qp_kkt: nR linear solves per instance with the KKT matrix of a given working set (eepacc_qp_kkt_solve_batched).
+// Workspace, LDS and work distribution are those of the solver.
+struct eepacc_qp_kkt_args {
+    int B, nV, nC, nR;
+    const double *H, *A;                 // as eepacc_qp_args
+    const int8_t *ws_a, *ws_x;           // [B][nC], [B][nV]: +-1 held, anything else not; each may be NULL
+    const double *r_p, *r_a, *r_x;       // [B][nR][nV], [B][nR][nC], [B][nR][nV]; r_a, r_x may be NULL (zeros)
+    double *p, *q_a, *q_x;               // same shapes; q_a, q_x may be NULL
+    int32_t* status;                     // [B] 0 solved, 1 singular or more than nV held (outputs NaN); may be NULL
+    int* counter;
+    double* ws;
+    size_t ws_stride;
+};
+hipError_t eepacc_qp_kkt_launch(const eepacc_qp_kkt_args& a, int grid, hipStream_t stream);
+
 #endif

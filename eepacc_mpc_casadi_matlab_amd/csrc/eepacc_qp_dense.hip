@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "eepacc_qp_dense.h"
+#include "eepacc_wave.h"
 
 #ifdef EEPACC_QP_TIMING
 __device__ long long g_qp_prof[16];
@@ -1184,6 +1185,282 @@ __global__ void __launch_bounds__(QT, 2) k_qp_dense(eepacc_qp_args a) {     // t
     }
 }
 
+// ---- k_qp_kkt: linear solves with the KKT matrix of a given working set (eepacc_qp_kkt_solve_batched) ----------------
+//     Hs p + A_W' q_a + E_W' q_x = r_p,   A_i p = r_a[i] (held rows),   p_j = r_x[j] (held variables)
+// i.e. [Hs N'; N 0][p; q] = [r_p; r_c] with the unsigned normals N: kkt_solve's system with every sgn = +1, no bounds read.
+// Same elimination of single-non-zero rows, same LU (lu_factor) and the same three rounds against residuals evaluated
+// from Hs and A.  The matrix is factorised once by the whole workgroup; after that one WAVEFRONT owns one right-hand side
+// (its sol / res / rhs vectors are wave-private LDS) and runs start, residuals, triangular solves and refinement without
+// a workgroup barrier, so up to four right-hand sides sweep the factor at the same time and the arithmetic of one
+// right-hand side does not depend on how many there are.
+
+// b <- (LU)^-1 P b, one wavefront, b in LDS.  Both sweeps are row-oriented (a row of the row-major factor is a coalesced
+// read), four rows per step: their dot products with the finished part are reduced side by side, the 4 x 4 triangle that
+// is left is done redundantly in every lane.
+__device__ void lu_solve_wave(const double* LU, int Nk, double* b, const int* piv) {
+    const int lane = lane_id();
+    if (lane == 0)
+        for (int k = 0; k < Nk; ++k) {
+            const int p = piv[k];
+            if (p != k) { const double t = b[k]; b[k] = b[p]; b[p] = t; }
+        }
+    WSYNC();
+    for (int i0 = 0; i0 < Nk; i0 += 4) {
+        double s[4] = {0.0, 0.0, 0.0, 0.0}, v[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int k = lane; k < i0; k += 64) {
+            const double bk = b[k];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) if (i0 + u < Nk) s[u] = fma(LU[(size_t)(i0 + u) * Nk + k], bk, s[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) s[u] = eepacc::wv::wave_sum(s[u]);
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (i0 + u < Nk) {
+                double t = b[i0 + u] - s[u];
+#pragma unroll
+                for (int w = 0; w < u; ++w) t = fma(-LU[(size_t)(i0 + u) * Nk + i0 + w], v[w], t);
+                v[u] = t;
+            }
+        WSYNC();
+        if (lane == 0) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) if (i0 + u < Nk) b[i0 + u] = v[u];
+        }
+        WSYNC();
+    }
+    for (int i0 = Nk - 1; i0 >= 0; i0 -= 4) {
+        double s[4] = {0.0, 0.0, 0.0, 0.0}, v[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int k = i0 + 1 + lane; k < Nk; k += 64) {
+            const double bk = b[k];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) if (i0 - u >= 0) s[u] = fma(LU[(size_t)(i0 - u) * Nk + k], bk, s[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) s[u] = eepacc::wv::wave_sum(s[u]);
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (i0 - u >= 0) {
+                const double* row = LU + (size_t)(i0 - u) * Nk;
+                double t = b[i0 - u] - s[u];
+#pragma unroll
+                for (int w = 0; w < u; ++w) t = fma(-row[i0 - w], v[w], t);
+                v[u] = t / row[i0 - u];
+            }
+        WSYNC();
+        if (lane == 0) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) if (i0 - u >= 0) b[i0 - u] = v[u];
+        }
+        WSYNC();
+    }
+}
+
+struct KktSys {          // one instance of k_qp_kkt, after the factorisation
+    int n, nC, q, nr, qg;
+    const double *Hs, *A, *K;
+};
+
+// coefficient of working-set entry e (a row of A if e < nC, else variable e - nC) on variable v
+__device__ __forceinline__ double kkt_coef(const KktSys& Y, int e, int v) {
+    return e < Y.nC ? Y.A[(size_t)v * Y.nC + e] : (v == e - Y.nC ? 1.0 : 0.0);
+}
+
+// res <- [r_p - Hs p - N' y;  r_c - N p] at sol = [p; y], one wavefront.  Hs is symmetric, so column i is read as the
+// coalesced row; an entry with y == 0 (the eliminated rows while their multipliers are held at zero) is not read.
+__device__ void kkt_residual_wave(const KktSys& Y, const Lds& S, const double* rp, const double* ra, const double* rx,
+                                  const double* sol, double* res) {
+    const int n = Y.n, nC = Y.nC;
+    for (int i = lane_id(); i < n; i += 64) {
+        double s = rp[i];
+        const double* h = Y.Hs + i;
+        int j = 0;
+        for (; j + 8 <= n; j += 8) {
+            double v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = h[(size_t)(j + u) * n];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) s = fma(-v[u], sol[j + u], s);
+        }
+        for (; j < n; ++j) s = fma(-h[(size_t)j * n], sol[j], s);
+        for (int c = 0; c < Y.q; ++c) {
+            const double y = sol[n + c];
+            if (y == 0.0) continue;
+            const int e = S.act[c];
+            if (e >= nC) { if (e - nC == i) s -= y; }
+            else {
+                const int sv = S.svar[e];
+                if (sv >= 0 ? sv == i : i < S.jend[e]) s = fma(-Y.A[(size_t)i * nC + e], y, s);
+            }
+        }
+        res[i] = s;
+    }
+    for (int c = lane_id(); c < Y.q; c += 64) {
+        const int e = S.act[c];
+        if (e >= nC) res[n + c] = (rx ? rx[e - nC] : 0.0) - sol[e - nC];
+        else {
+            double s = 0.0;
+            const int je = S.jend[e];
+            for (int j = 0; j < je; ++j) s = fma(Y.A[(size_t)j * nC + e], sol[j], s);
+            res[n + c] = (ra ? ra[e] : 0.0) - s;
+        }
+    }
+    WSYNC();
+}
+
+// one right-hand side, one wavefront: kkt_solve's start (eliminated variables from their rows), three rounds of
+// reduced solve + correction, multipliers of the eliminated rows from the stationarity rows of their variables.
+// Writes p[n] and the held entries of qa[nC], qx[n] (the others were zeroed by the workgroup).
+__device__ void kkt_rhs_wave(const KktSys& Y, const Lds& S, const double* rp, const double* ra, const double* rx,
+                             double* sol, double* res, double* rhs, double* p, double* qa, double* qx) {
+    const int n = Y.n, nC = Y.nC, q = Y.q, nr = Y.nr, Nr = Y.nr + Y.qg, lane = lane_id();
+    const int *kind = S.kk_kind, *freev = S.kk_free, *gpos = S.kk_gpos;
+    for (int i = lane; i < n + q; i += 64) sol[i] = 0.0;
+    WSYNC();
+    for (int c = lane; c < q; c += 64)
+        if (kind[c] >= 0) {
+            const int e = S.act[c];
+            sol[kind[c]] = e >= nC ? (rx ? rx[e - nC] : 0.0) : (ra ? ra[e] : 0.0) / Y.A[(size_t)kind[c] * nC + e];
+        }
+    WSYNC();
+    kkt_residual_wave(Y, S, rp, ra, rx, sol, res);
+    for (int round = 0; round < 3; ++round) {
+        for (int i = lane; i < Nr; i += 64) rhs[i] = i < nr ? res[freev[i]] : res[n + gpos[i - nr]];
+        WSYNC();
+        if (Nr > 0) lu_solve_wave(Y.K, Nr, rhs, S.piv);
+        for (int i = lane; i < Nr; i += 64) {
+            if (i < nr) sol[freev[i]] += rhs[i]; else sol[n + gpos[i - nr]] += rhs[i];
+        }
+        for (int c = lane; c < q; c += 64) if (kind[c] >= 0) sol[n + c] = 0.0;
+        WSYNC();
+        kkt_residual_wave(Y, S, rp, ra, rx, sol, res);
+        for (int c = lane; c < q; c += 64)
+            if (kind[c] >= 0) sol[n + c] = res[kind[c]] / kkt_coef(Y, S.act[c], kind[c]);
+        WSYNC();
+    }
+    for (int i = lane; i < n; i += 64) p[i] = sol[i];
+    for (int c = lane; c < q; c += 64) {
+        const int e = S.act[c];
+        if (e < nC) { if (qa) qa[e] = sol[n + c]; }
+        else if (qx) qx[e - nC] = sol[n + c];
+    }
+}
+
+__global__ void __launch_bounds__(QT, 2) k_qp_kkt(eepacc_qp_kkt_args a) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int n = a.nV, nC = a.nC, nR = a.nR;
+    Lds S;
+    carve(S, smem, n, nC);
+    double* const wsp = a.ws + (size_t)blockIdx.x * a.ws_stride;
+    double* const Hs = wsp;                                  // the places k_qp_dense gives them
+    double* const K = wsp + 7 * (size_t)n * n;
+    unsigned char* held = S.is_act;                          // [nC + n]
+    // what the factorisation leaves free of the carve: S.x .. S.ax, the vectors of the right-hand sides in flight
+    double* const pool = S.x;
+    const int pool_doubles = (int)(S.red - S.x);
+    for (;;) {
+        __syncthreads();
+        if (threadIdx.x == 0) S.ired[6] = atomicAdd(a.counter, 1);
+        __syncthreads();
+        const int b = S.ired[6];
+        if (b >= a.B) break;
+        const double* H = a.H + (size_t)b * n * n;
+        const double* A = a.A ? a.A + (size_t)b * nC * n : nullptr;
+        const int8_t* wa = a.ws_a ? a.ws_a + (size_t)b * nC : nullptr;
+        const int8_t* wx = a.ws_x ? a.ws_x + (size_t)b * n : nullptr;
+        for (int idx = threadIdx.x; idx < n * n; idx += QT) {
+            const int i = idx / n, j = idx % n;
+            Hs[idx] = 0.5 * (H[idx] + H[(size_t)j * n + i]);
+        }
+        int cnt = 0;
+        for (int i = threadIdx.x; i < nC; i += QT) {
+            const int hd = wa && (wa[i] == 1 || wa[i] == -1);
+            held[i] = (unsigned char)hd;
+            cnt += hd;
+            if (hd) {
+                int nnz = 0, var = -1;
+                for (int j = 0; j < n; ++j) if (A[(size_t)j * nC + i] != 0.0) { ++nnz; var = j; }
+                S.jend[i] = var + 1;
+                S.svar[i] = nnz == 1 ? var : -1;
+            }
+        }
+        for (int j = threadIdx.x; j < n; j += QT) {
+            const int hd = wx && (wx[j] == 1 || wx[j] == -1);
+            held[nC + j] = (unsigned char)hd;
+            cnt += hd;
+        }
+        KktSys Y;
+        Y.n = n; Y.nC = nC; Y.Hs = Hs; Y.A = A; Y.K = K;
+        Y.q = (int)block_sum((double)cnt, S);
+        int bad = Y.q > n;                                    // more rows than variables: no LDS for them, and singular
+        Y.nr = Y.qg = 0;
+        if (!bad) {
+            // working-set list (rows ascending, then variables) and kkt_solve's split: an entry with a single non-zero
+            // fixes its variable unless an earlier one did
+            if (threadIdx.x == 0) {
+                for (int v = 0; v < n; ++v) S.kk_vmap[v] = 0;
+                int c = 0, g = 0;
+                for (int e = 0; e < nC + n; ++e) {
+                    if (!held[e]) continue;
+                    S.act[c] = e;
+                    const int v = e >= nC ? e - nC : S.svar[e];
+                    if (v >= 0 && S.kk_vmap[v] == 0) { S.kk_kind[c] = v; S.kk_vmap[v] = -1; }
+                    else { S.kk_kind[c] = -1; S.kk_gpos[g++] = c; }
+                    ++c;
+                }
+                int nr = 0;
+                for (int v = 0; v < n; ++v) if (S.kk_vmap[v] == 0) { S.kk_vmap[v] = nr; S.kk_free[nr++] = v; }
+                S.ired[2] = nr; S.ired[3] = g;
+            }
+            __syncthreads();
+            Y.nr = S.ired[2]; Y.qg = S.ired[3];
+            const int nr = Y.nr, Nr = Y.nr + Y.qg;
+            for (int i = wave_id(); i < Nr; i += QW) {
+                double* kr = K + (size_t)i * Nr;
+                if (i < nr) {
+                    const double* h = Hs + (size_t)S.kk_free[i] * n;
+                    for (int j = lane_id(); j < nr; j += 64) kr[j] = h[S.kk_free[j]];
+                } else {
+                    const int e = S.act[S.kk_gpos[i - nr]];
+                    for (int j = lane_id(); j < nr; j += 64) {
+                        const double v = kkt_coef(Y, e, S.kk_free[j]);
+                        kr[j] = v;
+                        K[(size_t)j * Nr + i] = v;
+                    }
+                    for (int j = nr + lane_id(); j < Nr; j += 64) kr[j] = 0.0;
+                }
+            }
+            __syncthreads();
+            const double minpiv = Nr > 0 ? lu_factor(K, Nr, S) : 1.0;
+            if (minpiv < 1e-13) bad = 1;
+        }
+        __syncthreads();
+        // the entries outside the working set (all of them, as NaN, for an instance without a solution)
+        const double fill = bad ? NAN : 0.0;
+        for (int r = 0; r < nR; ++r) {
+            const size_t o = (size_t)b * nR + r;
+            for (int i = threadIdx.x; i < nC; i += QT) if (a.q_a && (bad || !held[i])) a.q_a[o * nC + i] = fill;
+            for (int j = threadIdx.x; j < n; j += QT) {
+                if (a.q_x && (bad || !held[nC + j])) a.q_x[o * n + j] = fill;
+                if (bad) a.p[o * n + j] = fill;
+            }
+        }
+        if (threadIdx.x == 0 && a.status) a.status[b] = bad;
+        if (bad) continue;
+        const int need = 2 * (n + Y.q) + Y.nr + Y.qg;                  // sol, res, rhs of one right-hand side
+        const int in_flight = pool_doubles / need < QW ? pool_doubles / need : QW;     // >= 3: need <= 6n, pool >= 20n
+        for (int r0 = 0; r0 < nR; r0 += in_flight) {
+            const int r = r0 + wave_id();
+            if (wave_id() >= in_flight || r >= nR) continue;
+            double* sol = pool + (size_t)wave_id() * need;
+            const size_t o = (size_t)b * nR + r;
+            kkt_rhs_wave(Y, S, a.r_p + o * n, a.r_a ? a.r_a + o * nC : nullptr, a.r_x ? a.r_x + o * n : nullptr,
+                         sol, sol + n + Y.q, sol + 2 * (n + Y.q), a.p + o * n,
+                         a.q_a ? a.q_a + o * nC : nullptr, a.q_x ? a.q_x + o * n : nullptr);
+        }
+    }
+}
+
 }  // namespace
 
 size_t eepacc_qp_dense_ws_doubles(int nV) {
@@ -1219,3 +1496,11 @@ static hipError_t launch(const eepacc_qp_args& a, int grid, hipStream_t stream) 
 
 hipError_t eepacc_qp_dense_launch(const eepacc_qp_args& a, int grid, hipStream_t stream) { return launch<false>(a, grid, stream); }
 hipError_t eepacc_qp_dense_launch_dual(const eepacc_qp_args& a, int grid, hipStream_t stream) { return launch<true>(a, grid, stream); }
+
+hipError_t eepacc_qp_kkt_launch(const eepacc_qp_kkt_args& a, int grid, hipStream_t stream) {
+    size_t lds = eepacc_qp_dense_lds_bytes(a.nV, a.nC);
+    hipError_t e = hipFuncSetAttribute((const void*)k_qp_kkt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_qp_kkt, dim3(grid), dim3(QT), lds, stream, a);
+    return hipGetLastError();
+}

@@ -70,6 +70,7 @@ def load_library() -> C.CDLL:
     lib.eepacc_run_fbmpc_host.argtypes = [vp, C.c_int, C.c_int] + [c_double_p] * 5 + [c_double_p, ip]
     lib.eepacc_qp_solve_batched.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [dp] * 8 + [dp, dp, dp, vp]
     lib.eepacc_qp_solve_batched_dual.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [dp] * 8 + [dp, dp] + [dp] * 3 + [dp] * 5 + [vp]
+    lib.eepacc_qp_kkt_solve_batched.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int] + [dp] * 2 + [dp] * 2 + [dp] * 3 + [dp] * 3 + [dp, vp]
     lib.eepacc_synchronize.argtypes = [vp, vp]
     lib.eepacc_build_flags.restype = C.c_char_p
     _lib = lib
@@ -82,7 +83,8 @@ ABI_SYMBOLS = ["eepacc_last_error", "eepacc_version", "eepacc_sizeof_settings", 
                "eepacc_run_abmpc_host", "eepacc_run_fbmpc_host", "eepacc_bl_step", "eepacc_run_blmpc", "eepacc_run_blmpc_host",
                "eepacc_tv_step", "eepacc_run_tvmpc", "eepacc_run_tvmpc_host", "eepacc_postprocess", "eepacc_kpis",
                "eepacc_follow_kpis",
-               "eepacc_last_iterations", "eepacc_qp_solve_batched", "eepacc_qp_solve_batched_dual", "eepacc_synchronize", "eepacc_build_flags"]
+               "eepacc_last_iterations", "eepacc_qp_solve_batched", "eepacc_qp_solve_batched_dual", "eepacc_qp_kkt_solve_batched",
+               "eepacc_synchronize", "eepacc_build_flags"]
 
 
 def _ptr(v):
@@ -362,6 +364,44 @@ class Engine:
                                                      r.lam_a.data_ptr(), r.lam_x.data_ptr(), r.ws_a.data_ptr(),
                                                      r.ws_x.data_ptr(), r.iters.data_ptr(), self._stream()))
         return r
+
+    def qp_kkt_solve(self, H, A, ws_a, ws_x, r_p, r_a=None, r_x=None):
+        """eepacc_qp_kkt_solve_batched: linear solves with the KKT matrix of a working set,
+            Hs p + A_W' q_a + E_W' q_x = r_p,   A_i p = r_a[i] on held rows,   p_j = r_x[j] on held variables.
+        H [B,nV,nV], A [B,nC,nV] as qp_solve_batched; ws_a [B,nC], ws_x [B,nV] int8 as qp_solve_batched_dual returns them
+        (+-1 held; None: none held); r_p [B,nR,nV] (or [B,nV]: one right-hand side), r_a [B,nR,nC] and r_x [B,nR,nV] or
+        None (zeros).  Returns p [B,nR,nV], q_a [B,nR,nC], q_x [B,nR,nV] (shaped like r_p: without the nR axis if r_p
+        came without it) and status [B] (1: singular or more than nV held, outputs NaN), all device tensors.
+        qp_sens.qp_jvp / qp_vjp turn this into derivatives of the QP's solution."""
+        t = self.torch
+        f64 = dict(dtype=t.float64, device=self.device)
+        H = t.as_tensor(H, **f64).contiguous()
+        B, nV = H.shape[0], H.shape[1]
+        A = t.as_tensor(A, **f64)
+        nC = A.shape[1]
+        A_cm = A.transpose(1, 2).contiguous()
+        r_p = t.as_tensor(r_p, **f64).contiguous()
+        flat = r_p.dim() == 2
+        nR = 1 if flat else r_p.shape[1]
+
+        def arr(v, n, dtype, per):
+            if v is None:
+                return None
+            v = t.as_tensor(v, dtype=dtype, device=self.device).contiguous()
+            if v.numel() != B * per * n:
+                raise ValueError(f"expected {B * per * n} entries, got {v.numel()}")
+            return v
+        ins = [H, A_cm, arr(ws_a, nC, t.int8, 1), arr(ws_x, nV, t.int8, 1), arr(r_p, nV, t.float64, nR),
+               arr(r_a, nC, t.float64, nR), arr(r_x, nV, t.float64, nR)]
+        p = t.empty((B, nR, nV), **f64)
+        q_a = t.empty((B, nR, nC), **f64)
+        q_x = t.empty((B, nR, nV), **f64)
+        status = t.empty((B,), dtype=t.int32, device=self.device)
+        _check(self.lib.eepacc_qp_kkt_solve_batched(self.h, B, nV, nC, nR, *[_ptr(v) for v in ins], p.data_ptr(),
+                                                    q_a.data_ptr(), q_x.data_ptr(), status.data_ptr(), self._stream()))
+        if flat:
+            p, q_a, q_x = p[:, 0], q_a[:, 0], q_x[:, 0]
+        return p, q_a, q_x, status
 
     def synchronize(self):
         """Wait for the engine's stream; raises if a closed-loop launch flagged a device-side failure."""

@@ -278,6 +278,36 @@ int  eepacc_qp_solve_batched_dual(eepacc_handle* h, int B, int nV, int nC,
                                   double* lam_a, double* lam_x, int8_t* ws_a, int8_t* ws_x,
                                   int32_t* iters, void* stream);
 
+/* Linear solves with the KKT matrix of a given working set: how the solution of the QP above moves with its data.
+ * Per instance, with Hs = (H+H')/2, the rows i with ws_a[i] = +-1 and the variables j with ws_x[j] = +-1 held (any other
+ * code: not held; the side does not enter; no bound is read), for each of nR >= 1 right-hand sides:
+ *     Hs p + A_W' q_a + E_W' q_x = r_p                 (nV rows)
+ *     A_i p = r_a[i]   on held rows,   p_j = r_x[j]   on held variables,   q_a[i] = q_x[j] = 0.0 elsewhere.
+ * This is the system in CasADi's sign (Hs x + g + A'lam_a + lam_x = 0), where a row's multiplier is one signed number.
+ * H, A as above; ws_a [B][nC], ws_x [B][nV] as the dual entry writes them (either may be NULL: none held);
+ * r_p [B][nR][nV], r_a [B][nR][nC], r_x [B][nR][nV] (r_a, r_x may be NULL: zeros; entries outside the working set are
+ * not read); outputs p, q_a, q_x of the same shapes (q_a, q_x may be NULL), status [B] (may be NULL).  The matrix is
+ * factorised once per instance (single-non-zero rows eliminated, LU with partial pivoting) and every right-hand side is
+ * refined twice against residuals evaluated from Hs and A.  More than nV held entries, or a smallest pivot below 1e-13
+ * (dependent rows, Hs singular on their null space): status 1 and NaN in every output of that instance; the other
+ * instances are unaffected.  Sizes, limits and refusals as for the operator above; nR < 1 is EEPACC_EINVAL.
+ * Meaning.  With (x, lam_a, lam_x, ws_a, ws_x) from the dual entry, the solution on the FIXED working set is a linear
+ * map of the data: the derivative below is the derivative of the QP's solution where the working set does not change
+ * (strict complementarity), and the one-sided derivative on that set where a held row has lam == 0.
+ *   Forward (directional derivative; d(.) are the data's directions, dHs = (dH+dH')/2):
+ *     r_p = -(dg + dHs x + dA' lam_a),  r_a = d(bound of the held side) - dA x,  r_x = d(bound of the held side)
+ *     gives p = dx, q_a = dlam_a, q_x = dlam_x.
+ *   Adjoint (the matrix is symmetric; gx, glam_a, glam_x are the gradients of a scalar loss L):
+ *     r_p = gx, r_a = glam_a, r_x = glam_x  gives (u, w_a, w_x) and
+ *     dL/dg = -u;  dL/d(bound) = w on the side held, 0 elsewhere;  dL/dH = -(u x' + x u')/2;
+ *     dL/dA = -(lam_a u' + w_a x')   (nC x nV). */
+int  eepacc_qp_kkt_solve_batched(eepacc_handle* h, int B, int nV, int nC, int nR,
+                                 const double* H, const double* A,
+                                 const int8_t* ws_a, const int8_t* ws_x,
+                                 const double* r_p, const double* r_a, const double* r_x,
+                                 double* p, double* q_a, double* q_x,
+                                 int32_t* status, void* stream);
+
 /* Same two operators for the force-based MPC (ABO/RunOpt_FBMPC.m:161-331).  v_prev, Fm_prev,
  * Fb_prev are the previous step's state/controls (ABO/RunOpt_FBMPC.m:188-191). */
 int  eepacc_fb_step(eepacc_handle* h, int B,
