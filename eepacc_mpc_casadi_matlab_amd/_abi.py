@@ -31,6 +31,18 @@ FKPI_N = len(FKPI_FIELDS)
 FKPI = {name: i for i, name in enumerate(FKPI_FIELDS)}
 FKPI_WEIGHTS = {"ab": 0, "fb": 1, "none": 2}      # EEPACC_FKPI_W_AB, _W_FB, _W_NONE
 
+# enum EEPACC_AB_ROW_*: the row types of eepacc_ab_qp_rows, ascending in the order of the rows within a stage
+AB_ROW_TYPES = ["s", "v", "xi_v", "xi_h", "xi_s", "xi_f", "blocked", "a_max", "a_min", "j_max", "j_min",
+                "v_lim", "v_curv", "v_stop", "v_tl", "v_inc", "safe1", "safe2", "hwp"]
+AB_ROW = {name: i for i, name in enumerate(AB_ROW_TYPES)}
+
+# argument types of the entry points that build the condensed QP of an ABMPC step; device arrays travel as addresses
+AB_BUILD_ARGTYPES = {
+    "eepacc_ab_qp_size": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "eepacc_ab_qp_rows": [C.c_void_p, c_int32_p, c_int32_p],
+    "eepacc_ab_build_qp": [C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p] * 5 + [C.c_void_p],
+}
+
 _VEH_FIELDS = ["m", "A_f", "c_d", "L", "h_g", "WD_s_F", "L_f", "L_r", "F0", "F1", "F2",
                "p00", "p10", "p01", "P_m_max", "T_m_max", "omega_m_r", "omega_m_max",
                "c_r", "R_w", "beta_gb", "beta_fd", "phi", "v_max", "eta_TF",

@@ -1,0 +1,264 @@
+// eepacc_ab_build.hip -- the condensed QP of one ABMPC step, written out as data: H, g, A, lba, uba in the layout the
+// dense QP operator reads.  The closed-loop kernels never form this problem; this kernel is the
+// boundary for callers who want it: to read multipliers row by row, to hand it to another solver, to differentiate it.
+//
+// Reference: ABO/RunOpt_ABMPC.m:193-252 with solverToUse = 1: estimators (EstimateVehicleTrajectory.m:55-88), bounds
+// (EstimateRouteAndComfortBounds.m:63-171), objective and rows of ABO/Functions/MPCs/CreateQP_AB.m:150-387 (zero rows
+// trimmed, RunOpt_ABMPC.m:229-233) and the condensing of TransformToDenseFormulation.m:30-91.
+//
+// No dense product with Psi is formed.  With A_k = [1 T_k; 0 1], B_k = [T_k^2/2; T_k] on the acceleration only,
+//   v_k = v_0 + sum_{i<k} T_i a_i,   s_k = d_s[k] + sum_{i<k} Ss[k][i] a_i,   Ss[k][i] = T_i^2/2 + T_i (T_{k-1} + .. + T_{i+1}),
+// the sparse-form Hessian is diagonal in v_k and xi_h and tridiagonal in a_k, and a row touches s_k, v_k, a_k, a_{k-1} and
+// one slack.  Every output entry is assembled from these pieces, which are put into LDS once.  Sums run in the order of
+// the reference's loops (the inner sum of Ss from stage k-1 downwards, the entries of g over ascending stages) and
+// products are not contracted into fused multiply-adds, so that an entry of A, lba, uba and g has the reference's
+// roundings; the a-a entries of H take the suffix sums of the speed curvature instead of a loop per entry.
+//
+// Dense variable order per stage (5): a, xi_v, xi_h, xi_s, xi_f.  Rows: eepacc_ab_build.h.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "eepacc_ab_build.h"
+
+// also for the estimators of eepacc_stage.h as this file compiles them
+#pragma clang fp contract(off)
+#include "eepacc_stage.h"
+
+namespace eepacc {
+namespace {
+
+constexpr int BT = 256;              // threads of a workgroup: four waves
+constexpr int kS = kMaxN + 1;        // stage arrays: index N is the terminal stage
+
+struct Stages {                      // per-stage quantities of the step, static LDS
+    double T[kS], stv[kS], chw[kS], ds[kS];
+    double v_lim[kS], v_curv[kS], v_stop[kS], v_TL[kS], a_min[kS], a_max[kS], j_min[kS], j_max[kS];
+    double hv[kS];                   // curvature of v_k in the sparse-form objective (CreateQP_AB.m:154-166)
+    double tv[kS];                   // (Hs d + cs) on v_k
+    double ta[kS];                   // (Hs d + cs) on a_k
+    double hsuf[kS + 1];             // hsuf[m] = sum_{k >= m} hv[k], stages below N
+    double q[kS];                    // jerk curvature 2 w_j / T_k^2 (:173-180)
+    double hd[kS];                   // diagonal of the a-a block
+};
+
+struct Row {                         // one row: as s_k + av v_k + ga a_k + de a_{k-1} + sc xi_slack in [lb, ub]
+    int k, slack;                    // slack 0..3 = xi_v, xi_h, xi_s, xi_f; -1 none
+    double as, av, ga, de, sc, lb, ub;
+};
+
+// Row `type` (EEPACC_AB_ROW_*) of stage k; k == N: the two terminal rows (CreateQP_AB.m:376-387)
+__device__ inline Row ab_row(const DevCfg& C, const Stages& S, int k, int type, double a_minus1) {
+    Row R;
+    R.k = k; R.slack = -1;
+    R.as = R.av = R.ga = R.de = R.sc = 0.0;
+    R.lb = -INFINITY; R.ub = INFINITY;
+    const int N = C.N;
+    if (k == N) {
+        R.as = 1.0;
+        if (type == EEPACC_AB_ROW_SAFE1) R.ub = S.stv[N - 1] - C.h_min;
+        else { R.av = C.tau_min; R.ub = S.stv[N - 1]; }
+        return R;
+    }
+    const double T = S.T[k];
+    const double A_hwp = 2.0;
+    switch (type) {
+    case EEPACC_AB_ROW_S: R.as = 1.0; R.lb = 0.0; R.ub = C.s_goal; break;                          // :256-279
+    case EEPACC_AB_ROW_V: R.av = 1.0; R.lb = 0.0; R.ub = C.v_max; break;
+    case EEPACC_AB_ROW_XI_V: R.slack = 0; R.sc = 1.0; R.lb = 0.0; break;
+    case EEPACC_AB_ROW_XI_H: R.slack = 1; R.sc = 1.0; R.lb = 0.0; break;
+    case EEPACC_AB_ROW_XI_S: R.slack = 2; R.sc = 1.0; R.lb = 0.0; break;
+    case EEPACC_AB_ROW_XI_F: R.slack = 3; R.sc = 1.0; R.lb = 0.0; break;
+    case EEPACC_AB_ROW_BLOCKED: R.de = 1.0; R.ga = -1.0; R.lb = 0.0; R.ub = 0.0; break;             // :283-289
+    case EEPACC_AB_ROW_A_MAX: R.ga = 1.0; R.slack = 3; R.sc = -1.0; R.ub = S.a_max[k]; break;       // :292-299
+    case EEPACC_AB_ROW_A_MIN: R.ga = 1.0; R.slack = 3; R.sc = 1.0; R.lb = S.a_min[k]; break;
+    case EEPACC_AB_ROW_J_MAX:                                                                       // :302-322
+        R.ga = 1.0; R.slack = 3; R.sc = -1.0;
+        if (k > 0) { R.de = -1.0; R.ub = T * S.j_max[k]; } else R.ub = T * S.j_max[k] + a_minus1;
+        break;
+    case EEPACC_AB_ROW_J_MIN:
+        R.ga = 1.0; R.slack = 3; R.sc = 1.0;
+        if (k > 0) { R.de = -1.0; R.lb = T * S.j_min[k]; } else R.lb = T * S.j_min[k] + a_minus1;
+        break;
+    case EEPACC_AB_ROW_V_LIM: R.av = 1.0; R.slack = 3; R.sc = -1.0; R.ub = S.v_lim[k]; break;       // ORIG :307-329
+    case EEPACC_AB_ROW_V_CURV: R.av = 1.0; R.slack = 3; R.sc = -1.0; R.ub = S.v_curv[k]; break;
+    case EEPACC_AB_ROW_V_STOP: R.av = 1.0; R.slack = 2; R.sc = -1.0; R.ub = S.v_stop[k]; break;
+    case EEPACC_AB_ROW_V_TL: R.av = 1.0; R.slack = 2; R.sc = -1.0; R.ub = S.v_TL[k]; break;
+    case EEPACC_AB_ROW_V_INC: R.av = 1.0; R.slack = 0; R.sc = 1.0; R.lb = fmin(S.v_lim[k], S.v_curv[k]); break;   // :349-352
+    case EEPACC_AB_ROW_SAFE1: R.as = 1.0; R.slack = 2; R.sc = -1.0; R.ub = S.stv[k] - C.h_min; break;            // :355-362
+    case EEPACC_AB_ROW_SAFE2: R.as = 1.0; R.av = C.tau_min; R.slack = 2; R.sc = -1.0; R.ub = S.stv[k]; break;
+    default: R.as = 1.0; R.av = S.chw[k]; R.slack = 1; R.sc = -1.0; R.ub = S.stv[k] - A_hwp; break;              // :365-371
+    }
+    return R;
+}
+
+__global__ void __launch_bounds__(BT) k_ab_build(const DevCfg* __restrict__ cfg, int nC, const double* __restrict__ s,
+                                                 const double* __restrict__ v, const double* __restrict__ a_prev,
+                                                 const double* __restrict__ t0, const double* __restrict__ s_tv,
+                                                 const double* __restrict__ v_tv, const double* __restrict__ a_tv_prev,
+                                                 double* __restrict__ H, double* __restrict__ g, double* __restrict__ A,
+                                                 double* __restrict__ lba, double* __restrict__ uba) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    __shared__ Stages S;
+    const DevCfg& C = *cfg;
+    const int N = C.N, nV = 5 * N, tid = threadIdx.x;
+    const size_t b = blockIdx.x;
+    const int ld = N | 1;                                   // odd row stride: a column of Ss is read without bank conflicts
+    double* Ss = reinterpret_cast<double*>(smem);           // [N+1][ld]
+    unsigned short* rows = reinterpret_cast<unsigned short*>(Ss + (size_t)(N + 1) * ld);   // [nC]: stage | type << 8
+    const double s_0 = s[b], v_0 = v[b], a_minus1 = a_prev[b], t_0 = t0[b];
+
+    // ---- estimators, bounds and the sparse-form objective per stage (A2, A3, CreateQP_AB.m:150-187)
+    if (tid <= N) {
+        const int k = tid;
+        double se, ve, st, vt;
+        if (C.paramEstSetting == 2) {
+            // EstimateVehicleTrajectory.m:81-88: [x_curr; prev(3:end); prev(end) + Ts v_prev(end)]; the handle carries
+            // the previous step's predictions, which are read and not written here
+            const double* predp = C.pred + b * 128;
+            const int idx = k < N ? k + 1 : N;
+            const double ps = predp[idx], pv = predp[64 + idx];
+            se = k == 0 ? s_0 : (k < N ? ps : ps + C.Tvec[N - 1] * pv);
+            ve = k == 0 ? v_0 : pv;
+        } else {
+            estimate_traj(C, C.paramEstSetting, C.tConstACC_ego, s_0, v_0, a_minus1, k, se, ve);
+        }
+        estimate_traj(C, C.TVestSetting, C.tConstACC_tar, s_tv[b], v_tv[b], a_tv_prev[b], k, st, vt);
+        S.stv[k] = st;
+        double hv = 0.0, tv = 0.0, ta = 0.0, T = 0.0, q = 0.0;
+        if (k < N) {
+            T = C.Tvec[k];
+            route_bounds(C, se, ve, t_0, k, S.v_lim[k], S.v_curv[k], S.v_stop[k], S.v_TL[k], S.a_min[k], S.a_max[k],
+                         S.j_min[k], S.j_max[k]);
+            const double T_hwp = 2.0, G_hwp = -0.0246 * T_hwp + 0.010819;
+            S.chw[k] = T_hwp + G_hwp * ve;
+            double cv, ca;
+            if (C.ab_fuel_term == 2) {
+                // ICE map :154-159, gear ratio of the stage from its estimated speed (LUTgearshift.m:17-41)
+                double tg = C.ice_gb[7];
+#pragma unroll
+                for (int g2 = 6; g2 >= 0; --g2) if (ve < C.ice_up[g2]) tg = C.ice_gb[g2];
+                hv = 2.0 * C.ice_cq / tg; cv = C.ice_lv * tg; ca = C.ice_la / tg;
+            } else {
+                hv = 2.0 * C.cq; cv = C.glin_v; ca = C.glin_a;                  // :162-166 (all zero without a fuel term)
+            }
+            tv = hv * v_0 + cv;
+            ta = ca;
+            if (k == 0) ta -= 2.0 * C.w_j / T * a_minus1;                       // :173-176
+            q = 2.0 * C.w_j / (T * T);
+        }
+        S.T[k] = T; S.hv[k] = hv; S.tv[k] = tv; S.ta[k] = ta; S.q[k] = q;
+    }
+    __syncthreads();
+
+    // ---- position sensitivities and free response; suffix sums and the a-a diagonal; the row catalogue
+    if (tid <= N) {
+        const int k = tid;
+        double R = 0.0;                                     // T_{k-1} + .. + T_{i+1}, summed downwards as the reference does
+        for (int i = k - 1; i >= 0; --i) {
+            const double Ti = S.T[i];
+            Ss[(size_t)k * ld + i] = 0.5 * Ti * Ti + R * Ti;
+            R += Ti;
+        }
+        S.ds[k] = k == 0 ? s_0 : s_0 + R * v_0;
+        if (k < N) {
+            double hd = 2.0 * C.w_a + S.q[k];                                   // :169-180
+            if (k + 1 < N) hd += S.q[k + 1];
+            S.hd[k] = hd;
+            // first row of the stage: the rows of the stages before it
+            int r = (C.ab_route_rows ? 18 : 14) * k;
+            for (int j = 0; j < k; ++j) r += C.mb_mask[j] ? 1 : 0;
+            for (int type = 0; type < EEPACC_AB_ROW_N; ++type)
+                if (ab_row_present(type, C.ab_route_rows, C.mb_mask[k])) rows[r++] = (unsigned short)(k | (type << 8));
+        } else {
+            rows[nC - 2] = (unsigned short)(N | (EEPACC_AB_ROW_SAFE1 << 8));
+            rows[nC - 1] = (unsigned short)(N | (EEPACC_AB_ROW_SAFE2 << 8));
+        }
+    } else if (tid == 64) {
+        double acc = 0.0;
+        S.hsuf[N] = 0.0;
+        for (int k = N - 1; k >= 0; --k) { acc += S.hv[k]; S.hsuf[k] = acc; }
+    }
+    __syncthreads();
+
+    // ---- H, row-major: consecutive lanes write consecutive entries; (ra, rb) advance without a division
+    {
+        double* Hd = H + b * (size_t)nV * nV;
+        const int total = nV * nV, dra = BT / nV, drb = BT % nV;
+        int ra = tid / nV, rb = tid % nV;
+        for (int idx = tid; idx < total; idx += BT) {
+            const int i = ra / 5, ci = ra - 5 * i, j = rb / 5, cj = rb - 5 * j;
+            double h = 0.0;
+            if (ci == 0 && cj == 0) {
+                const int hi = i > j ? i : j, lo = i > j ? j : i;
+                if (i == j) h = S.hd[i];
+                else if (hi == lo + 1) h = -S.q[hi];
+                h += S.T[i] * S.T[j] * S.hsuf[hi + 1];
+            } else if (ra == rb && ci == 2) {
+                h = 2.0 * C.w_h;                                                // :185
+            }
+            Hd[idx] = h;
+            rb += drb; ra += dra;
+            if (rb >= nV) { rb -= nV; ++ra; }
+        }
+    }
+    // ---- g: Psi'(Hs d + cs), the sum over ascending stages (:183-187 for the slacks)
+    for (int col = tid; col < nV; col += BT) {
+        const int i = col / 5, c = col - 5 * i;
+        double gv;
+        if (c == 0) {
+            gv = S.ta[i];
+            const double Ti = S.T[i];
+            for (int k = i + 1; k < N; ++k) gv += Ti * S.tv[k];
+        } else {
+            gv = c == 1 ? C.w_v : c == 2 ? 1e2 * C.w_h : c == 3 ? C.w_s : C.w_f;
+        }
+        g[b * (size_t)nV + col] = gv;
+    }
+    // ---- lba, uba: the row's bounds less its value at the free response
+    for (int r = tid; r < nC; r += BT) {
+        const int e = rows[r];
+        const Row R = ab_row(C, S, e & 0xff, e >> 8, a_minus1);
+        const double shift = R.as * S.ds[R.k] + R.av * v_0;
+        lba[b * (size_t)nC + r] = R.lb - shift;
+        uba[b * (size_t)nC + r] = R.ub - shift;
+    }
+    // ---- A, column-major nC x nV: a wave takes 64 consecutive rows (consecutive addresses of one column) and walks the
+    // columns of its quarter of the stages, so the four waves share every block of rows evenly
+    {
+        double* Ad = A + b * (size_t)nV * nC;
+        const int wave = tid >> 6, lane = tid & 63;
+        const int i0 = wave * N / 4, i1 = (wave + 1) * N / 4;
+        for (int r0 = 0; r0 < nC; r0 += 64) {
+            const int r = r0 + lane;
+            if (r >= nC) continue;
+            const int e = rows[r];
+            const Row R = ab_row(C, S, e & 0xff, e >> 8, a_minus1);
+            const int k = R.k;
+            double* col = Ad + (size_t)(5 * i0) * nC + r;
+            for (int i = i0; i < i1; ++i) {
+                double va = 0.0;
+                if (i < k) { va = R.as * Ss[(size_t)k * ld + i]; va += R.av * S.T[i]; }
+                if (i == k) va = R.ga;
+                if (i == k - 1) va += R.de;
+                col[0] = va;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) col[(size_t)(1 + c) * nC] = (i == k && c == R.slack) ? R.sc : 0.0;
+                col += (size_t)5 * nC;
+            }
+        }
+    }
+}
+
+}  // namespace
+
+hipError_t launch_ab_build(const DevCfg* cfg, int N, int nC, int B, const double* s, const double* v, const double* a_prev,
+                           const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                           double* H, double* g, double* A, double* lba, double* uba, hipStream_t stream) {
+    const size_t smem = (size_t)(N + 1) * (N | 1) * sizeof(double) + (size_t)nC * sizeof(unsigned short);
+    hipLaunchKernelGGL(k_ab_build, dim3(B), dim3(BT), smem, stream, cfg, nC, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev,
+                       H, g, A, lba, uba);
+    return hipGetLastError();
+}
+
+}  // namespace eepacc

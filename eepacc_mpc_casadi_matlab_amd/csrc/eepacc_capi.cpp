@@ -10,6 +10,7 @@
 #include <memory>
 #include "eepacc_device.h"
 #include "eepacc_ab.h"
+#include "eepacc_ab_build.h"
 #include "eepacc_qp_dense.h"
 #include "eepacc_fb.h"
 #include "eepacc_fbs.h"
@@ -575,6 +576,55 @@ extern "C" int eepacc_run_tvmpc(eepacc_handle* h, int B, int n_steps, const doub
                                 const double* a_minus1, double* traj, int32_t* status, void* stream) {
     const int rc = need_tv(h);
     return rc != EEPACC_OK ? rc : ab_run_impl(h, "eepacc_run_tvmpc", "eepacc_run_tvmpc: bad B / n_steps", B, n_steps, s0, v0, a_minus1, nullptr, nullptr, traj, status, stream);
+}
+
+// The condensed QP of an ABMPC step as data (eepacc_ab_build.hip).  Only a handle of eepacc_create with bl_mode = 0 has it.
+static int ab_qp_handle(const eepacc_handle* h, const char* who) {
+    if (!h) return fail(EEPACC_EINVAL, std::string(who) + ": NULL handle");
+    if (h->n_classes) return fail(EEPACC_ENOTSUP, std::string(who) + ": a handle of eepacc_create_classes has no single problem size (nC can differ per class)");
+    if (h->cfg.bl_mode != 0) return fail(EEPACC_ENOTSUP, std::string(who) + ": the handle was created with bl_mode = " + std::to_string(h->cfg.bl_mode) + "; only the ABMPC problem (CreateQP_AB) is built");
+    return EEPACC_OK;
+}
+
+extern "C" int eepacc_ab_qp_size(const eepacc_handle* h, int* nV, int* nC) {
+    if (const int rc = ab_qp_handle(h, "eepacc_ab_qp_size")) return rc;
+    if (!nV) return fail(EEPACC_EINVAL, "eepacc_ab_qp_size: nV is NULL");
+    if (!nC) return fail(EEPACC_EINVAL, "eepacc_ab_qp_size: nC is NULL");
+    *nV = 5 * h->cfg.N;
+    *nC = eepacc::ab_qp_num_rows(h->cfg);
+    return EEPACC_OK;
+}
+
+extern "C" int eepacc_ab_qp_rows(const eepacc_handle* h, int32_t* stage, int32_t* type) {
+    if (const int rc = ab_qp_handle(h, "eepacc_ab_qp_rows")) return rc;
+    if (!stage) return fail(EEPACC_EINVAL, "eepacc_ab_qp_rows: stage is NULL");
+    if (!type) return fail(EEPACC_EINVAL, "eepacc_ab_qp_rows: type is NULL");
+    const DevCfg& C = h->cfg;
+    int r = 0;
+    for (int k = 0; k < C.N; ++k)
+        for (int t = 0; t < EEPACC_AB_ROW_N; ++t)
+            if (eepacc::ab_row_present(t, C.ab_route_rows, C.mb_mask[k])) { stage[r] = k; type[r] = t; ++r; }
+    stage[r] = C.N; type[r] = EEPACC_AB_ROW_SAFE1; ++r;
+    stage[r] = C.N; type[r] = EEPACC_AB_ROW_SAFE2; ++r;
+    return EEPACC_OK;
+}
+
+extern "C" int eepacc_ab_build_qp(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
+                                  const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                                  double* H, double* g, double* A, double* lba, double* uba, void* stream) {
+    if (const int rc = ab_qp_handle(h, "eepacc_ab_build_qp")) return rc;
+    if (B < 0 || B > h->max_batch)
+        return fail(EEPACC_EINVAL, "eepacc_ab_build_qp: B = " + std::to_string(B) + " is outside [0, max_batch = " + std::to_string(h->max_batch) + "]");
+    if (B == 0) return EEPACC_OK;
+    const struct { const void* p; const char* name; } bufs[] = {
+        {s, "s"}, {v, "v"}, {a_prev, "a_prev"}, {t0, "t0"}, {s_tv, "s_tv"}, {v_tv, "v_tv"}, {a_tv_prev, "a_tv_prev"},
+        {H, "H"}, {g, "g"}, {A, "A"}, {lba, "lba"}, {uba, "uba"}};
+    for (const auto& bf : bufs)
+        if (!bf.p) return fail(EEPACC_EINVAL, std::string("eepacc_ab_build_qp: ") + bf.name + " is NULL");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(eepacc::launch_ab_build(h->d_cfg, h->cfg.N, eepacc::ab_qp_num_rows(h->cfg), B, s, v, a_prev, t0, s_tv, v_tv,
+                                   a_tv_prev, H, g, A, lba, uba, (hipStream_t)stream));
+    return EEPACC_OK;
 }
 
 extern "C" int eepacc_postprocess(eepacc_handle* h, int B, int n_steps, const double* traj, double* rpm,

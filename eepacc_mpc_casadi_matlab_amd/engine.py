@@ -13,8 +13,8 @@ from typing import Any, Dict, NamedTuple, Optional
 
 import numpy as np
 
-from ._abi import (SettingsHolder, SettingsPOD, Vehicle, make_vehicle, pack_classes, OUT, OUT_N, OUT_FIELDS, KPI_N, FKPI_N, FKPI_WEIGHTS, c_double_p,
-                   as_dptr, as_iptr)
+from ._abi import (SettingsHolder, SettingsPOD, Vehicle, make_vehicle, pack_classes, OUT, OUT_N, OUT_FIELDS, KPI_N, FKPI_N, FKPI_WEIGHTS, AB_BUILD_ARGTYPES,
+                   c_double_p, as_dptr, as_iptr)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIBPATH = os.path.join(_HERE, "libeepacc.so")
@@ -71,6 +71,8 @@ def load_library() -> C.CDLL:
     lib.eepacc_qp_solve_batched.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [dp] * 8 + [dp, dp, dp, vp]
     lib.eepacc_qp_solve_batched_dual.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [dp] * 8 + [dp, dp] + [dp] * 3 + [dp] * 5 + [vp]
     lib.eepacc_qp_kkt_solve_batched.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int] + [dp] * 2 + [dp] * 2 + [dp] * 3 + [dp] * 3 + [dp, vp]
+    for name, argtypes in AB_BUILD_ARGTYPES.items():
+        getattr(lib, name).argtypes = argtypes
     lib.eepacc_synchronize.argtypes = [vp, vp]
     lib.eepacc_build_flags.restype = C.c_char_p
     _lib = lib
@@ -84,6 +86,7 @@ ABI_SYMBOLS = ["eepacc_last_error", "eepacc_version", "eepacc_sizeof_settings", 
                "eepacc_tv_step", "eepacc_run_tvmpc", "eepacc_run_tvmpc_host", "eepacc_postprocess", "eepacc_kpis",
                "eepacc_follow_kpis",
                "eepacc_last_iterations", "eepacc_qp_solve_batched", "eepacc_qp_solve_batched_dual", "eepacc_qp_kkt_solve_batched",
+               "eepacc_ab_qp_size", "eepacc_ab_qp_rows", "eepacc_ab_build_qp",
                "eepacc_synchronize", "eepacc_build_flags"]
 
 
@@ -106,6 +109,16 @@ class QpDualResult(NamedTuple):
     ws_a: Any
     ws_x: Any
     iters: Any
+
+
+class AbQp(NamedTuple):
+    """What Engine.ab_build_qp returns (device tensors): the condensed QP of one ABMPC step, min 1/2 x'Hx + g'x subject to
+    lba <= Ax <= uba, in the shapes qp_solve_batched takes.  A is the transposed view of the column-major buffer."""
+    H: Any
+    g: Any
+    A: Any
+    lba: Any
+    uba: Any
 
 
 class Engine:
@@ -218,6 +231,36 @@ class Engine:
     # B2 ------------------------------------------------------------------------------------
     def ab_step(self, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, want_pred: bool = True):
         return self._step(self.lib.eepacc_ab_step, (s, v, a_prev, t0, s_tv, v_tv, a_tv_prev), want_pred)
+
+    def ab_qp_size(self):
+        """eepacc_ab_qp_size: (nV, nC) of the condensed QP of an ABMPC step of this engine."""
+        nV, nC = C.c_int(), C.c_int()
+        _check(self.lib.eepacc_ab_qp_size(self.h, C.byref(nV), C.byref(nC)))
+        return nV.value, nC.value
+
+    def ab_qp_rows(self):
+        """eepacc_ab_qp_rows: (stage, type), two int32 arrays [nC]: the horizon stage of every row of the built problem (N for
+        the two terminal rows) and its type as an index into _abi.AB_ROW_TYPES."""
+        _, nC = self.ab_qp_size()
+        stage = np.empty(nC, dtype=np.int32); typ = np.empty(nC, dtype=np.int32)
+        _check(self.lib.eepacc_ab_qp_rows(self.h, as_iptr(stage), as_iptr(typ)))
+        return stage, typ
+
+    def ab_build_qp(self, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev) -> AbQp:
+        """eepacc_ab_build_qp: the condensed QP the reference poses at this step (ABO/RunOpt_ABMPC.m:238-252), for the inputs
+        of ab_step.  Returns AbQp(H [B,nV,nV], g [B,nV], A [B,nC,nV], lba [B,nC], uba [B,nC]); qp_solve_batched,
+        qp_solve_batched_dual, qp_kkt_solve and the qp_sens functions take the fields as they are (A's column-major buffer
+        is used without a copy).  Reads and writes no solver state of the engine."""
+        t = self.torch
+        B = int(t.as_tensor(s).numel())
+        ins = [self._d(x, B) for x in (s, v, a_prev, t0, s_tv, v_tv, a_tv_prev)]
+        nV, nC = self.ab_qp_size()
+        f64 = dict(dtype=t.float64, device=self.device)
+        H = t.empty((B, nV, nV), **f64); g = t.empty((B, nV), **f64); A_cm = t.empty((B, nV, nC), **f64)
+        lba = t.empty((B, nC), **f64); uba = t.empty((B, nC), **f64)
+        _check(self.lib.eepacc_ab_build_qp(self.h, B, *[x.data_ptr() for x in ins], H.data_ptr(), g.data_ptr(), A_cm.data_ptr(),
+                                           lba.data_ptr(), uba.data_ptr(), self._stream()))
+        return AbQp(H, g, A_cm.transpose(1, 2), lba, uba)
 
     # B1 ------------------------------------------------------------------------------------
     def run_abmpc(self, s0, v0, a_minus1, s_tv, v_tv, resume: bool = False, out=None, by_name_bl: bool = False):

@@ -229,6 +229,64 @@ int  eepacc_run_abmpc(eepacc_handle* h, int B, int n_steps,
                       const double* s_tv, const double* v_tv,
                       double* traj, int32_t* status, void* stream);
 
+/* The condensed QP of one ABMPC step as data: what a user of the reference holds in the workspace as H, c, G, g_lb, g_ub
+ * (ABO/RunOpt_ABMPC.m:238-252, solverToUse = 1) and finds saved as optSol.H, optSol.G.  The ABMPC kernels above never form it;
+ * eepacc_ab_build_qp does, for the inputs of eepacc_ab_step (device, each [B]): the estimators and bounds
+ * (EstimateVehicleTrajectory.m:55-88, EstimateRouteAndComfortBounds.m:63-171), the objective and rows of
+ * ABO/Functions/MPCs/CreateQP_AB.m:150-387 with the zero rows trimmed as RunOpt_ABMPC.m:229-233 does, condensed as
+ * TransformToDenseFormulation.m:30-91.  Outputs, device, instance-major, in the layout eepacc_qp_solve_batched reads:
+ * H [B][nV*nV], g [B][nV], A [B][nV][nC] (column-major nC x nV), lba, uba [B][nC], an absent side -inf / +inf.  There are no
+ * lbx / ubx: the reference passes infinite ones in the dense branch (:100-104); hand the operator NULL.
+ * nV = 5 N_hor, variables per stage a, xi_v, xi_h, xi_s, xi_f.  nC = 14 N_hor + 2 (ABO) or 18 N_hor + 2 (ab_route_rows = 1)
+ * plus one row per blocked stage (Mb[k] = 1, CreateQP_AB.m:283-289), rows in the reference's order; eepacc_ab_qp_size
+ * returns both.  Covered: both trees, ab_fuel_term 0, 1 and 2, Mb, variable Tvec, every N_hor the handle accepts, the
+ * estimator modes 0, 1 and 2 (mode 2 reads the predictions the handle carries from the last step and does not write them).
+ *
+ * eepacc_ab_qp_rows fills two host arrays [nC]: stage[i] in 0 .. N_hor-1, or N_hor for the two terminal rows
+ * (CreateQP_AB.m:376-387), and type[i], one of EEPACC_AB_ROW_*, so that lam_a and ws_a of eepacc_qp_solve_batched_dual on
+ * the built problem can be read row by row.  The values ascend in the order of the rows within a stage: */
+enum {
+    EEPACC_AB_ROW_S = 0,     /* CreateQP_AB.m:256-279  0 <= s_k <= s_goal                                                  */
+    EEPACC_AB_ROW_V,         /*   0 <= v_k <= v_max                                                                        */
+    EEPACC_AB_ROW_XI_V,      /*   xi_v >= 0                                                                                */
+    EEPACC_AB_ROW_XI_H,      /*   xi_h >= 0                                                                                */
+    EEPACC_AB_ROW_XI_S,      /*   xi_s >= 0                                                                                */
+    EEPACC_AB_ROW_XI_F,      /*   xi_f >= 0                                                                                */
+    EEPACC_AB_ROW_BLOCKED,   /* :283-289  a_{k-1} - a_k = 0, only on a stage with Mb[k] = 1                                */
+    EEPACC_AB_ROW_A_MAX,     /* :292-299  a_k - xi_f <= a_max                                                              */
+    EEPACC_AB_ROW_A_MIN,     /*   a_k + xi_f >= a_min                                                                      */
+    EEPACC_AB_ROW_J_MAX,     /* :302-322  a_k - a_{k-1} - xi_f <= T_k j_max (stage 0: a_minus1 on the right-hand side)     */
+    EEPACC_AB_ROW_J_MIN,     /*   a_k - a_{k-1} + xi_f >= T_k j_min                                                        */
+    EEPACC_AB_ROW_V_LIM,     /* ORIG/.../CreateQP_AB.m:307-329, only with ab_route_rows:  v_k - xi_f <= speed limit        */
+    EEPACC_AB_ROW_V_CURV,    /*   v_k - xi_f <= curve speed                                                                */
+    EEPACC_AB_ROW_V_STOP,    /*   v_k - xi_s <= stop speed                                                                 */
+    EEPACC_AB_ROW_V_TL,      /*   v_k - xi_s <= traffic-light speed                                                        */
+    EEPACC_AB_ROW_V_INC,     /* :349-352  speed incentive  v_k + xi_v >= min(speed limit, curve speed)                     */
+    EEPACC_AB_ROW_SAFE1,     /* :355-362  safe distance 1  s_k - xi_s <= s_tv - h_min (terminal row: no slack)             */
+    EEPACC_AB_ROW_SAFE2,     /*   safe distance 2  s_k + tau_min v_k - xi_s <= s_tv (terminal row: no slack)               */
+    EEPACC_AB_ROW_HWP,       /* :365-371  headway policy  s_k + (T_hwp + G_hwp v_est) v_k - xi_h <= s_tv - A_hwp           */
+    EEPACC_AB_ROW_N
+};
+/* The built problem is the reference's own.  A measured state outside its hard bounds shows up as a stage-0 row without
+ * coefficients whose bounds exclude 0 (the operator then reports status 1); the tolerance state_bound_tol of the ABMPC
+ * kernels is not applied.  The constant term of the objective is excluded: 1/2 x'Hx + g'x at the solution equals
+ * EEPACC_OUT_COST of the same step, x[0] is EEPACC_OUT_AQP and x[1..4] are the four slack outputs.
+ *
+ * The build is asynchronous on stream.  It reads no solver state of the handle (warm start, loop counters, carry) and writes
+ * none: a build between two ABMPC calls leaves their results bit for bit unchanged.  One workgroup per instance writes every
+ * entry, zeros included (no memset, no atomics): the arrays do not depend on B or on timing.  EEPACC_EINVAL, with a message
+ * that names the argument: a NULL buffer, B < 0 or B > max_batch.  EEPACC_ENOTSUP: a handle of eepacc_create_classes (nC can
+ * differ per class) and a handle created with bl_mode 1 or 2.  B = 0 returns EEPACC_OK.
+ * Not built: the FBMPC problem (its build kernel updates the carried A22 / D2 state; exposing it needs a variant that does
+ * not), BLMPC and TVMPC handles, class handles, the formulations of solverToUse 0 (dynamics kept as rows) and 2 (HPIPM).
+ * Throughput: not measured (tools/gpu_ab_build_bench.py times the build against a plain device fill of the same bytes). */
+int  eepacc_ab_qp_size(const eepacc_handle* h, int* nV, int* nC);
+int  eepacc_ab_qp_rows(const eepacc_handle* h, int32_t* stage, int32_t* type);
+int  eepacc_ab_build_qp(eepacc_handle* h, int B,
+                        const double* s, const double* v, const double* a_prev, const double* t0,
+                        const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                        double* H, double* g, double* A, double* lba, double* uba, void* stream);
+
 /* B3 -- dense QP operator: the call
  *   sol = QPsolver('h',H,'g',c,'a',G,'lbx',z_lb,'ubx',z_ub,'lba',g_lb,'uba',g_ub)
  * of ABO/RunOpt_ABMPC.m:252 and ABO/RunOpt_FBMPC.m:278 (CasADi conic, CAS/+casadi/conic.m:951-966)
