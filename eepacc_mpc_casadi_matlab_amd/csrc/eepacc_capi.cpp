@@ -1,5 +1,5 @@
-// eepacc_capi.cpp -- C-ABI of libeepacc (include/eepacc.h): handle management, validation of the
-// reference settings, one-time host precomputation, kernel launches.  Compiled with hipcc.
+// eepacc_capi.cpp -- C-ABI of libeepacc (include/eepacc.h): handle management, argument checks, kernel launches.  The
+// translation of the reference settings (validation, one-time host precomputation) is eepacc_cfg.cpp.  Compiled with hipcc.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -9,6 +9,7 @@
 #include <vector>
 #include <memory>
 #include "eepacc_device.h"
+#include "eepacc_cfg.h"
 #include "eepacc_ab.h"
 #include "eepacc_ab_build.h"
 #include "eepacc_qp_dense.h"
@@ -24,7 +25,7 @@ using eepacc::FollowCfg;
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) { g_err = msg; return code; }
-namespace eepacc { int set_error(int code, const std::string& msg) { return fail(code, msg); } }   // other translation units (eepacc_nlp.hip)
+namespace eepacc { int set_error(int code, const std::string& msg) { return fail(code, msg); } }   // other translation units (eepacc_cfg.cpp, eepacc_nlp.hip)
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(EEPACC_EDEVICE, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 
 // Device memory owned by a handle or by a host-pointer wrapper: move-only, freed with its owner.
@@ -98,229 +99,16 @@ extern "C" int eepacc_version(void) { return EEPACC_VERSION; }
 extern "C" int eepacc_sizeof_settings(void) { return (int)sizeof(eepacc_settings); }
 extern "C" int eepacc_sizeof_vehicle(void) { return (int)sizeof(eepacc_vehicle); }
 
-// symmetric positive definite inverse (Gauss-Jordan in long double; N <= 63)
-static bool spd_inverse(std::vector<long double>& A, int n) {
-    std::vector<long double> I((size_t)n * n, 0.0L);
-    for (int i = 0; i < n; ++i) I[(size_t)i * n + i] = 1.0L;
-    for (int k = 0; k < n; ++k) {
-        long double d = A[(size_t)k * n + k];
-        if (!(d > 0.0L)) return false;
-        for (int j = 0; j < n; ++j) { A[(size_t)k * n + j] /= d; I[(size_t)k * n + j] /= d; }
-        for (int i = 0; i < n; ++i) {
-            if (i == k) continue;
-            long double f = A[(size_t)i * n + k];
-            if (f == 0.0L) continue;
-            for (int j = 0; j < n; ++j) { A[(size_t)i * n + j] -= f * A[(size_t)k * n + j]; I[(size_t)i * n + j] -= f * I[(size_t)k * n + j]; }
-        }
-    }
-    A.swap(I);
-    return true;
-}
-
-static int build_cfg(const eepacc_settings* S, const eepacc_vehicle* V, DevCfg& C, std::vector<double>& Hinv) {
-    memset(&C, 0, sizeof(C));
-    const int N = S->N_hor;
-    if (N < 2 || N > eepacc::kMaxN) return fail(EEPACC_EINVAL, "N_hor must be in [2, 63]");
-    if (!S->Tvec) return fail(EEPACC_EINVAL, "Tvec is NULL");
-    // solverToUse 0 (sparse qpOASES) states the same QP as 1 (dense qpOASES) with the dynamics kept as
-    // equality rows (CreateQP_AB.m:227-246): same feasible set and objective, hence the same minimiser and
-    // the same kernels.  2 (HPIPM) is a different problem (hard bounds a in [-8, 8], :79-99).
-    if (S->solverToUse != 0 && S->solverToUse != 1)
-        return fail(EEPACC_ENOTSUP, "solverToUse == 2 (HPIPM formulation, ABO/Settings.m:114) is not built");
-    if (S->paramEstSetting < 0 || S->paramEstSetting > 2) return fail(EEPACC_EINVAL, "paramEstSetting must be 0, 1 or 2");
-    if (S->TVestSetting != 0 && S->TVestSetting != 1) return fail(EEPACC_EINVAL, "TVestSetting must be 0 or 1");
-    if (S->n_speedLim < 1 || S->n_speedLim > eepacc::kMaxKnots || S->n_curv < 1 || S->n_curv > eepacc::kMaxKnots ||
-        S->n_slope < 1 || S->n_slope > eepacc::kMaxKnots || S->n_stop < 0 || S->n_stop > eepacc::kMaxStops ||
-        S->n_TL < 0 || S->n_TL > eepacc::kMaxTL)
-        return fail(EEPACC_EINVAL, "route table sizes out of range");
-    if (S->N_integratePlant < 1) return fail(EEPACC_EINVAL, "N_integratePlant < 1");
-    if (S->ab_fuel_term < 0 || S->ab_fuel_term > 2) return fail(EEPACC_EINVAL, "ab_fuel_term must be 0, 1 or 2");
-    if (S->ab_fuel_term == 2 && !S->bl_mode) {
-        // ICE-map fuel term (CreateQP_AB.m:154-159): step-varying Hessian, built (folded for Mb) and inverted in LDS by its
-        // own kernel variant, at every N and with or without move blocking
-        if (!(V->tau_fd > 0.0) || !(V->eta_drive > 0.0) || !(V->R_w > 0.0))
-            return fail(EEPACC_EINVAL, "ab_fuel_term == 2 needs V.tau_fd, V.eta_drive, V.R_w > 0 (SetVehicleParameters.m:92,100-101)");
-        for (int g2 = 0; g2 < 8; ++g2) if (!(V->tau_gb[g2] > 0.0)) return fail(EEPACC_EINVAL, "ab_fuel_term == 2 needs positive gear ratios V.tau_gb");
-        for (int g2 = 1; g2 < 7; ++g2) if (!(V->upSpd[g2] >= V->upSpd[g2 - 1])) return fail(EEPACC_EINVAL, "V.upSpd must ascend");
-    }
-    C.N = N;
-    C.ab_fuel_term = S->ab_fuel_term; C.ab_route_rows = S->ab_route_rows;
-    C.paramEstSetting = S->paramEstSetting; C.TVestSetting = S->TVestSetting;
-    C.N_integratePlant = S->N_integratePlant;
-    C.max_iter = 60 * N + 200;
-    C.const_T = 1;
-    C.tau[0] = 0.0;
-    for (int k = 0; k < N; ++k) {
-        if (!(S->Tvec[k] > 0.0)) return fail(EEPACC_EINVAL, "Tvec entries must be positive");
-        C.Tvec[k] = S->Tvec[k];
-        C.tau[k + 1] = C.tau[k] + S->Tvec[k];
-        if (S->Tvec[k] != S->Tvec[0]) C.const_T = 0;
-        if (S->Mb && S->Mb[k] != 0) C.mb_any = 1;
-    }
-    if (C.mb_any) {
-        // block structure: stage k with Mb[k] = 1 repeats the acceleration of the previous stage
-        if (S->Mb[0] != 0) return fail(EEPACC_EINVAL, "Mb[0] must be 0 (the first stage has no predecessor in the horizon)");
-        int maxlen = 1;
-        for (int k = 0, lead = 0; k < N; ++k) {
-            if (S->Mb[k] != 0 && S->Mb[k] != 1) return fail(EEPACC_EINVAL, "Mb entries must be 0 or 1");
-            if (S->Mb[k] == 0) lead = k;
-            C.mb_lead[k] = lead;
-            C.mb_end[lead] = k;
-            if (k - lead + 1 > maxlen) maxlen = k - lead + 1;
-        }
-        for (int k = 0; k < N; ++k) if (C.mb_lead[k] != k) C.mb_end[k] = k;
-        C.mb_lead[N] = N; C.mb_end[N] = N;
-        C.mb_maxlen = maxlen;
-    } else {
-        for (int k = 0; k <= N; ++k) { C.mb_lead[k] = k; C.mb_end[k] = k; }
-        C.mb_maxlen = 1;
-    }
-    C.fb_row0[0] = 0;
-    for (int k = 0; k < N; ++k) {
-        C.mb_mask[k] = (S->Mb && S->Mb[k] == 1) ? 1 : 0;
-        C.fb_row0[k + 1] = C.fb_row0[k] + 26 + 2 * C.mb_mask[k];
-    }
-    C.mb_mask[N] = 0;
-    C.w_FC = S->ab_fuel_term ? S->W_AB[0] : 0.0;
-    C.w_a = S->W_AB[1]; C.w_j = S->W_AB[2]; C.w_v = S->W_AB[3]; C.w_h = S->W_AB[4]; C.w_s = S->W_AB[5]; C.w_f = S->W_AB[6];
-    // default: above the noise level of the closed loop at standstill -- ABMPC 1e-10; the baseline LP (solved with the
-    // curvature 1e-4) leaves 2e-9 on plain stops and up to 1.5e-6 when its slack is in play (use case 12)
-    C.state_tol = S->state_bound_tol > 0.0 ? S->state_bound_tol : (S->bl_mode ? 1e-5 : 1e-9);
-    double bl_travel = 0.0;
-    if (S->bl_mode) {
-        // the LP needs about 13 working-set changes per warm step and 3N from cold (871 saved steps at N = 20 as cold QPs:
-        // mean 58, 99th percentile 113, maximum 270); a solve that is still going after 15N + 60 is cycling on a degenerate
-        // vertex and is cut off there
-        C.max_iter = 15 * N + 60;
-        if (const char* ev = getenv("EEPACC_DEBUG_BL_MAX_ITER")) C.max_iter = atoi(ev);
-        // RunOpt_BLMPC: CreateQP_BL.m:36-39,131-148  W_BL = [w_v (travel incentive), w_a, w_j, w_f]
-        // bl_mode = 2: RunOpt_TVMPC, CreateQP_TV.m:36-39 W_TV = [w_v, w_a, w_j, w_f] in W_BL, TV_*_Lim* in BL_*_Lim*
-        if (S->bl_mode != 1 && S->bl_mode != 2) return fail(EEPACC_EINVAL, "bl_mode must be 0, 1 (RunOpt_BLMPC) or 2 (RunOpt_TVMPC)");
-        if (C.mb_any) return fail(EEPACC_ENOTSUP, "the baseline controller has no move blocking (RunOpt_BLMPC.m)");
-        if (S->bl_mode == 2 && !C.const_T)
-            return fail(EEPACC_EINVAL, "bl_mode = 2: Tvec must be uniform (TV_Ts, CreateQP_TV.m:29)");
-        if (S->W_BL[0] < 0 || S->W_BL[1] < 0 || S->W_BL[2] < 0 || !(S->W_BL[3] > 0))
-            return fail(EEPACC_EINVAL, "W_BL weights must be non-negative (w_f positive)");
-        C.bl_mode = S->bl_mode;
-        C.ab_fuel_term = 0; C.ab_route_rows = 1;            // CreateQP_BL.m:264-288: the four speed caps are always present
-        C.w_FC = 0.0; C.w_a = S->W_BL[1]; C.w_j = S->W_BL[2]; C.w_f = S->W_BL[3];
-        C.w_v = 0.0; C.w_s = 0.0; C.w_h = 1.0;              // groups that do not exist in the baseline QP
-        bl_travel = S->W_BL[0];
-        C.bl_eps = (C.w_a == 0.0 && C.w_j == 0.0) ? (S->bl_lp_eps > 0.0 ? S->bl_lp_eps : 0.1) : 0.0;
-        if (const char* ev = getenv("EEPACC_DEBUG_BL_EPS")) { if (C.bl_eps > 0.0 && atof(ev) > 0.0) C.bl_eps = atof(ev); }
-        C.bl_prox_max = C.bl_eps > 0.0 ? (S->bl_prox_iter == 0 ? 40 : (S->bl_prox_iter < 0 ? 0 : S->bl_prox_iter)) : 0;
-        C.bl_aLo = S->BL_a_LimLowVel; C.bl_aHi = S->BL_a_LimHighVel; C.bl_jLo = S->BL_j_LimLowVel; C.bl_jHi = S->BL_j_LimHighVel;
-        if (!(C.bl_aLo > 0) || !(C.bl_aHi > 0) || !(C.bl_jLo > 0) || !(C.bl_jHi > 0))
-            return fail(EEPACC_EINVAL, "baseline acceleration / jerk limits must be positive");
-    } else if (!(C.w_a > 0.0) || !(C.w_h > 0.0) || C.w_v < 0 || C.w_s < 0 || C.w_f < 0 || C.w_j < 0)
-        return fail(EEPACC_EINVAL, "W_AB weights must be positive (w_a, w_h) / non-negative");
-    C.tau_min = S->tau_min; C.h_min = S->h_min; C.s_goal = S->s_goal;
-    C.tConstACC_ego = S->tConstACC_ego; C.tConstACC_tar = S->tConstACC_tar;
-    C.m = V->m; C.lambda = V->lambda; C.g = V->g; C.zeta_a = V->zeta_a; C.c_r = V->c_r; C.mu = V->mu; C.L = V->L;
-    C.L_f = V->L_f; C.h_g = V->h_g; C.phi = V->phi; C.T_m_max = V->T_m_max; C.P_m_max = V->P_m_max;
-    C.eta_TF = V->eta_TF; C.omega_m_r = V->omega_m_r; C.v_max = V->v_max;
-    C.p01 = V->p01; C.p10 = V->p10; C.F2 = V->F2;
-    C.cq = C.w_FC * V->p01 * V->F2;
-    C.glin_v = C.bl_mode ? -bl_travel : C.w_FC * V->p10;
-    C.glin_a = C.w_FC * V->p01 * V->lambda * V->m;
-    if (C.ab_fuel_term == 2) {
-        // per stage: cq_k = ice_cq / tau_k, lv_k = ice_lv tau_k, la_k = ice_la / tau_k (CreateQP_AB.m:154-159)
-        C.cq = 0.0; C.glin_v = 0.0; C.glin_a = 0.0;
-        C.ice_cq = C.w_FC * V->k01 * V->F2 * V->R_w / V->tau_fd / V->eta_drive;
-        C.ice_lv = C.w_FC * V->k10 / V->R_w * V->tau_fd;
-        C.ice_la = C.w_FC * V->k01 * V->lambda * V->m * V->R_w / V->tau_fd / V->eta_drive;
-        for (int g2 = 0; g2 < 7; ++g2) C.ice_up[g2] = V->upSpd[g2];
-        for (int g2 = 0; g2 < 8; ++g2) C.ice_gb[g2] = V->tau_gb[g2];
-    }
-    C.n_speedLim = S->n_speedLim; C.n_curv = S->n_curv; C.n_slope = S->n_slope; C.n_stop = S->n_stop; C.n_TL = S->n_TL;
-    for (int i = 0; i < S->n_speedLim; ++i) { C.s_speedLim[i] = S->s_speedLim[i]; C.v_speedLim[i] = S->v_speedLim[i]; }
-    const double alpha = S->alpha_TTL;
-    for (int i = 0; i < S->n_curv; ++i) {
-        C.s_curv[i] = S->s_curv[i];
-        C.vcurv_tab[i] = alpha * pow(fabs(S->curvature[i]), -1.0 / 3.0);   // EstimateRouteAndComfortBounds.m:106,108
-    }
-    C.const_slope = 1;
-    for (int i = 0; i < S->n_slope; ++i) {
-        C.s_slope[i] = S->s_slope[i]; C.slope[i] = S->slope[i];
-        if (S->slope[i] != S->slope[0]) C.const_slope = 0;
-    }
-    C.theta0 = S->slope[0]; C.sin_theta0 = sin(C.theta0); C.cos_theta0 = cos(C.theta0);
-    for (int i = 0; i < S->n_stop; ++i) C.stopLoc[i] = S->stopLoc[i];
-    for (int i = 0; i < 4 * S->n_TL; ++i) C.TLLoc[i] = S->TLLoc[i];
-    C.stopRefDist = S->stopRefDist; C.stopRefVelSlope = S->stopRefVelSlope; C.stopVel = S->stopVel;
-    C.TLstopVel = S->TLstopVel; C.TLStopRegionSize = S->TLStopRegionSize;
-    for (int i = 0; i < 21; ++i) C.b5[i] = S->b_fifthOrder[i];
-    for (int i = 0; i < 7; ++i) C.fb_w[i] = S->W_FB[i];
-    for (int i = 0; i < 6; ++i) C.b_quadr[i] = S->b_quadr[i];
-    C.FBuseTaylor = S->FBuseTaylor ? 1 : 0;
-    // a-space Hessian of the condensed objective (step invariant for AB):
-    //   H = 2 cq Sv'Sv + 2 w_a I + jerk tridiagonal (CreateQP_AB.m:162-180 through Psi)
-    std::vector<long double> H((size_t)N * N, 0.0L);
-    for (int i = 0; i < N; ++i)
-        for (int j = 0; j < N; ++j) {
-            // sum over stages k = max(i,j)+1 .. N-1 of T_i T_j
-            int cnt = N - 1 - (i > j ? i : j);
-            if (cnt > 0) H[(size_t)i * N + j] += 2.0L * C.cq * C.Tvec[i] * C.Tvec[j] * cnt;
-        }
-    for (int k = 0; k < N; ++k) {
-        H[(size_t)k * N + k] += 2.0L * C.w_a + (long double)C.bl_eps;
-        long double qj = 2.0L * C.w_j / ((long double)C.Tvec[k] * C.Tvec[k]);
-        H[(size_t)k * N + k] += qj;
-        if (k > 0) {
-            H[(size_t)(k - 1) * N + (k - 1)] += qj;
-            H[(size_t)k * N + (k - 1)] -= qj;
-            H[(size_t)(k - 1) * N + k] -= qj;
-        }
-    }
-    if (C.mb_any) {
-        // reduced variables (one acceleration per block): Hbar = E'HE on the leaders, identity on the rest
-        std::vector<long double> Hb((size_t)N * N, 0.0L);
-        for (int i = 0; i < N; ++i)
-            for (int j = 0; j < N; ++j)
-                Hb[(size_t)C.mb_lead[i] * N + C.mb_lead[j]] += H[(size_t)i * N + j];
-        for (int k = 0; k < N; ++k) if (C.mb_lead[k] != k) Hb[(size_t)k * N + k] = 1.0L;
-        H.swap(Hb);
-    }
-    if (!spd_inverse(H, N)) return fail(EEPACC_EINVAL, "condensed Hessian is not positive definite");
-    Hinv.assign((size_t)N * N, 0.0);
-    for (int i = 0; i < N; ++i)
-        for (int j = 0; j < N; ++j)
-            Hinv[(size_t)i * N + j] = (double)(0.5L * (H[(size_t)i * N + j] + H[(size_t)j * N + i]));
-    if (eepacc::ab_smem_bytes(N) > 157 * 1024)
+// The settings as the kernels read them: eepacc::build_cfg (eepacc_cfg.cpp, host only), then the one refusal that needs the
+// kernels' own LDS layout.
+static int build_cfg_fit(const eepacc_settings* S, const eepacc_vehicle* V, DevCfg& C, std::vector<double>& Hinv) {
+    if (const int rc = eepacc::build_cfg(S, V, C, Hinv)) return rc;
+    if (eepacc::ab_smem_bytes(C.N) > 157 * 1024)
         return fail(EEPACC_ENOTSUP, "N_hor too large for the LDS layout of this build");
     return EEPACC_OK;
 }
-
-// What eepacc_kpis reads of a class (validated by build_cfg before): the power fit and driveline of the energy, the fuel
-// map and coast-down terms of ABO/Custom_plots.m:73-107 and the speed-limit table of ABO/Main.m:133.
-static KpiCfg build_kpi_cfg(const eepacc_settings* S, const eepacc_vehicle* V) {
-    KpiCfg K;
-    memset(&K, 0, sizeof(K));
-    K.Ts = S->Tvec[0]; K.phi = V->phi;
-    for (int i = 0; i < 21; ++i) K.b5[i] = S->b_fifthOrder[i];
-    K.lm = V->lambda * V->m; K.F0 = V->F0; K.F2 = V->F2; K.R_w = V->R_w;
-    K.p00 = V->p00; K.p10 = V->p10; K.p01 = V->p01;
-    K.n_speedLim = S->n_speedLim;
-    for (int i = 0; i < S->n_speedLim; ++i) { K.s_speedLim[i] = S->s_speedLim[i]; K.v_speedLim[i] = S->v_speedLim[i]; }
-    return K;
-}
-
-// What eepacc_follow_kpis reads of a class: the minimum-headway policy of ABO/Main.m:687, the power surface of cost_P and
-// the weights of the reference's cost_* series, one row per EEPACC_FKPI_W_*, in the order w_P, w_a, w_j, w_v, w_h, w_s, w_f.
-// RunOpt_ABMPC.m:383-388 takes W(1..5) of the user's W_AB with w_f = W(5); ORIG's six entries are stored behind a leading
-// zero (ab_fuel_term = 0), ABO's seven as they are, so that W(1) is w_FC there, as in the reference's own cost_a.
-static FollowCfg build_follow_cfg(const eepacc_settings* S, const eepacc_vehicle* V) {
-    FollowCfg F;
-    memset(&F, 0, sizeof(F));
-    F.Ts = S->Tvec[0]; F.h_min = S->h_min; F.tau_min = S->tau_min; F.phi = V->phi;
-    for (int i = 0; i < 21; ++i) F.b5[i] = S->b_fifthOrder[i];
-    const double* W = S->W_AB + (S->ab_fuel_term ? 0 : 1);
-    for (int i = 0; i < 5; ++i) F.w[EEPACC_FKPI_W_AB][1 + i] = W[i];
-    F.w[EEPACC_FKPI_W_AB][6] = W[4];
-    for (int i = 0; i < 7; ++i) F.w[EEPACC_FKPI_W_FB][i] = S->W_FB[i];
-    for (int i = 1; i < 7; ++i) F.w[EEPACC_FKPI_W_NONE][i] = 1.0;
-    return F;
-}
+using eepacc::build_kpi_cfg;
+using eepacc::build_follow_cfg;
 
 // The device side of a handle.  Cs: one validated DevCfg per class with its inverse Hessian in Hinv (N x N each, class after
 // class); classes: the handle of eepacc_create_classes, which keeps a class map and runs AbVariant::Classes, also with one class.
@@ -390,7 +178,7 @@ extern "C" int eepacc_create(eepacc_handle** out, const eepacc_settings* S, cons
     *out = nullptr;
     std::vector<DevCfg> Cs(1);
     std::vector<double> Hinv;
-    int rc = build_cfg(S, V, Cs[0], Hinv);
+    int rc = build_cfg_fit(S, V, Cs[0], Hinv);
     if (rc != EEPACC_OK) return rc;
     return create_on_device(out, Cs, Hinv, {build_kpi_cfg(S, V)}, {build_follow_cfg(S, V)}, false, device, max_batch);
 }
@@ -418,7 +206,7 @@ extern "C" int eepacc_create_classes(eepacc_handle** out, const eepacc_settings*
         if (S[k].Mb)
             for (int j = 0; j < N; ++j)
                 if (S[k].Mb[j] != 0) return fail(EEPACC_ENOTSUP, who + "Mb[" + std::to_string(j) + "] != 0: move blocking has no class variant");
-        const int rc = build_cfg(&S[k], &V[k], Cs[(size_t)k], Hk);
+        const int rc = build_cfg_fit(&S[k], &V[k], Cs[(size_t)k], Hk);
         if (rc != EEPACC_OK) return fail(rc, who + g_err);
         for (int j = 0; j < N; ++j)
             if (Cs[(size_t)k].Tvec[j] != Cs[0].Tvec[j])
@@ -728,6 +516,35 @@ static int qp_workspace(eepacc_handle* h, int grid, int nV) {
     return EEPACC_OK;
 }
 
+// What the operator's entry points do before they fill their argument struct, in this order: the handle, the sizes (nR: 1
+// where the entry point has none), B = 0, the limits, the entry point's own buffers (missing: one of them is NULL), the LDS
+// fit; then device, grid and workspace.  *grid stays 0 where there is nothing to launch (B = 0, or a refusal).
+static int qp_begin(eepacc_handle* h, const char* name, int B, int nV, int nC, int nR, bool missing, int* grid) {
+    const std::string who = std::string(name) + ": ";
+    *grid = 0;
+    if (!h) return fail(EEPACC_EINVAL, "NULL handle");
+    if (const int rc = not_classes(h, name)) return rc;
+    if (B < 0 || nV < 1 || nC < 0 || nR < 1) return fail(EEPACC_EINVAL, who + "bad sizes");
+    if (B == 0) return EEPACC_OK;
+    if (nV > EEPACC_QP_MAX_NV || nC > EEPACC_QP_MAX_NC)
+        return fail(EEPACC_EINVAL, who + "nV/nC above EEPACC_QP_MAX_NV/NC");
+    if (missing) return fail(EEPACC_EINVAL, who + "NULL buffer");
+    if (eepacc_qp_dense_lds_bytes(nV, nC) > 160 * 1024) return fail(EEPACC_EINVAL, who + "problem does not fit LDS");
+    HIPCHK(hipSetDevice(h->device));
+    const int g = qp_grid(h, B);
+    if (const int rc = qp_workspace(h, g, nV)) return rc;
+    *grid = g;
+    return EEPACC_OK;
+}
+
+// The tail of the preamble, which fb_one_step shares: workspace and work counter into the argument struct (a.nV set), the
+// counter zeroed on the stream of the launch.
+template <class Args> static int qp_arm(eepacc_handle* h, Args& a, hipStream_t stream) {
+    a.ws = h->d_qp_ws; a.ws_stride = eepacc_qp_dense_ws_doubles(a.nV); a.counter = h->d_qp_counter;
+    HIPCHK(hipMemsetAsync(h->d_qp_counter, 0, sizeof(int), stream));
+    return EEPACC_OK;
+}
+
 // both entry points of the operator; dual = nullptr: eepacc_qp_solve_batched
 struct QpDual {
     const int8_t *ws0_a, *ws0_x;
@@ -739,29 +556,18 @@ struct QpDual {
 static int qp_solve(eepacc_handle* h, const char* name, int B, int nV, int nC, const double* H, const double* g,
                     const double* A, const double* lba, const double* uba, const double* lbx, const double* ubx,
                     const double* x0, double* x, double* cost, int32_t* status, const QpDual* dual, void* stream) {
-    const std::string who = std::string(name) + ": ";
-    if (!h) return fail(EEPACC_EINVAL, "NULL handle");
-    if (const int rc = not_classes(h, name)) return rc;
-    if (B < 0 || nV < 1 || nC < 0) return fail(EEPACC_EINVAL, who + "bad sizes");
-    if (B == 0) return EEPACC_OK;
-    if (nV > EEPACC_QP_MAX_NV || nC > EEPACC_QP_MAX_NC)
-        return fail(EEPACC_EINVAL, who + "nV/nC above EEPACC_QP_MAX_NV/NC");
-    if (!H || !g || !x || (nC > 0 && !A)) return fail(EEPACC_EINVAL, who + "NULL buffer");
-    if (eepacc_qp_dense_lds_bytes(nV, nC) > 160 * 1024) return fail(EEPACC_EINVAL, who + "problem does not fit LDS");
-    HIPCHK(hipSetDevice(h->device));
-    int grid = qp_grid(h, B);
-    int rc = qp_workspace(h, grid, nV);
-    if (rc != EEPACC_OK) return rc;
+    int grid;
+    const int rc = qp_begin(h, name, B, nV, nC, 1, !H || !g || !x || (nC > 0 && !A), &grid);
+    if (rc != EEPACC_OK || !grid) return rc;
     eepacc_qp_args a;
     a.B = B; a.nV = nV; a.nC = nC; a.H = H; a.g = g; a.A = A; a.lba = lba; a.uba = uba; a.lbx = lbx; a.ubx = ubx;
     a.x0 = x0; a.x = x; a.cost = cost; a.status = status; a.iters = (B <= h->max_batch) ? h->d_iters : nullptr;
-    a.ws = h->d_qp_ws; a.ws_stride = eepacc_qp_dense_ws_doubles(nV); a.rho_rel = 0.0; a.max_prox = 0;
-    a.counter = h->d_qp_counter; a.rho_k = nullptr;
+    a.rho_rel = 0.0; a.max_prox = 0; a.rho_k = nullptr;
     if (dual) {
         a.ws0_a = dual->ws0_a; a.ws0_x = dual->ws0_x; a.lam_a = dual->lam_a; a.lam_x = dual->lam_x;
         a.ws_a = dual->ws_a; a.ws_x = dual->ws_x; a.iters = dual->iters;
     }
-    HIPCHK(hipMemsetAsync(h->d_qp_counter, 0, sizeof(int), (hipStream_t)stream));
+    if (const int rc2 = qp_arm(h, a, (hipStream_t)stream)) return rc2;
     HIPCHK(dual ? eepacc_qp_dense_launch_dual(a, grid, (hipStream_t)stream) : eepacc_qp_dense_launch(a, grid, (hipStream_t)stream));
     return EEPACC_OK;
 }
@@ -786,25 +592,14 @@ extern "C" int eepacc_qp_kkt_solve_batched(eepacc_handle* h, int B, int nV, int 
                                            const int8_t* ws_a, const int8_t* ws_x, const double* r_p, const double* r_a,
                                            const double* r_x, double* p, double* q_a, double* q_x, int32_t* status,
                                            void* stream) {
-    const char* name = "eepacc_qp_kkt_solve_batched";
-    const std::string who = std::string(name) + ": ";
-    if (!h) return fail(EEPACC_EINVAL, "NULL handle");
-    if (const int rc = not_classes(h, name)) return rc;
-    if (B < 0 || nV < 1 || nC < 0 || nR < 1) return fail(EEPACC_EINVAL, who + "bad sizes");
-    if (B == 0) return EEPACC_OK;
-    if (nV > EEPACC_QP_MAX_NV || nC > EEPACC_QP_MAX_NC)
-        return fail(EEPACC_EINVAL, who + "nV/nC above EEPACC_QP_MAX_NV/NC");
-    if (!H || !r_p || !p || (nC > 0 && !A)) return fail(EEPACC_EINVAL, who + "NULL buffer");
-    if (eepacc_qp_dense_lds_bytes(nV, nC) > 160 * 1024) return fail(EEPACC_EINVAL, who + "problem does not fit LDS");
-    HIPCHK(hipSetDevice(h->device));
-    const int grid = qp_grid(h, B);
-    const int rc = qp_workspace(h, grid, nV);
-    if (rc != EEPACC_OK) return rc;
+    int grid;
+    const int rc = qp_begin(h, "eepacc_qp_kkt_solve_batched", B, nV, nC, nR, !H || !r_p || !p || (nC > 0 && !A), &grid);
+    if (rc != EEPACC_OK || !grid) return rc;
     eepacc_qp_kkt_args a;
     a.B = B; a.nV = nV; a.nC = nC; a.nR = nR; a.H = H; a.A = A; a.ws_a = nC > 0 ? ws_a : nullptr; a.ws_x = ws_x;
     a.r_p = r_p; a.r_a = nC > 0 ? r_a : nullptr; a.r_x = r_x; a.p = p; a.q_a = nC > 0 ? q_a : nullptr; a.q_x = q_x;
-    a.status = status; a.counter = h->d_qp_counter; a.ws = h->d_qp_ws; a.ws_stride = eepacc_qp_dense_ws_doubles(nV);
-    HIPCHK(hipMemsetAsync(h->d_qp_counter, 0, sizeof(int), (hipStream_t)stream));
+    a.status = status;
+    if (const int rc2 = qp_arm(h, a, (hipStream_t)stream)) return rc2;
     HIPCHK(eepacc_qp_kkt_launch(a, grid, (hipStream_t)stream));
     return EEPACC_OK;
 }
@@ -865,9 +660,9 @@ static int fb_one_step(eepacc_handle* h, int B, int mode, const double* s, const
         q.lbx = nullptr; q.ubx = nullptr;
         q.x0 = h->fb.x0 + (size_t)b0 * nV; q.x = h->fb.x + (size_t)b0 * nV; q.cost = h->fb.cost + b0;
         q.status = h->fb.qpstat + b0; q.iters = (B <= h->max_batch) ? h->d_iters + b0 : nullptr;
-        q.ws = h->d_qp_ws; q.ws_stride = eepacc_qp_dense_ws_doubles(nV); q.rho_rel = 0.0; q.max_prox = 0;
-        q.counter = h->d_qp_counter; q.rho_k = h->fb.rhok + b0;
-        HIPCHK(hipMemsetAsync(h->d_qp_counter, 0, sizeof(int), stream));
+        q.rho_rel = 0.0; q.max_prox = 0; q.rho_k = h->fb.rhok + b0;
+        rc = qp_arm(h, q, stream);
+        if (rc != EEPACC_OK) return rc;
         HIPCHK(eepacc_qp_dense_launch(q, grid, stream));
     }
     eepacc::eepacc_fb_apply_args p;

@@ -6,18 +6,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "eepacc_kpis.h"
+#include "eepacc_follow_cfg.h"    // FollowCfg: what the operator reads of a settings class
 
 namespace eepacc {
-
-// What the operator reads of a settings class: a table of the handle's own, FollowCfg[n_classes], beside DevCfg and KpiCfg
-// (whose layouts and the kernels that take them stay as they are).
-struct FollowCfg {
-    double Ts;                    // Tvec[0]
-    double h_min, tau_min;        // minimum-headway policy max(h_min, v tau_min), ABO/Main.m:687
-    double phi;                   // rpm = 30 / pi * v * phi
-    double b5[21];                // fifth-order power surface
-    double w[3][7];               // [EEPACC_FKPI_W_*][w_P, w_a, w_j, w_v, w_h, w_s, w_f]
-};
 
 // Geometry of k_kpis (kKpiWaves, kKpiMinSlice, kpi_slice_len).  A slice hands the join 12 doubles (four minima, one
 // maximum, seven sums) and 3 ints (first index of the smallest gap, two counts) per lane through LDS.

@@ -6,20 +6,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "eepacc_device.h"
+#include "eepacc_kpis_cfg.h"      // KpiCfg: what the key figures read of a settings class
 
 namespace eepacc {
-
-// What the key figures read of a settings class: a table of the handle's own, KpiCfg[n_classes], beside DevCfg (whose
-// layout and the kernels that take it stay as they are).
-struct KpiCfg {
-    double Ts;                    // Tvec[0]
-    double phi;                   // rpm = 30 / pi * v * phi
-    double b5[21];                // fifth-order power surface
-    double lm, F0, F2, R_w;       // wheel torque TW = max(0, (lambda m a + F0 + F2 v^2) R_w); lm = lambda * m
-    double p00, p10, p01;         // fuel flow FC = max(0.25, p00 + p10 v + p01 TW) [g/s]
-    int32_t n_speedLim, pad;
-    double s_speedLim[kMaxKnots], v_speedLim[kMaxKnots];
-};
 
 // Geometry: a workgroup of kKpiWaves waves serves 64 consecutive instances (lane = instance); wave w reduces the steps
 // [w Ls, (w + 1) Ls), Ls = max(kKpiMinSlice, ceil(n_steps / kKpiWaves)).
