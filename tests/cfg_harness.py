@@ -56,7 +56,7 @@ class Built:
 
 class Harness:
     INT_FIELDS = ("N", "const_T", "const_slope", "mb_any", "max_iter", "bl_mode", "mb_lead", "mb_end", "mb_maxlen", "fb_row0",
-                  "mb_mask")
+                  "mb_mask", "N_integratePlant", "n_TL")
 
     def __init__(self, lib: str):
         self.lib = C.CDLL(lib)

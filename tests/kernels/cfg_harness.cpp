@@ -18,7 +18,8 @@ struct Field { const char* name; size_t offset, bytes; };
 static const Field kFields[] = {
     CH_FIELD(N), CH_FIELD(const_T), CH_FIELD(const_slope), CH_FIELD(mb_any), CH_FIELD(max_iter), CH_FIELD(Tvec), CH_FIELD(tau),
     CH_FIELD(w_a), CH_FIELD(w_j), CH_FIELD(cq), CH_FIELD(bl_eps), CH_FIELD(bl_mode), CH_FIELD(Hinv), CH_FIELD(pred), CH_FIELD(hb),
-    CH_FIELD(mb_lead), CH_FIELD(mb_end), CH_FIELD(mb_maxlen), CH_FIELD(fb_row0), CH_FIELD(mb_mask)};
+    CH_FIELD(mb_lead), CH_FIELD(mb_end), CH_FIELD(mb_maxlen), CH_FIELD(fb_row0), CH_FIELD(mb_mask),
+    CH_FIELD(N_integratePlant), CH_FIELD(n_TL)};
 
 extern "C" {
 
