@@ -43,6 +43,19 @@ AB_BUILD_ARGTYPES = {
     "eepacc_ab_build_qp": [C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p] * 5 + [C.c_void_p],
 }
 
+# enum EEPACC_FB_ROW_*: the row types of eepacc_fb_qp_rows, ascending in the order of the rows within a stage
+FB_ROW_TYPES = ["s", "v", "fm", "fb", "xi_v", "xi_h", "xi_s", "xi_f", "blocked_fm", "blocked_fb", "tm_min", "tm_max",
+                "axle_min", "axle_max", "fric_max", "fric_min", "a_max", "a_min", "j_max", "j_min",
+                "v_lim", "v_curv", "v_stop", "v_tl", "v_inc", "safe1", "safe2", "hwp"]
+FB_ROW = {name: i for i, name in enumerate(FB_ROW_TYPES)}
+
+# the same for an FBMPC step: the seven inputs, the model A22, D2 (or None), the five outputs, A22_used, D2_used (or None)
+FB_BUILD_ARGTYPES = {
+    "eepacc_fb_qp_size": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "eepacc_fb_qp_rows": [C.c_void_p, c_int32_p, c_int32_p],
+    "eepacc_fb_build_qp": [C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p] * 2 + [C.c_void_p] * 5 + [C.c_void_p] * 2 + [C.c_void_p],
+}
+
 _VEH_FIELDS = ["m", "A_f", "c_d", "L", "h_g", "WD_s_F", "L_f", "L_r", "F0", "F1", "F2",
                "p00", "p10", "p01", "P_m_max", "T_m_max", "omega_m_r", "omega_m_max",
                "c_r", "R_w", "beta_gb", "beta_fd", "phi", "v_max", "eta_TF",

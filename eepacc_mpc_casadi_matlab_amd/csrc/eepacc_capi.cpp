@@ -14,6 +14,8 @@
 #include "eepacc_ab_build.h"
 #include "eepacc_qp_dense.h"
 #include "eepacc_fb.h"
+#include "eepacc_fb_qp.h"
+#include "eepacc_fb_rows.h"
 #include "eepacc_fbs.h"
 #include "eepacc_kpis.h"
 #include "eepacc_follow.h"
@@ -44,6 +46,7 @@ template <class T> struct DevMem {
 // dense FBMPC path (eepacc_fb.hip + the dense QP operator): buffers for B instances, allocated on first use
 struct FbDense {
     int B = 0, chunk = 0;
+    int steps_B = 0;                                       // B of the steps that wrote A22, D2, sp, vp: their stride (<= B)
     DevMem<double> H, g, A, lba, uba;                      // [chunk]
     DevMem<double> x, x0, cost, meas, carry, A22, D2;      // [B]
     DevMem<double> sp, vp;                                 // [N+1][B] predictions of the last step
@@ -680,6 +683,7 @@ static int fb_one_step(eepacc_handle* h, int B, int mode, const double* s, const
     HIPCHK(hipMemcpyAsync(h->fb.x0, h->fb.x, (size_t)B * nV * sizeof(double), hipMemcpyDeviceToDevice, stream));
     h->fb_k_done += 1;
     h->last_B = B;
+    h->fb.steps_B = B;
     return EEPACC_OK;
 }
 
@@ -709,6 +713,94 @@ extern "C" int eepacc_fb_step(eepacc_handle* h, int B, const double* s, const do
     if (rc != EEPACC_OK) return rc;
     h->fb_by_step = true;              // after fb_prepare: its first (re)allocation clears the flag
     return fb_one_step(h, B, 0, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, out, s_pred, v_pred, status, (hipStream_t)stream);
+}
+
+// The condensed QP of an FBMPC step as data (eepacc_fb_qp.hip).  Only a handle of eepacc_create with bl_mode = 0 has it.
+static int fb_qp_handle(const eepacc_handle* h, const char* who) {
+    if (!h) return fail(EEPACC_EINVAL, std::string(who) + ": NULL handle");
+    if (h->n_classes) return fail(EEPACC_ENOTSUP, std::string(who) + ": a handle of eepacc_create_classes runs ABMPC only and has no FBMPC problem");
+    if (h->cfg.bl_mode != 0) return fail(EEPACC_ENOTSUP, std::string(who) + ": the handle was created with bl_mode = " + std::to_string(h->cfg.bl_mode) + "; only the FBMPC problem (CreateQP_FB) is built");
+    return EEPACC_OK;
+}
+
+extern "C" int eepacc_fb_qp_size(const eepacc_handle* h, int* nV, int* nC) {
+    if (const int rc = fb_qp_handle(h, "eepacc_fb_qp_size")) return rc;
+    if (!nV) return fail(EEPACC_EINVAL, "eepacc_fb_qp_size: nV is NULL");
+    if (!nC) return fail(EEPACC_EINVAL, "eepacc_fb_qp_size: nC is NULL");
+    *nV = 6 * h->cfg.N;
+    *nC = h->cfg.fb_row0[h->cfg.N] + 2;
+    return EEPACC_OK;
+}
+
+extern "C" int eepacc_fb_qp_rows(const eepacc_handle* h, int32_t* stage, int32_t* type) {
+    if (const int rc = fb_qp_handle(h, "eepacc_fb_qp_rows")) return rc;
+    if (!stage) return fail(EEPACC_EINVAL, "eepacc_fb_qp_rows: stage is NULL");
+    if (!type) return fail(EEPACC_EINVAL, "eepacc_fb_qp_rows: type is NULL");
+    const DevCfg& C = h->cfg;
+    int r = 0;
+    for (int k = 0; k < C.N; ++k)
+        for (int t = 0; t < EEPACC_FB_ROW_N; ++t)
+            if (eepacc::fb_row_present(t, C.mb_mask[k])) { stage[r] = k; type[r] = t; ++r; }
+    stage[r] = C.N; type[r] = EEPACC_FB_ROW_SAFE1; ++r;
+    stage[r] = C.N; type[r] = EEPACC_FB_ROW_SAFE2; ++r;
+    return EEPACC_OK;
+}
+
+extern "C" int eepacc_fb_build_qp(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
+                                  const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                                  const double* A22, const double* D2, double* H, double* g, double* A, double* lba,
+                                  double* uba, double* A22_used, double* D2_used, void* stream) {
+    const char* who = "eepacc_fb_build_qp";
+    if (const int rc = fb_qp_handle(h, who)) return rc;
+    if (B < 0 || B > h->max_batch)
+        return fail(EEPACC_EINVAL, "eepacc_fb_build_qp: B = " + std::to_string(B) + " is outside [0, max_batch = " + std::to_string(h->max_batch) + "]");
+    if (B == 0) return EEPACC_OK;
+    const struct { const void* p; const char* name; } bufs[] = {
+        {s, "s"}, {v, "v"}, {a_prev, "a_prev"}, {t0, "t0"}, {s_tv, "s_tv"}, {v_tv, "v_tv"}, {a_tv_prev, "a_tv_prev"},
+        {H, "H"}, {g, "g"}, {A, "A"}, {lba, "lba"}, {uba, "uba"}};
+    for (const auto& bf : bufs)
+        if (!bf.p) return fail(EEPACC_EINVAL, std::string("eepacc_fb_build_qp: ") + bf.name + " is NULL");
+    if (!A22 != !D2)
+        return fail(EEPACC_EINVAL, std::string("eepacc_fb_build_qp: ") + (A22 ? "D2" : "A22") + " is NULL while " + (A22 ? "A22" : "D2") + " is given; pass both or neither");
+    const DevCfg& C = h->cfg;
+    if (A22 && !C.FBuseTaylor)
+        return fail(EEPACC_EINVAL, "eepacc_fb_build_qp: A22 and D2 are given, but with FBuseTaylor = 0 no model is carried (A22 = 1, D2 from the step's estimate); pass NULL");
+    const int N = C.N;
+    eepacc::fb_qp_args a;
+    a.cfg = h->d_cfg; a.B = B; a.nC = C.fb_row0[N] + 2;
+    a.s = s; a.v = v; a.a_prev = a_prev; a.t0 = t0; a.s_tv = s_tv; a.v_tv = v_tv; a.a_tv_prev = a_tv_prev;
+    a.H = H; a.g = g; a.A = A; a.lba = lba; a.uba = uba; a.A22_used = A22_used; a.D2_used = D2_used;
+    a.A22 = a.D2 = a.sp = a.vp = eepacc::FbCarried{nullptr, 0, 0};
+    // What the handle carries from its FBMPC steps: instance-major in fbs_state on a structured handle, [.][B of the steps]
+    // in h->fb on a dense-path handle.  Before the first step (and after a reset) nothing is carried: the model is
+    // initialised in the kernel and the predictions are zero.
+    const bool carried_model = !A22 && C.FBuseTaylor && h->fb_k_done > 0;
+    const bool carried_pred = C.paramEstSetting == 2 && h->fb_k_done > 0;
+    // The stride of the dense path's arrays is the B of the FBMPC steps that wrote them (fb.steps_B <= fb.B, what they are
+    // allocated for); h->last_B will not do, since the ABMPC entry points write it too.
+    if (!h->fbs && (carried_model || carried_pred) && (B != h->fb.steps_B || B > h->fb.B))
+        return fail(EEPACC_EINVAL, "eepacc_fb_build_qp: B = " + std::to_string(B) + " differs from the B = " + std::to_string(h->fb.steps_B) +
+                                   " of the FBMPC steps whose carried state this handle holds");
+    const size_t ks = eepacc::kFbsStateDoubles, lB = (size_t)h->fb.steps_B;
+    if (A22) {
+        a.k_step = -1;
+        a.A22 = eepacc::FbCarried{A22, (size_t)B, 1}; a.D2 = eepacc::FbCarried{D2, (size_t)B, 1};
+    } else {
+        a.k_step = h->fb_k_done;
+        if (carried_model && h->fbs) {
+            a.A22 = eepacc::FbCarried{h->fbs_state + 64, 1, ks}; a.D2 = eepacc::FbCarried{h->fbs_state + 128, 1, ks};
+        } else if (carried_model) {
+            a.A22 = eepacc::FbCarried{h->fb.A22, lB, 1}; a.D2 = eepacc::FbCarried{h->fb.D2, lB, 1};
+        }
+    }
+    if (carried_pred && h->fbs) {
+        a.sp = eepacc::FbCarried{h->fbs_state + 192, 1, ks}; a.vp = eepacc::FbCarried{h->fbs_state + 256, 1, ks};
+    } else if (carried_pred) {
+        a.sp = eepacc::FbCarried{h->fb.sp, lB, 1}; a.vp = eepacc::FbCarried{h->fb.vp, lB, 1};
+    }
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(eepacc::launch_fb_qp(a, N, (hipStream_t)stream));
+    return EEPACC_OK;
 }
 
 extern "C" int eepacc_run_fbmpc(eepacc_handle* h, int B, int n_steps, const double* s0, const double* v0,

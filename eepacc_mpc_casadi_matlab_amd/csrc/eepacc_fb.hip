@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "eepacc_fb.h"
+#include "eepacc_fb_rows.h"
 #include "eepacc_stage.h"
 #include "../../include/eepacc.h"
 
@@ -24,12 +25,6 @@ namespace {
 
 constexpr int FT = 256;
 constexpr int kRowsPerStage = 26;
-
-struct RowDesc {
-    double as, av, aFm, aFb, aFmp, aFbp, sc;   // coefficients; sc = slack coefficient
-    int slack;                                  // 0..3 = xi_v, xi_h, xi_s, xi_f ; -1 none
-    double lb, ub;
-};
 
 struct StageData {      // per-stage scalars in LDS
     double *s_est, *v_est, *stv_est, *v_lim, *v_curv, *v_stop, *v_TL, *a_min, *a_max, *j_min, *j_max;
@@ -44,75 +39,6 @@ __device__ void carve(StageData& S, double* p, int N) {
     S.A22 = p; p += n1; S.D2 = p; p += n1; S.ds = p; p += n1; S.dv = p; p += n1;
     S.Dblk = p; p += 9 * n1; S.Oblk = p; p += 9 * n1; S.cs = p; p += 3 * n1; S.tmp = p; p += 3 * n1;
     S.Sv = p; p += (size_t)n1 * N; S.Ss = p; p += (size_t)n1 * N; S.scal = p; p += 16;
-}
-
-// row t of stage k (k == N: terminal rows t = 0,1)
-__device__ RowDesc fb_row(const DevCfg& C, const StageData& S, int k, int t, double s_0, double v_0, double a_minus1) {
-    RowDesc R;
-    R.as = R.av = R.aFm = R.aFb = R.aFmp = R.aFbp = R.sc = 0.0;
-    R.slack = -1; R.lb = -INFINITY; R.ub = INFINITY;
-    const int N = C.N;
-    const double lm = C.lambda * C.m, za = C.zeta_a;
-    const double zeta_rg = C.m * C.g * (C.c_r * C.cos_theta0 + C.sin_theta0);
-    if (k == N) {                                           // CreateQP_FB.m:478-489
-        R.as = 1.0;
-        if (t == 0) R.ub = S.stv_est[N - 1] - C.h_min;
-        else { R.av = C.tau_min; R.ub = S.stv_est[N - 1]; }
-        return R;
-    }
-    const double ve = S.v_est[k], Tp = C.Tvec[k];
-    const double base = za * ve * ve + zeta_rg;
-    switch (t) {
-    case 0: R.as = 1.0; R.lb = s_0; R.ub = C.s_goal; break;                       // :311-342
-    case 1: R.av = 1.0; R.lb = 0.0; R.ub = C.v_max; break;
-    case 2: R.aFm = 1.0; R.lb = -1e4; R.ub = 1e4; break;
-    case 3: R.aFb = 1.0; R.lb = -1e4; R.ub = 0.0; break;
-    case 4: R.slack = 0; R.sc = 1.0; R.lb = 0.0; break;
-    case 5: R.slack = 1; R.sc = 1.0; R.lb = 0.0; break;
-    case 6: R.slack = 2; R.sc = 1.0; R.lb = 0.0; break;
-    case 7: R.slack = 3; R.sc = 1.0; R.lb = 0.0; break;
-    case 8: {                                                                       // :359-366
-        double cv = C.phi * C.T_m_max * C.T_m_max / 4.0 / C.P_m_max;
-        R.av = -cv; R.aFm = C.eta_TF / C.phi; R.slack = 3; R.sc = 1.0; R.lb = -C.T_m_max; break; }
-    case 9: {
-        double cv = C.phi * C.T_m_max * C.T_m_max / 4.0 / C.P_m_max;
-        R.av = cv; R.aFm = 1.0 / C.eta_TF / C.phi; R.slack = 3; R.sc = -1.0; R.ub = C.T_m_max; break; }
-    case 10: {                                                                      // :369-377
-        double zeta_w = C.m * C.g * (C.L_f * C.cos_theta0 + C.h_g * C.sin_theta0);
-        R.aFm = C.L / C.mu + C.h_g; R.aFb = C.h_g; R.slack = 3; R.sc = 1.0; R.lb = -zeta_w + C.h_g * zeta_rg; break; }
-    case 11: {
-        double zeta_w = C.m * C.g * (C.L_f * C.cos_theta0 + C.h_g * C.sin_theta0);
-        R.aFm = C.L / C.mu - C.h_g; R.aFb = -C.h_g; R.slack = 3; R.sc = -1.0; R.ub = zeta_w - C.h_g * zeta_rg; break; }
-    case 12: R.aFm = 1.0; R.aFb = 1.0; R.slack = 3; R.sc = -1.0; R.ub = C.mu * C.m * C.g * C.cos_theta0; break;   // :380-387
-    case 13: R.aFm = 1.0; R.aFb = 1.0; R.slack = 3; R.sc = 1.0; R.lb = -C.mu * C.m * C.g * C.cos_theta0; break;
-    case 14: R.aFm = 1.0; R.aFb = 1.0; R.slack = 3; R.sc = -1.0; R.ub = lm * S.a_max[k] + base; break;            // :390-397
-    case 15: R.aFm = 1.0; R.aFb = 1.0; R.slack = 3; R.sc = 1.0; R.lb = lm * S.a_min[k] + base; break;
-    case 16: case 17: {                                                             // :400-418
-        R.aFm = 1.0; R.aFb = 1.0; R.slack = 3;
-        double rhs_j = (t == 16) ? S.j_max[k] : S.j_min[k], rhs;
-        if (k == 0) rhs = lm * (Tp * rhs_j + a_minus1) + base;
-        else {
-            double vp = S.v_est[k - 1];
-            R.aFmp = -1.0; R.aFbp = -1.0;
-            rhs = lm * Tp * rhs_j + za * (ve * ve - vp * vp);      // + Dzeta_rg = 0: slope_est is constant
-        }
-        if (t == 16) { R.sc = -1.0; R.ub = rhs; } else { R.sc = 1.0; R.lb = rhs; }
-        break; }
-    case 18: R.av = 1.0; R.slack = 3; R.sc = -1.0; R.ub = S.v_lim[k]; break;        // :421-442
-    case 19: R.av = 1.0; R.slack = 3; R.sc = -1.0; R.ub = S.v_curv[k]; break;
-    case 20: R.av = 1.0; R.slack = 2; R.sc = -1.0; R.ub = S.v_stop[k]; break;
-    case 21: R.av = 1.0; R.slack = 2; R.sc = -1.0; R.ub = S.v_TL[k]; break;
-    case 22: R.av = 1.0; R.slack = 0; R.sc = 1.0; R.lb = fmin(S.v_lim[k], S.v_curv[k]); break;   // :445-448
-    case 23: R.as = 1.0; R.slack = 2; R.sc = -1.0; R.ub = S.stv_est[k] - C.h_min; break;        // :451-458
-    case 24: R.as = 1.0; R.av = C.tau_min; R.slack = 2; R.sc = -1.0; R.ub = S.stv_est[k]; break;
-    default: {                                                                      // :461-473
-        const double T_hwp = 2.0, A_hwp = 2.0, G_hwp = -0.0246 * T_hwp + 0.010819;
-        R.as = 1.0; R.slack = 1; R.sc = -1.0;
-        if (C.FBuseTaylor) { R.av = T_hwp + 2.0 * G_hwp * ve; R.ub = S.stv_est[k] - A_hwp + G_hwp * ve * ve; }
-        else { R.av = T_hwp + G_hwp * ve; R.ub = S.stv_est[k] - A_hwp; }
-        break; }
-    }
-    return R;
 }
 
 __global__ void __launch_bounds__(FT) k_fb_build(eepacc_fb_args a) {

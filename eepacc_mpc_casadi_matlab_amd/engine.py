@@ -14,6 +14,7 @@ from typing import Any, Dict, NamedTuple, Optional
 import numpy as np
 
 from ._abi import (SettingsHolder, SettingsPOD, Vehicle, make_vehicle, pack_classes, OUT, OUT_N, OUT_FIELDS, KPI_N, FKPI_N, FKPI_WEIGHTS, AB_BUILD_ARGTYPES,
+                   FB_BUILD_ARGTYPES,
                    c_double_p, as_dptr, as_iptr)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -71,7 +72,7 @@ def load_library() -> C.CDLL:
     lib.eepacc_qp_solve_batched.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [dp] * 8 + [dp, dp, dp, vp]
     lib.eepacc_qp_solve_batched_dual.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [dp] * 8 + [dp, dp] + [dp] * 3 + [dp] * 5 + [vp]
     lib.eepacc_qp_kkt_solve_batched.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int] + [dp] * 2 + [dp] * 2 + [dp] * 3 + [dp] * 3 + [dp, vp]
-    for name, argtypes in AB_BUILD_ARGTYPES.items():
+    for name, argtypes in list(AB_BUILD_ARGTYPES.items()) + list(FB_BUILD_ARGTYPES.items()):
         getattr(lib, name).argtypes = argtypes
     lib.eepacc_synchronize.argtypes = [vp, vp]
     lib.eepacc_build_flags.restype = C.c_char_p
@@ -87,6 +88,7 @@ ABI_SYMBOLS = ["eepacc_last_error", "eepacc_version", "eepacc_sizeof_settings", 
                "eepacc_follow_kpis",
                "eepacc_last_iterations", "eepacc_qp_solve_batched", "eepacc_qp_solve_batched_dual", "eepacc_qp_kkt_solve_batched",
                "eepacc_ab_qp_size", "eepacc_ab_qp_rows", "eepacc_ab_build_qp",
+               "eepacc_fb_qp_size", "eepacc_fb_qp_rows", "eepacc_fb_build_qp",
                "eepacc_synchronize", "eepacc_build_flags"]
 
 
@@ -119,6 +121,26 @@ class AbQp(NamedTuple):
     A: Any
     lba: Any
     uba: Any
+
+
+class FbQp(NamedTuple):
+    """What Engine.fb_build_qp returns: the fields of AbQp for the condensed QP of one FBMPC step."""
+    H: Any
+    g: Any
+    A: Any
+    lba: Any
+    uba: Any
+
+
+class FbQpModel(NamedTuple):
+    """Engine.fb_build_qp(want_model=True): FbQp and the model that went into the problem (A22_used, D2_used [N,B])."""
+    H: Any
+    g: Any
+    A: Any
+    lba: Any
+    uba: Any
+    A22_used: Any
+    D2_used: Any
 
 
 class Engine:
@@ -291,6 +313,41 @@ class Engine:
     def run_fbmpc(self, s0, v0, a_minus1, s_tv, v_tv, resume: bool = False, out=None):
         """Closed-loop FBMPC; arguments and results as run_abmpc."""
         return self._run(self.lib.eepacc_run_fbmpc, (s0, v0, a_minus1), (s_tv, v_tv), None, resume, out)
+
+    def fb_qp_size(self):
+        """eepacc_fb_qp_size: (nV, nC) of the condensed QP of an FBMPC step of this engine."""
+        nV, nC = C.c_int(), C.c_int()
+        _check(self.lib.eepacc_fb_qp_size(self.h, C.byref(nV), C.byref(nC)))
+        return nV.value, nC.value
+
+    def fb_qp_rows(self):
+        """eepacc_fb_qp_rows: (stage, type), two int32 arrays [nC]: the horizon stage of every row of the built problem (N for
+        the two terminal rows) and its type as an index into _abi.FB_ROW_TYPES."""
+        _, nC = self.fb_qp_size()
+        stage = np.empty(nC, dtype=np.int32); typ = np.empty(nC, dtype=np.int32)
+        _check(self.lib.eepacc_fb_qp_rows(self.h, as_iptr(stage), as_iptr(typ)))
+        return stage, typ
+
+    def fb_build_qp(self, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, A22=None, D2=None, want_model: bool = False):
+        """eepacc_fb_build_qp: the condensed QP the reference poses at this FBMPC step (ABO/RunOpt_FBMPC.m:215-264), for the
+        inputs of fb_step that CreateQP_FB reads.  A22, D2 ([N,B]) are the model A(k,2,2), D(k,2) of the step; with None the
+        build uses what the engine's next fb_step / run_fbmpc step would use (carried entries and step counter) and writes
+        none of it back.  Returns FbQp(H [B,nV,nV], g [B,nV], A [B,nC,nV], lba [B,nC], uba [B,nC]) as ab_build_qp does; with
+        want_model FbQpModel, which adds A22_used, D2_used ([N,B]): fed back as A22, D2 they reproduce the build."""
+        t = self.torch
+        B = int(t.as_tensor(s).numel())
+        ins = [self._d(x, B) for x in (s, v, a_prev, t0, s_tv, v_tv, a_tv_prev)]
+        model = [None if x is None else self._d(x, self.N * B) for x in (A22, D2)]
+        nV, nC = self.fb_qp_size()
+        f64 = dict(dtype=t.float64, device=self.device)
+        H = t.empty((B, nV, nV), **f64); g = t.empty((B, nV), **f64); A_cm = t.empty((B, nV, nC), **f64)
+        lba = t.empty((B, nC), **f64); uba = t.empty((B, nC), **f64)
+        used = [t.empty((self.N, B), **f64) if want_model else None for _ in range(2)]
+        _check(self.lib.eepacc_fb_build_qp(self.h, B, *[x.data_ptr() for x in ins], _ptr(model[0]), _ptr(model[1]),
+                                           H.data_ptr(), g.data_ptr(), A_cm.data_ptr(), lba.data_ptr(), uba.data_ptr(),
+                                           _ptr(used[0]), _ptr(used[1]), self._stream()))
+        q = FbQp(H, g, A_cm.transpose(1, 2), lba, uba)
+        return FbQpModel(*q, used[0], used[1]) if want_model else q
 
     def postprocess(self, traj):
         t = self.torch

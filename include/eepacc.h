@@ -277,9 +277,10 @@ enum {
  * entry, zeros included (no memset, no atomics): the arrays do not depend on B or on timing.  EEPACC_EINVAL, with a message
  * that names the argument: a NULL buffer, B < 0 or B > max_batch.  EEPACC_ENOTSUP: a handle of eepacc_create_classes (nC can
  * differ per class) and a handle created with bl_mode 1 or 2.  B = 0 returns EEPACC_OK.
- * Not built: the FBMPC problem (its build kernel updates the carried A22 / D2 state; exposing it needs a variant that does
- * not), BLMPC and TVMPC handles, class handles, the formulations of solverToUse 0 (dynamics kept as rows) and 2 (HPIPM).
- * Throughput: not measured (tools/gpu_ab_build_bench.py times the build against a plain device fill of the same bytes). */
+ * The FBMPC problem: eepacc_fb_build_qp below.  Not built: BLMPC and TVMPC handles, class handles, the formulations of
+ * solverToUse 0 (dynamics kept as rows) and 2 (HPIPM).
+ * Throughput (tools/gpu_ab_build_bench.py, the build against a plain device fill of the same bytes, profiles/ab_build_bench.json):
+ * 1.53 of the fill's time at N_hor = 20 x 4096 instances, 1.80 at N_hor = 60 x 1024; DESIGN.md section 3.6a. */
 int  eepacc_ab_qp_size(const eepacc_handle* h, int* nV, int* nC);
 int  eepacc_ab_qp_rows(const eepacc_handle* h, int32_t* stage, int32_t* type);
 int  eepacc_ab_build_qp(eepacc_handle* h, int B,
@@ -379,6 +380,86 @@ int  eepacc_run_fbmpc(eepacc_handle* h, int B, int n_steps,
                       const double* s0, const double* v0, const double* a_minus1,
                       const double* s_tv, const double* v_tv,
                       double* traj, int32_t* status, void* stream);
+
+/* The condensed QP of one FBMPC step as data, the counterpart of eepacc_ab_build_qp: what a user of the reference holds as H,
+ * c, G, g_lb, g_ub after ABO/RunOpt_FBMPC.m:215-264 and finds saved as optSol.H, optSol.G.  The structured FBMPC kernels never
+ * form it (they optimise u = Fm + Fb); eepacc_fb_build_qp does, for the inputs of eepacc_fb_step that CreateQP_FB reads
+ * (device, each [B]): the estimators and bounds (EstimateVehicleTrajectory.m:55-88, EstimateRouteAndComfortBounds.m:63-171),
+ * the objective and rows of ABO/Functions/MPCs/CreateQP_FB.m:158-489, condensed as TransformToDenseFormulation.m:30-91 with
+ * the model of RunOpt_FBMPC.m:78-90, 247-259.  Outputs, device, instance-major, in the layout eepacc_qp_solve_batched reads:
+ * H [B][nV*nV], g [B][nV], A [B][nV][nC] (column-major nC x nV), lba, uba [B][nC], an absent side -inf / +inf.  There are no
+ * lbx / ubx: hand the operator NULL.  H is indefinite.
+ * nV = 6 N_hor, variables per stage Fm, Fb, xi_v, xi_h, xi_s, xi_f.  nC = 26 N_hor + 2 plus two rows per blocked stage
+ * (Mb[k] = 1, CreateQP_FB.m:346-356), rows in the reference's order (:311-489); eepacc_fb_qp_size returns both.  Covered:
+ * both trees, Mb, b_quadr(4) != 0, FBuseTaylor 0 and 1, variable Tvec, every N_hor the handle accepts (the size limit of the
+ * dense operator does not apply to the build), the estimator modes 0, 1 and 2 (mode 2 reads the predictions the handle
+ * carries from the last FBMPC step).  The slope is the constant one the reference's CreateQP_FB sees (slope(1)).
+ *
+ * The model A(k), D(k).  With A22 == D2 == NULL the build uses the model the handle's next eepacc_fb_step / eepacc_run_fbmpc
+ * step would use: the entries the handle carries and its step counter, with the initialisation at step 0 (:78-90) and the
+ * replacement of entry k == step from v_est[N_hor-1] (:247-259); on a handle whose FBMPC steps run through the dense path
+ * (Mb, b_quadr(4) != 0, EEPACC_FB_DENSE) B must then be the B of those steps (EEPACC_EINVAL otherwise; ABMPC calls on the
+ * handle in between do not matter).  None of it is written back.  The build does not contract products into fused
+ * multiply-adds and the step kernels do, so the entry it replaces at k == step can differ from the one the step will compute
+ * in the last bit.  With both arrays
+ * given ([N_hor][B] each, device) they are the A(k,2,2), D(k,2) the loop holds when it condenses this step; they are used as
+ * they are and no step counter is read.  With FBuseTaylor = 0 nothing is carried (A22 = 1, D2 from this step's estimate) and
+ * given arrays are EEPACC_EINVAL.  A22_used, D2_used ([N_hor][B] each, device, may be NULL) receive what went into the
+ * problem, so that a caller can chain steps without the handle's state.
+ *
+ * eepacc_fb_qp_rows fills two host arrays [nC]: stage[i] in 0 .. N_hor-1, or N_hor for the two terminal rows, and type[i], one
+ * of EEPACC_FB_ROW_*, whose values ascend in the order of the rows within a stage: */
+enum {
+    EEPACC_FB_ROW_S = 0,       /* CreateQP_FB.m:311-342  s_0 <= s_k <= s_goal                                              */
+    EEPACC_FB_ROW_V,           /*   0 <= v_k <= v_max                                                                      */
+    EEPACC_FB_ROW_FM,          /*   -1e4 <= Fm_k <= 1e4                                                                    */
+    EEPACC_FB_ROW_FB,          /*   -1e4 <= Fb_k <= 0                                                                      */
+    EEPACC_FB_ROW_XI_V,        /*   xi_v >= 0                                                                              */
+    EEPACC_FB_ROW_XI_H,        /*   xi_h >= 0                                                                              */
+    EEPACC_FB_ROW_XI_S,        /*   xi_s >= 0                                                                              */
+    EEPACC_FB_ROW_XI_F,        /*   xi_f >= 0                                                                              */
+    EEPACC_FB_ROW_BLOCKED_FM,  /* :346-356  Fm_{k-1} - Fm_k = 0, only on a stage with Mb[k] = 1                            */
+    EEPACC_FB_ROW_BLOCKED_FB,  /*   Fb_{k-1} - Fb_k = 0, only on a stage with Mb[k] = 1                                    */
+    EEPACC_FB_ROW_TM_MIN,      /* :359-366  motor torque  -c v_k + eta_TF/phi Fm_k + xi_f >= -T_m_max                      */
+    EEPACC_FB_ROW_TM_MAX,      /*   c v_k + Fm_k/(eta_TF phi) - xi_f <= T_m_max                                            */
+    EEPACC_FB_ROW_AXLE_MIN,    /* :369-377  rear-axle traction  (L/mu + h_g) Fm_k + h_g Fb_k + xi_f >= -zeta_w + h_g zeta_rg */
+    EEPACC_FB_ROW_AXLE_MAX,    /*   (L/mu - h_g) Fm_k - h_g Fb_k - xi_f <= zeta_w - h_g zeta_rg                            */
+    EEPACC_FB_ROW_FRIC_MAX,    /* :380-387  total friction  Fm_k + Fb_k - xi_f <= mu m g cos(theta)                        */
+    EEPACC_FB_ROW_FRIC_MIN,    /*   Fm_k + Fb_k + xi_f >= -mu m g cos(theta)                                               */
+    EEPACC_FB_ROW_A_MAX,       /* :390-397  Fm_k + Fb_k - xi_f <= lambda m a_max + zeta_a v_est^2 + zeta_rg                */
+    EEPACC_FB_ROW_A_MIN,       /*   Fm_k + Fb_k + xi_f >= lambda m a_min + zeta_a v_est^2 + zeta_rg                        */
+    EEPACC_FB_ROW_J_MAX,       /* :400-418  (Fm + Fb)_k - (Fm + Fb)_{k-1} - xi_f <= lambda m T_k j_max + ... (stage 0: a_minus1) */
+    EEPACC_FB_ROW_J_MIN,       /*   (Fm + Fb)_k - (Fm + Fb)_{k-1} + xi_f >= lambda m T_k j_min + ...                       */
+    EEPACC_FB_ROW_V_LIM,       /* :421-442  v_k - xi_f <= speed limit                                                      */
+    EEPACC_FB_ROW_V_CURV,      /*   v_k - xi_f <= curve speed                                                              */
+    EEPACC_FB_ROW_V_STOP,      /*   v_k - xi_s <= stop speed                                                               */
+    EEPACC_FB_ROW_V_TL,        /*   v_k - xi_s <= traffic-light speed                                                      */
+    EEPACC_FB_ROW_V_INC,       /* :445-448  speed incentive  v_k + xi_v >= min(speed limit, curve speed)                   */
+    EEPACC_FB_ROW_SAFE1,       /* :451-458  safe distance 1  s_k - xi_s <= s_tv - h_min (terminal row :478-489: no slack)  */
+    EEPACC_FB_ROW_SAFE2,       /*   safe distance 2  s_k + tau_min v_k - xi_s <= s_tv (terminal row: no slack)             */
+    EEPACC_FB_ROW_HWP,         /* :461-473  headway policy, linearised about v_est with FBuseTaylor = 1                    */
+    EEPACC_FB_ROW_N
+};
+/* The built problem is the reference's own: a measured state outside its hard bounds shows up as a stage-0 row without
+ * coefficients whose bounds exclude 0.  The constant term of the objective is excluded: 1/2 x'Hx + g'x at the solution equals
+ * EEPACC_OUT_COST of the same step, x[0], x[1] are EEPACC_OUT_FM, EEPACC_OUT_FB and x[2..5] are EEPACC_OUT_XI_V, _XI_H,
+ * _XI_S, _XI_F (what the extraction of the dense path reads, RunOpt_FBMPC.m:291-299).
+ *
+ * The build is asynchronous on stream.  Of the handle's state it reads the carried model entries, predictions and step
+ * counter named above and nothing else (no warm start, no closed-loop carry), and it writes none: a build between two FBMPC
+ * calls leaves their results bit for bit unchanged.  One workgroup per instance writes every entry, zeros included (no
+ * memset, no atomics): the arrays do not depend on B or on timing.  EEPACC_EINVAL, with a message that names the argument: a
+ * NULL buffer, only one of A22 / D2, B < 0 or B > max_batch.  EEPACC_ENOTSUP: a handle of eepacc_create_classes and a handle
+ * created with bl_mode 1 or 2.  B = 0 returns EEPACC_OK.
+ * Throughput: see DESIGN.md section 3.6b (tools/gpu_fb_qp_bench.py times the build against a plain device fill). */
+int  eepacc_fb_qp_size(const eepacc_handle* h, int* nV, int* nC);
+int  eepacc_fb_qp_rows(const eepacc_handle* h, int32_t* stage, int32_t* type);
+int  eepacc_fb_build_qp(eepacc_handle* h, int B,
+                        const double* s, const double* v, const double* a_prev, const double* t0,
+                        const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                        const double* A22, const double* D2,
+                        double* H, double* g, double* A, double* lba, double* uba,
+                        double* A22_used, double* D2_used, void* stream);
 
 /* Host-pointer convenience wrappers (what a MEX gateway calls). */
 int  eepacc_run_abmpc_host(eepacc_handle* h, int B, int n_steps,
