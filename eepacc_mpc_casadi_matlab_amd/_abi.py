@@ -56,6 +56,18 @@ FB_BUILD_ARGTYPES = {
     "eepacc_fb_build_qp": [C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p] * 2 + [C.c_void_p] * 5 + [C.c_void_p] * 2 + [C.c_void_p],
 }
 
+# enum EEPACC_BL_ROW_*: the row types of eepacc_bl_qp_rows, ascending in the order of the rows within a stage (a handle created
+# with bl_mode = 2 has none of the two safe-distance types)
+BL_ROW_TYPES = ["s", "v", "xi_f", "a_min", "a_max", "j_min", "j_max", "v_lim", "v_curv", "v_stop", "v_tl", "safe1", "safe2"]
+BL_ROW = {name: i for i, name in enumerate(BL_ROW_TYPES)}
+
+# the same for a BLMPC / TVMPC step: the seven inputs (the three lead arrays may be None with bl_mode = 2), the five outputs
+BL_BUILD_ARGTYPES = {
+    "eepacc_bl_qp_size": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "eepacc_bl_qp_rows": [C.c_void_p, c_int32_p, c_int32_p],
+    "eepacc_bl_build_qp": [C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p] * 5 + [C.c_void_p],
+}
+
 _VEH_FIELDS = ["m", "A_f", "c_d", "L", "h_g", "WD_s_F", "L_f", "L_r", "F0", "F1", "F2",
                "p00", "p10", "p01", "P_m_max", "T_m_max", "omega_m_r", "omega_m_max",
                "c_r", "R_w", "beta_gb", "beta_fd", "phi", "v_max", "eta_TF",

@@ -1,0 +1,231 @@
+// eepacc_bl_qp.hip -- the condensed QP of one BLMPC step (bl_mode = 1) or TVMPC step (bl_mode = 2), written out as data:
+// H, g, A, lba, uba in the layout the dense QP operator reads.  The closed-loop kernels never form this problem; this
+// kernel is the boundary for callers who want it: to compare objective values on the faces of the LP, to read which
+// speed-limit, stop or headway row is tight, to hand the problem to another solver.  Geometry of k_ab_build
+// (eepacc_ab_build.hip): one workgroup of 256 threads per instance, stage quantities into LDS once.
+//
+// Reference, bl_mode = 1: ABO/RunOpt_BLMPC.m:182-230 with solverToUse = 1: estimators (EstimateVehicleTrajectory.m:55-88),
+// bounds (EstimateRouteAndComfortBounds.m:63-143,173-189), objective and rows of ABO/Functions/MPCs/CreateQP_BL.m:99-314
+// and the condensing of TransformToDenseFormulation.m:30-91.  bl_mode = 2: ABO/RunOpt_TVMPC.m:161-208 with CreateQP_TV.m:
+// the same rows without the headway rows (:288-292: no terminal rows either), 0.8 of the speed-limit and curve caps
+// (:265,271) and the comfort limits of a zero speed estimate (:44-45).
+//
+// With A_k = [1 T_k; 0 1], B_k = [T_k^2/2; T_k] on the acceleration only,
+//   v_k = v_0 + sum_{i<k} T_i a_i,   s_k = d_s[k] + sum_{i<k} Ss[k][i] a_i,   Ss[k][i] = T_i^2/2 + T_i (T_{k-1} + .. + T_{i+1}).
+// The sparse-form objective has no curvature on s_k, v_k: H is the tridiagonal of the w_a and w_j terms on the
+// accelerations (both zero with the reference's weights: a linear program), and g carries the travel incentive -w_v on
+// v_0 .. v_N through the speed sensitivities.  CreateQP_BL.m:31 takes Ts = Tvec(1) for the jerk terms at every stage; the
+// dynamics take Tvec(k).  Sums run in the order of the reference's loops and products are not contracted into fused
+// multiply-adds, so that an entry of A, lba, uba and g has the reference's roundings.
+//
+// Dense variable order per stage (2): a, xi_f.  Rows: eepacc_bl_qp.h.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "eepacc_bl_qp.h"
+
+// also for the estimators of eepacc_stage.h as this file compiles them
+#pragma clang fp contract(off)
+#include "eepacc_stage.h"
+
+namespace eepacc {
+namespace {
+
+constexpr int BT = 256;              // threads of a workgroup: four waves
+constexpr int kS = kMaxN + 1;        // stage arrays: index N is the terminal stage
+
+struct Stages {                      // per-stage quantities of the step, static LDS
+    double T[kS], stv[kS], ds[kS];
+    double v_lim[kS], v_curv[kS], v_stop[kS], v_TL[kS], a_min[kS], a_max[kS], j_min[kS], j_max[kS];
+};
+
+struct Row {                         // one row: as s_k + av v_k + ga a_k + de a_{k-1} + sc xi_f in [lb, ub]
+    int k;
+    double as, av, ga, de, sc, lb, ub;
+};
+
+// Row `type` (EEPACC_BL_ROW_*) of stage k; k == N: the two terminal rows (CreateQP_BL.m:306-314)
+__device__ inline Row bl_row(const DevCfg& C, const Stages& S, int k, int type, double a_minus1) {
+    Row R;
+    R.k = k;
+    R.as = R.av = R.ga = R.de = R.sc = 0.0;
+    R.lb = -INFINITY; R.ub = INFINITY;
+    const int N = C.N;
+    if (k == N) {
+        R.as = 1.0;
+        if (type == EEPACC_BL_ROW_SAFE1) R.ub = S.stv[N - 1] - C.h_min;
+        else { R.av = C.tau_min; R.ub = S.stv[N - 1]; }
+        return R;
+    }
+    const double Ts = C.Tvec[0];                                                                    // :31
+    switch (type) {
+    case EEPACC_BL_ROW_S: R.as = 1.0; R.lb = 0.0; R.ub = C.s_goal; break;                           // :217-228
+    case EEPACC_BL_ROW_V: R.av = 1.0; R.lb = 0.0; R.ub = C.v_max; break;
+    case EEPACC_BL_ROW_XI_F: R.sc = 1.0; R.lb = 0.0; break;
+    case EEPACC_BL_ROW_A_MIN: R.ga = 1.0; R.sc = 1.0; R.lb = S.a_min[k]; break;                     // :232-239
+    case EEPACC_BL_ROW_A_MAX: R.ga = 1.0; R.sc = -1.0; R.ub = S.a_max[k]; break;
+    case EEPACC_BL_ROW_J_MIN:                                                                       // :242-261
+        R.ga = 1.0; R.sc = 1.0;
+        if (k > 0) { R.de = -1.0; R.lb = Ts * S.j_min[k]; } else R.lb = Ts * S.j_min[k] + a_minus1;
+        break;
+    case EEPACC_BL_ROW_J_MAX:
+        R.ga = 1.0; R.sc = -1.0;
+        if (k > 0) { R.de = -1.0; R.ub = Ts * S.j_max[k]; } else R.ub = Ts * S.j_max[k] + a_minus1;
+        break;
+    case EEPACC_BL_ROW_V_LIM: R.av = 1.0; R.sc = -1.0; R.ub = S.v_lim[k]; break;                    // :265-286
+    case EEPACC_BL_ROW_V_CURV: R.av = 1.0; R.sc = -1.0; R.ub = S.v_curv[k]; break;
+    case EEPACC_BL_ROW_V_STOP: R.av = 1.0; R.sc = -1.0; R.ub = S.v_stop[k]; break;
+    case EEPACC_BL_ROW_V_TL: R.av = 1.0; R.sc = -1.0; R.ub = S.v_TL[k]; break;
+    case EEPACC_BL_ROW_SAFE1: R.as = 1.0; R.sc = -1.0; R.ub = S.stv[k] - C.h_min; break;            // :289-296
+    default: R.as = 1.0; R.av = C.tau_min; R.sc = -1.0; R.ub = S.stv[k]; break;
+    }
+    return R;
+}
+
+__global__ void __launch_bounds__(BT) k_bl_qp(const DevCfg* __restrict__ cfg, int nC, const double* __restrict__ s,
+                                              const double* __restrict__ v, const double* __restrict__ a_prev,
+                                              const double* __restrict__ t0, const double* __restrict__ s_tv,
+                                              const double* __restrict__ v_tv, const double* __restrict__ a_tv_prev,
+                                              double* __restrict__ H, double* __restrict__ g, double* __restrict__ A,
+                                              double* __restrict__ lba, double* __restrict__ uba) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    __shared__ Stages S;
+    const DevCfg& C = *cfg;
+    const int N = C.N, nV = 2 * N, tid = threadIdx.x;
+    const bool tv = C.bl_mode == 2;
+    const size_t b = blockIdx.x;
+    const int ld = N | 1;                                   // odd row stride: a column of Ss is read without bank conflicts
+    double* Ss = reinterpret_cast<double*>(smem);           // [N+1][ld]
+    unsigned short* rows = reinterpret_cast<unsigned short*>(Ss + (size_t)(N + 1) * ld);   // [nC]: stage | type << 8
+    const double s_0 = s[b], v_0 = v[b], a_minus1 = a_prev[b], t_0 = t0[b];
+    const double Ts = C.Tvec[0];                                                // CreateQP_BL.m:31, CreateQP_TV.m:29
+    const double q = 2.0 * C.w_j / (Ts * Ts);                                   // jerk curvature, CreateQP_BL.m:138-145
+
+    // ---- estimators and bounds per stage (EstimateVehicleTrajectory.m, EstimateRouteAndComfortBounds.m)
+    if (tid <= N) {
+        const int k = tid;
+        double se, ve, st = 0.0, vt;
+        if (C.paramEstSetting == 2) {
+            // EstimateVehicleTrajectory.m:81-88: [x_curr; prev(3:end); prev(end) + Ts v_prev(end)]; the handle carries
+            // the previous step's predictions, which are read and not written here
+            const double* predp = C.pred + b * 128;
+            const int idx = k < N ? k + 1 : N;
+            const double ps = predp[idx], pv = predp[64 + idx];
+            se = k == 0 ? s_0 : (k < N ? ps : ps + C.Tvec[N - 1] * pv);
+            ve = k == 0 ? v_0 : pv;
+        } else {
+            estimate_traj(C, C.paramEstSetting, C.tConstACC_ego, s_0, v_0, a_minus1, k, se, ve);
+        }
+        // (target-vehicle MPC: no lead vehicle, RunOpt_TVMPC.m:157 estimates its own trajectory only)
+        if (!tv) estimate_traj(C, C.TVestSetting, C.tConstACC_tar, s_tv[b], v_tv[b], a_tv_prev[b], k, st, vt);
+        S.stv[k] = st;
+        double T = 0.0;
+        if (k < N) {
+            T = C.Tvec[k];
+            // CreateQP_TV.m:44-45 hands the bounds a zero speed estimate: the low-speed comfort limits at every stage
+            route_bounds(C, se, tv ? 0.0 : ve, t_0, k, S.v_lim[k], S.v_curv[k], S.v_stop[k], S.v_TL[k], S.a_min[k], S.a_max[k],
+                         S.j_min[k], S.j_max[k]);
+            if (tv) { S.v_lim[k] *= 0.8; S.v_curv[k] *= 0.8; }                  // CreateQP_TV.m:265,271
+        }
+        S.T[k] = T;
+    }
+    __syncthreads();
+
+    // ---- position sensitivities and free response; the row catalogue
+    if (tid <= N) {
+        const int k = tid;
+        double R = 0.0;                                     // T_{k-1} + .. + T_{i+1}, summed downwards as the reference does
+        for (int i = k - 1; i >= 0; --i) {
+            const double Ti = S.T[i];
+            Ss[(size_t)k * ld + i] = 0.5 * Ti * Ti + R * Ti;
+            R += Ti;
+        }
+        S.ds[k] = k == 0 ? s_0 : s_0 + R * v_0;
+        if (k < N) {
+            int r = bl_rows_per_stage(C.bl_mode) * k;       // first row of the stage
+            for (int type = 0; type < EEPACC_BL_ROW_N; ++type)
+                if (bl_row_present(type, C.bl_mode)) rows[r++] = (unsigned short)(k | (type << 8));
+        } else if (!tv) {
+            rows[nC - 2] = (unsigned short)(N | (EEPACC_BL_ROW_SAFE1 << 8));
+            rows[nC - 1] = (unsigned short)(N | (EEPACC_BL_ROW_SAFE2 << 8));
+        }
+    }
+    __syncthreads();
+
+    // ---- H, row-major: consecutive lanes write consecutive entries; (ra, rb) advance without a division
+    {
+        double* Hd = H + b * (size_t)nV * nV;
+        const int total = nV * nV, dra = BT / nV, drb = BT % nV;
+        int ra = tid / nV, rb = tid % nV;
+        for (int idx = tid; idx < total; idx += BT) {
+            double h = 0.0;
+            if (((ra | rb) & 1) == 0) {                                         // a_i, a_j: CreateQP_BL.m:134-145
+                const int i = ra >> 1, j = rb >> 1;
+                if (i == j) { h = 2.0 * C.w_a + q; if (i + 1 < N) h += q; }
+                else if (i == j + 1 || j == i + 1) h = 0.0 - q;
+            }
+            Hd[idx] = h;
+            rb += drb; ra += dra;
+            if (rb >= nV) { rb -= nV; ++ra; }
+        }
+    }
+    // ---- g: Psi' cs, the sum over ascending stages: -w_v on v_{i+1} .. v_N (:131,304), the jerk term of stage 0 (:141), w_f (:148)
+    for (int col = tid; col < nV; col += BT) {
+        const int i = col >> 1;
+        double gv;
+        if ((col & 1) == 0) {
+            gv = i == 0 ? 0.0 - 2.0 * C.w_j / Ts * a_minus1 : 0.0;
+            const double Ti = S.T[i];
+            for (int k = i + 1; k <= N; ++k) gv += Ti * C.glin_v;
+        } else {
+            gv = C.w_f;
+        }
+        g[b * (size_t)nV + col] = gv;
+    }
+    // ---- lba, uba: the row's bounds less its value at the free response
+    for (int r = tid; r < nC; r += BT) {
+        const int e = rows[r];
+        const Row R = bl_row(C, S, e & 0xff, e >> 8, a_minus1);
+        const double shift = R.as * S.ds[R.k] + R.av * v_0;
+        lba[b * (size_t)nC + r] = R.lb - shift;
+        uba[b * (size_t)nC + r] = R.ub - shift;
+    }
+    // ---- A, column-major nC x nV: a wave takes 64 consecutive rows (consecutive addresses of one column) and walks the
+    // columns of its quarter of the stages, so the four waves share every block of rows evenly
+    {
+        double* Ad = A + b * (size_t)nV * nC;
+        const int wave = tid >> 6, lane = tid & 63;
+        const int i0 = wave * N / 4, i1 = (wave + 1) * N / 4;
+        for (int r0 = 0; r0 < nC; r0 += 64) {
+            const int r = r0 + lane;
+            if (r >= nC) continue;
+            const int e = rows[r];
+            const Row R = bl_row(C, S, e & 0xff, e >> 8, a_minus1);
+            const int k = R.k;
+            double* col = Ad + (size_t)(2 * i0) * nC + r;
+            for (int i = i0; i < i1; ++i) {
+                double va = 0.0;
+                if (i < k) { va = R.as * Ss[(size_t)k * ld + i]; va += R.av * S.T[i]; }
+                if (i == k) va = R.ga;
+                if (i == k - 1) va += R.de;
+                col[0] = va;
+                col[nC] = i == k ? R.sc : 0.0;
+                col += (size_t)2 * nC;
+            }
+        }
+    }
+}
+
+}  // namespace
+
+hipError_t launch_bl_qp(const DevCfg* cfg, int N, int nC, int B, const double* s, const double* v, const double* a_prev,
+                        const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                        double* H, double* g, double* A, double* lba, double* uba, hipStream_t stream) {
+    const size_t smem = (size_t)(N + 1) * (N | 1) * sizeof(double) + (size_t)nC * sizeof(unsigned short);
+    hipLaunchKernelGGL(k_bl_qp, dim3(B), dim3(BT), smem, stream, cfg, nC, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev,
+                       H, g, A, lba, uba);
+    return hipGetLastError();
+}
+
+}  // namespace eepacc

@@ -12,6 +12,7 @@
 #include "eepacc_cfg.h"
 #include "eepacc_ab.h"
 #include "eepacc_ab_build.h"
+#include "eepacc_bl_qp.h"
 #include "eepacc_qp_dense.h"
 #include "eepacc_fb.h"
 #include "eepacc_fb_qp.h"
@@ -373,7 +374,7 @@ extern "C" int eepacc_run_tvmpc(eepacc_handle* h, int B, int n_steps, const doub
 static int ab_qp_handle(const eepacc_handle* h, const char* who) {
     if (!h) return fail(EEPACC_EINVAL, std::string(who) + ": NULL handle");
     if (h->n_classes) return fail(EEPACC_ENOTSUP, std::string(who) + ": a handle of eepacc_create_classes has no single problem size (nC can differ per class)");
-    if (h->cfg.bl_mode != 0) return fail(EEPACC_ENOTSUP, std::string(who) + ": the handle was created with bl_mode = " + std::to_string(h->cfg.bl_mode) + "; only the ABMPC problem (CreateQP_AB) is built");
+    if (h->cfg.bl_mode != 0) return fail(EEPACC_ENOTSUP, std::string(who) + ": the handle was created with bl_mode = " + std::to_string(h->cfg.bl_mode) + "; only the ABMPC problem (CreateQP_AB) is built here, eepacc_bl_build_qp builds the problem of such a handle");
     return EEPACC_OK;
 }
 
@@ -415,6 +416,58 @@ extern "C" int eepacc_ab_build_qp(eepacc_handle* h, int B, const double* s, cons
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(eepacc::launch_ab_build(h->d_cfg, h->cfg.N, eepacc::ab_qp_num_rows(h->cfg), B, s, v, a_prev, t0, s_tv, v_tv,
                                    a_tv_prev, H, g, A, lba, uba, (hipStream_t)stream));
+    return EEPACC_OK;
+}
+
+// The condensed QP of a BLMPC or TVMPC step as data (eepacc_bl_qp.hip).  Only a handle of eepacc_create with bl_mode = 1 or 2 has it.
+static int bl_qp_handle(const eepacc_handle* h, const char* who) {
+    if (!h) return fail(EEPACC_EINVAL, std::string(who) + ": NULL handle");
+    if (h->n_classes) return fail(EEPACC_ENOTSUP, std::string(who) + ": a handle of eepacc_create_classes has no baseline or target-vehicle problem (its classes are ABMPC settings)");
+    if (h->cfg.bl_mode == 0) return fail(EEPACC_ENOTSUP, std::string(who) + ": the handle was created with bl_mode = 0; eepacc_ab_build_qp / eepacc_fb_build_qp build its problems, only the BLMPC and TVMPC problems (CreateQP_BL, CreateQP_TV) are built here");
+    return EEPACC_OK;
+}
+
+extern "C" int eepacc_bl_qp_size(const eepacc_handle* h, int* nV, int* nC) {
+    if (const int rc = bl_qp_handle(h, "eepacc_bl_qp_size")) return rc;
+    if (!nV) return fail(EEPACC_EINVAL, "eepacc_bl_qp_size: nV is NULL");
+    if (!nC) return fail(EEPACC_EINVAL, "eepacc_bl_qp_size: nC is NULL");
+    *nV = 2 * h->cfg.N;
+    *nC = eepacc::bl_qp_num_rows(h->cfg);
+    return EEPACC_OK;
+}
+
+extern "C" int eepacc_bl_qp_rows(const eepacc_handle* h, int32_t* stage, int32_t* type) {
+    if (const int rc = bl_qp_handle(h, "eepacc_bl_qp_rows")) return rc;
+    if (!stage) return fail(EEPACC_EINVAL, "eepacc_bl_qp_rows: stage is NULL");
+    if (!type) return fail(EEPACC_EINVAL, "eepacc_bl_qp_rows: type is NULL");
+    const DevCfg& C = h->cfg;
+    int r = 0;
+    for (int k = 0; k < C.N; ++k)
+        for (int t = 0; t < EEPACC_BL_ROW_N; ++t)
+            if (eepacc::bl_row_present(t, C.bl_mode)) { stage[r] = k; type[r] = t; ++r; }
+    if (C.bl_mode != 2) {
+        stage[r] = C.N; type[r] = EEPACC_BL_ROW_SAFE1; ++r;
+        stage[r] = C.N; type[r] = EEPACC_BL_ROW_SAFE2; ++r;
+    }
+    return EEPACC_OK;
+}
+
+extern "C" int eepacc_bl_build_qp(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
+                                  const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                                  double* H, double* g, double* A, double* lba, double* uba, void* stream) {
+    if (const int rc = bl_qp_handle(h, "eepacc_bl_build_qp")) return rc;
+    if (B < 0 || B > h->max_batch)
+        return fail(EEPACC_EINVAL, "eepacc_bl_build_qp: B = " + std::to_string(B) + " is outside [0, max_batch = " + std::to_string(h->max_batch) + "]");
+    if (B == 0) return EEPACC_OK;
+    const bool tv = h->cfg.bl_mode == 2;                   // no lead vehicle: the three lead arrays are not read
+    const struct { const void* p; const char* name; bool needed; } bufs[] = {
+        {s, "s", true}, {v, "v", true}, {a_prev, "a_prev", true}, {t0, "t0", true}, {s_tv, "s_tv", !tv}, {v_tv, "v_tv", !tv},
+        {a_tv_prev, "a_tv_prev", !tv}, {H, "H", true}, {g, "g", true}, {A, "A", true}, {lba, "lba", true}, {uba, "uba", true}};
+    for (const auto& bf : bufs)
+        if (bf.needed && !bf.p) return fail(EEPACC_EINVAL, std::string("eepacc_bl_build_qp: ") + bf.name + " is NULL");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(eepacc::launch_bl_qp(h->d_cfg, h->cfg.N, eepacc::bl_qp_num_rows(h->cfg), B, s, v, a_prev, t0, tv ? nullptr : s_tv,
+                                tv ? nullptr : v_tv, tv ? nullptr : a_tv_prev, H, g, A, lba, uba, (hipStream_t)stream));
     return EEPACC_OK;
 }
 
@@ -719,7 +772,7 @@ extern "C" int eepacc_fb_step(eepacc_handle* h, int B, const double* s, const do
 static int fb_qp_handle(const eepacc_handle* h, const char* who) {
     if (!h) return fail(EEPACC_EINVAL, std::string(who) + ": NULL handle");
     if (h->n_classes) return fail(EEPACC_ENOTSUP, std::string(who) + ": a handle of eepacc_create_classes runs ABMPC only and has no FBMPC problem");
-    if (h->cfg.bl_mode != 0) return fail(EEPACC_ENOTSUP, std::string(who) + ": the handle was created with bl_mode = " + std::to_string(h->cfg.bl_mode) + "; only the FBMPC problem (CreateQP_FB) is built");
+    if (h->cfg.bl_mode != 0) return fail(EEPACC_ENOTSUP, std::string(who) + ": the handle was created with bl_mode = " + std::to_string(h->cfg.bl_mode) + "; only the FBMPC problem (CreateQP_FB) is built here, eepacc_bl_build_qp builds the problem of such a handle");
     return EEPACC_OK;
 }
 

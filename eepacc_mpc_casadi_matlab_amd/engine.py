@@ -14,7 +14,7 @@ from typing import Any, Dict, NamedTuple, Optional
 import numpy as np
 
 from ._abi import (SettingsHolder, SettingsPOD, Vehicle, make_vehicle, pack_classes, OUT, OUT_N, OUT_FIELDS, KPI_N, FKPI_N, FKPI_WEIGHTS, AB_BUILD_ARGTYPES,
-                   FB_BUILD_ARGTYPES,
+                   FB_BUILD_ARGTYPES, BL_BUILD_ARGTYPES,
                    c_double_p, as_dptr, as_iptr)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -72,7 +72,7 @@ def load_library() -> C.CDLL:
     lib.eepacc_qp_solve_batched.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [dp] * 8 + [dp, dp, dp, vp]
     lib.eepacc_qp_solve_batched_dual.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [dp] * 8 + [dp, dp] + [dp] * 3 + [dp] * 5 + [vp]
     lib.eepacc_qp_kkt_solve_batched.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int] + [dp] * 2 + [dp] * 2 + [dp] * 3 + [dp] * 3 + [dp, vp]
-    for name, argtypes in list(AB_BUILD_ARGTYPES.items()) + list(FB_BUILD_ARGTYPES.items()):
+    for name, argtypes in list(AB_BUILD_ARGTYPES.items()) + list(FB_BUILD_ARGTYPES.items()) + list(BL_BUILD_ARGTYPES.items()):
         getattr(lib, name).argtypes = argtypes
     lib.eepacc_synchronize.argtypes = [vp, vp]
     lib.eepacc_build_flags.restype = C.c_char_p
@@ -89,6 +89,7 @@ ABI_SYMBOLS = ["eepacc_last_error", "eepacc_version", "eepacc_sizeof_settings", 
                "eepacc_last_iterations", "eepacc_qp_solve_batched", "eepacc_qp_solve_batched_dual", "eepacc_qp_kkt_solve_batched",
                "eepacc_ab_qp_size", "eepacc_ab_qp_rows", "eepacc_ab_build_qp",
                "eepacc_fb_qp_size", "eepacc_fb_qp_rows", "eepacc_fb_build_qp",
+               "eepacc_bl_qp_size", "eepacc_bl_qp_rows", "eepacc_bl_build_qp",
                "eepacc_synchronize", "eepacc_build_flags"]
 
 
@@ -125,6 +126,15 @@ class AbQp(NamedTuple):
 
 class FbQp(NamedTuple):
     """What Engine.fb_build_qp returns: the fields of AbQp for the condensed QP of one FBMPC step."""
+    H: Any
+    g: Any
+    A: Any
+    lba: Any
+    uba: Any
+
+
+class BlQp(NamedTuple):
+    """What Engine.bl_build_qp returns: the fields of AbQp for the condensed QP of one BLMPC or TVMPC step."""
     H: Any
     g: Any
     A: Any
@@ -305,6 +315,37 @@ class Engine:
         """eepacc_run_tvmpc: closed loop of n_steps from s0 = TVinitDist, v0 = TVinitVel, a_minus1 (each [B]).
         Returns traj [n_steps, OUT_N, B], status [n_steps, B]; resume / out as run_abmpc."""
         return self._run(self.lib.eepacc_run_tvmpc, (s0, v0, a_minus1), None, n_steps, resume, out)
+
+    # the condensed QP of a baseline (Settings_BL) or target-vehicle (Settings_TV) step as data ---------------------------
+    def bl_qp_size(self):
+        """eepacc_bl_qp_size: (nV, nC) of the condensed QP of a BLMPC or TVMPC step of this engine."""
+        nV, nC = C.c_int(), C.c_int()
+        _check(self.lib.eepacc_bl_qp_size(self.h, C.byref(nV), C.byref(nC)))
+        return nV.value, nC.value
+
+    def bl_qp_rows(self):
+        """eepacc_bl_qp_rows: (stage, type), two int32 arrays [nC]: the horizon stage of every row of the built problem (N for
+        the two terminal rows of the baseline problem) and its type as an index into _abi.BL_ROW_TYPES."""
+        _, nC = self.bl_qp_size()
+        stage = np.empty(nC, dtype=np.int32); typ = np.empty(nC, dtype=np.int32)
+        _check(self.lib.eepacc_bl_qp_rows(self.h, as_iptr(stage), as_iptr(typ)))
+        return stage, typ
+
+    def bl_build_qp(self, s, v, a_prev, t0, s_tv=None, v_tv=None, a_tv_prev=None) -> BlQp:
+        """eepacc_bl_build_qp: the condensed QP the reference poses at this step of RunOpt_BLMPC (:182-230) or RunOpt_TVMPC
+        (:161-208), for the inputs of ab_step on a Settings_BL engine or of tv_step; a target-vehicle engine reads no lead
+        arrays and takes None for them.  Returns BlQp(H [B,nV,nV], g [B,nV], A [B,nC,nV], lba [B,nC], uba [B,nC]) as
+        ab_build_qp does.  Reads and writes no solver state of the engine."""
+        t = self.torch
+        B = int(t.as_tensor(s).numel())
+        ins = [None if x is None else self._d(x, B) for x in (s, v, a_prev, t0, s_tv, v_tv, a_tv_prev)]
+        nV, nC = self.bl_qp_size()
+        f64 = dict(dtype=t.float64, device=self.device)
+        H = t.empty((B, nV, nV), **f64); g = t.empty((B, nV), **f64); A_cm = t.empty((B, nV, nC), **f64)
+        lba = t.empty((B, nC), **f64); uba = t.empty((B, nC), **f64)
+        _check(self.lib.eepacc_bl_build_qp(self.h, B, *[_ptr(x) for x in ins], H.data_ptr(), g.data_ptr(), A_cm.data_ptr(),
+                                           lba.data_ptr(), uba.data_ptr(), self._stream()))
+        return BlQp(H, g, A_cm.transpose(1, 2), lba, uba)
 
     # FBMPC: same two operators (ABO/RunOpt_FBMPC.m:161-331) -----------------------------------
     def fb_step(self, s, v, v_prev, a_prev, Fm_prev, Fb_prev, t0, s_tv, v_tv, a_tv_prev, want_pred: bool = True):

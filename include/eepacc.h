@@ -276,9 +276,10 @@ enum {
  * none: a build between two ABMPC calls leaves their results bit for bit unchanged.  One workgroup per instance writes every
  * entry, zeros included (no memset, no atomics): the arrays do not depend on B or on timing.  EEPACC_EINVAL, with a message
  * that names the argument: a NULL buffer, B < 0 or B > max_batch.  EEPACC_ENOTSUP: a handle of eepacc_create_classes (nC can
- * differ per class) and a handle created with bl_mode 1 or 2.  B = 0 returns EEPACC_OK.
- * The FBMPC problem: eepacc_fb_build_qp below.  Not built: BLMPC and TVMPC handles, class handles, the formulations of
- * solverToUse 0 (dynamics kept as rows) and 2 (HPIPM).
+ * differ per class) and a handle created with bl_mode 1 or 2, whose problem eepacc_bl_build_qp builds.  B = 0 returns
+ * EEPACC_OK.
+ * The FBMPC problem: eepacc_fb_build_qp below; the BLMPC and TVMPC problems: eepacc_bl_build_qp below.  Not built: class
+ * handles, the formulations of solverToUse 0 (dynamics kept as rows) and 2 (HPIPM).
  * Throughput (tools/gpu_ab_build_bench.py, the build against a plain device fill of the same bytes, profiles/ab_build_bench.json):
  * 1.53 of the fill's time at N_hor = 20 x 4096 instances, 1.80 at N_hor = 60 x 1024; DESIGN.md section 3.6a. */
 int  eepacc_ab_qp_size(const eepacc_handle* h, int* nV, int* nC);
@@ -450,7 +451,7 @@ enum {
  * calls leaves their results bit for bit unchanged.  One workgroup per instance writes every entry, zeros included (no
  * memset, no atomics): the arrays do not depend on B or on timing.  EEPACC_EINVAL, with a message that names the argument: a
  * NULL buffer, only one of A22 / D2, B < 0 or B > max_batch.  EEPACC_ENOTSUP: a handle of eepacc_create_classes and a handle
- * created with bl_mode 1 or 2.  B = 0 returns EEPACC_OK.
+ * created with bl_mode 1 or 2, whose problem eepacc_bl_build_qp builds.  B = 0 returns EEPACC_OK.
  * Throughput: see DESIGN.md section 3.6b (tools/gpu_fb_qp_bench.py times the build against a plain device fill). */
 int  eepacc_fb_qp_size(const eepacc_handle* h, int* nV, int* nC);
 int  eepacc_fb_qp_rows(const eepacc_handle* h, int32_t* stage, int32_t* type);
@@ -509,6 +510,67 @@ int  eepacc_run_tvmpc(eepacc_handle* h, int B, int n_steps,
 int  eepacc_run_tvmpc_host(eepacc_handle* h, int B, int n_steps,
                            const double* s0, const double* v0, const double* a_minus1,
                            double* traj, int32_t* status);
+
+/* The condensed QP of one BLMPC or TVMPC step as data, the counterpart of eepacc_ab_build_qp for a handle created with
+ * bl_mode = 1 or 2: what a user of the reference holds as H, c, G, g_lb, g_ub and finds saved as optSol.H, optSol.G of a
+ * baseline run.  The kernels behind eepacc_bl_step / eepacc_tv_step never form it; eepacc_bl_build_qp does, for the inputs of
+ * those entry points (device, each [B]).
+ * bl_mode = 1: the problem of ABO/RunOpt_BLMPC.m:182-230 with solverToUse = 1: estimators and bounds
+ * (EstimateVehicleTrajectory.m:55-88, EstimateRouteAndComfortBounds.m:63-143,173-189), objective and rows of
+ * ABO/Functions/MPCs/CreateQP_BL.m:99-314, condensed as TransformToDenseFormulation.m:30-91.  nV = 2 N_hor, variables per
+ * stage a, xi_f; nC = 13 N_hor + 2.
+ * bl_mode = 2: the problem of ABO/RunOpt_TVMPC.m:161-208 with ABO/Functions/MPCs/CreateQP_TV.m: the rows of CreateQP_BL
+ * without the two safe-distance rows of a stage and without terminal rows, 0.8 of the speed-limit and curve caps
+ * (CreateQP_TV.m:265,271) and the comfort limits of a zero speed estimate (:44-45).  nV = 2 N_hor, nC = 11 N_hor.  The lead
+ * arguments s_tv, v_tv, a_tv_prev are not read and may be NULL.
+ * eepacc_bl_qp_size returns nV and nC of the handle.  Outputs, device, instance-major, in the layout eepacc_qp_solve_batched
+ * reads: H [B][nV*nV], g [B][nV], A [B][nV][nC] (column-major nC x nV), lba, uba [B][nC], an absent side -inf / +inf.  There
+ * are no lbx / ubx; hand the operator NULL.  Rows are in the reference's order.  The jerk terms take Ts = Tvec[0] at every
+ * stage as CreateQP_BL.m:31 does, the dynamics Tvec[k]; the stage-0 jerk rows carry a_minus1 on the right-hand side
+ * (:253-261).  H holds the w_a and w_j terms, also where the reference's weights make it zero (a linear program).  Covered:
+ * both trees, variable Tvec (bl_mode = 1), every N_hor the handle accepts, the estimator modes 0, 1 and 2 (mode 2 reads the
+ * predictions the handle carries from the last step and does not write them), all route features.
+ *
+ * eepacc_bl_qp_rows fills two host arrays [nC]: stage[i] in 0 .. N_hor-1, or N_hor for the two terminal rows
+ * (CreateQP_BL.m:306-314, bl_mode = 1 only), and type[i], one of EEPACC_BL_ROW_*, so that lam_a and ws_a of
+ * eepacc_qp_solve_batched_dual on the built problem can be read row by row: which speed-limit, stop or headway row is tight.
+ * The values ascend in the order of the rows within a stage; bl_mode = 2 uses the same values and has no SAFE1 / SAFE2 rows: */
+enum {
+    EEPACC_BL_ROW_S = 0,     /* CreateQP_BL.m:217-228  0 <= s_k <= s_goal                                                  */
+    EEPACC_BL_ROW_V,         /*   0 <= v_k <= v_max                                                                        */
+    EEPACC_BL_ROW_XI_F,      /*   xi_f >= 0                                                                                */
+    EEPACC_BL_ROW_A_MIN,     /* :232-239  a_k + xi_f >= a_min                                                              */
+    EEPACC_BL_ROW_A_MAX,     /*   a_k - xi_f <= a_max                                                                      */
+    EEPACC_BL_ROW_J_MIN,     /* :242-261  a_k - a_{k-1} + xi_f >= Ts j_min (stage 0: a_minus1 on the right-hand side)      */
+    EEPACC_BL_ROW_J_MAX,     /*   a_k - a_{k-1} - xi_f <= Ts j_max                                                         */
+    EEPACC_BL_ROW_V_LIM,     /* :265-268  v_k - xi_f <= speed limit (bl_mode = 2: 0.8 of it)                               */
+    EEPACC_BL_ROW_V_CURV,    /* :271-274  v_k - xi_f <= curve speed (bl_mode = 2: 0.8 of it)                               */
+    EEPACC_BL_ROW_V_STOP,    /* :277-280  v_k - xi_f <= stop speed                                                         */
+    EEPACC_BL_ROW_V_TL,      /* :283-286  v_k - xi_f <= traffic-light speed                                                */
+    EEPACC_BL_ROW_SAFE1,     /* :289-292  safe distance 1  s_k - xi_f <= s_tv - h_min (terminal row :307-310: no slack)    */
+    EEPACC_BL_ROW_SAFE2,     /* :293-296  safe distance 2  s_k + tau_min v_k - xi_f <= s_tv (terminal row :311-314)        */
+    EEPACC_BL_ROW_N
+};
+/* The built problem is the reference's own.  A measured state outside its hard bounds shows up as a stage-0 row without
+ * coefficients whose bounds exclude 0; the tolerance state_bound_tol of the kernels is not applied, and neither is their
+ * proximal curvature bl_lp_eps.  The constant term of the objective is excluded: 1/2 x'Hx + g'x at a solution equals
+ * EEPACC_OUT_COST of the same step.  With the reference's weights the problem is a linear program with faces of optima: compare
+ * objective values, not points; x[0] of a solution is an EEPACC_OUT_AQP of the face, x[1] an EEPACC_OUT_XI_F.
+ *
+ * The build is asynchronous on stream.  It reads no solver state of the handle (warm start, loop counters, carry) and writes
+ * none: a build between two eepacc_bl_step / eepacc_run_blmpc / eepacc_tv_step calls leaves their results bit for bit
+ * unchanged.  One workgroup per instance writes every entry, zeros included (no memset, no atomics): the arrays do not depend
+ * on B or on timing.  EEPACC_EINVAL, with a message that names the argument: a NULL buffer (the lead arrays excepted with
+ * bl_mode = 2), B < 0 or B > max_batch.  EEPACC_ENOTSUP: a handle of eepacc_create_classes, and a handle created with
+ * bl_mode = 0, whose problems eepacc_ab_build_qp / eepacc_fb_build_qp build.  B = 0 returns EEPACC_OK.
+ * Throughput (tools/gpu_bl_qp_bench.py, the build against a plain device fill of the same bytes, profiles/bl_qp_bench.json):
+ * 1.34 of the fill's time at N_hor = 20 x 4096 instances, 1.69 at N_hor = 60 x 1024; DESIGN.md section 3.6c. */
+int  eepacc_bl_qp_size(const eepacc_handle* h, int* nV, int* nC);
+int  eepacc_bl_qp_rows(const eepacc_handle* h, int32_t* stage, int32_t* type);
+int  eepacc_bl_build_qp(eepacc_handle* h, int B,
+                        const double* s, const double* v, const double* a_prev, const double* t0,
+                        const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                        double* H, double* g, double* A, double* lba, double* uba, void* stream);
 
 /* Post-processing of a closed-loop trajectory (ABO/RunOpt_ABMPC.m:343-349): rpm, Tm,
  * fifth-order battery power P and cumulative energy E, all device [n_steps][B]. */
