@@ -1123,7 +1123,15 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const Cfg& c, WaveMem<MM
                 if (lane == el) set_code(L, et, 0);
             }
             else if (ek == EV_COMPL) { if (lane == el) set_code(L, et, 3); WHY(3); }
-            else if (ek == EV_DROPH) { if (lane == el) set_code(L, et, 0); finished = true; WHY(3); }
+            else if (ek == EV_DROPH) {
+                if (lane == el) set_code(L, et, 0);
+                finished = true; WHY(3);
+                // a penalised row whose slack already lies below its bound (a warm state that belongs to another problem:
+                // w + q xi < 0, the step length above is clipped to zero) leaves He at once and the slack jumps back onto its
+                // bound: discontinuous like EV_CAPIN below, so the multipliers of the working set are re-validated as well
+                // (also taken when w + q xi - lam_q is exactly 0 at a right state: harmless, one repair pass)
+                if (!(tstep > 0.0)) { warm = true; pass = 0; }
+            }
             else if (ek == EV_CAPIN) {
                 // the slack jumps off its bound by the remaining violation: the one discontinuous event of the method.
                 // The multipliers of the working set are re-validated (repair passes) before the next constraint is

@@ -14,6 +14,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from ab_cert_cases import rollout
 from conftest import make_case, load_golden, golden_step_inputs, GOLDEN_AB_VARIANTS, GOLDEN_AB_ICEMAP
 from eepacc_mpc_casadi_matlab_amd._abi import OUT, AB_ROW_TYPES
 from eepacc_mpc_casadi_matlab_amd.scenarios import make_s1, make_s2
@@ -193,12 +194,7 @@ def _round_trip(OPT, V, cols, tree, eng=None):
     cerr = np.abs(cost - o[OUT["cost"]]) / (1 + np.abs(o[OUT["cost"]]))
     print("cost (relative) %.3g" % cerr.max())
     assert cerr.max() < (1e-6 if orig else 1e-8)
-    s = np.empty((N + 1, B)); v = np.empty((N + 1, B))
-    s[0], v[0] = cols["s"], cols["v"]
-    for k in range(N):
-        a = x[:, 5 * k]
-        s[k + 1] = s[k] + T[k] * v[k] + 0.5 * T[k] * T[k] * a
-        v[k + 1] = v[k] + T[k] * a
+    s, v = rollout(x[:, 0:5 * N:5], cols["s"], cols["v"], T)
     print("s_pred %.3g v_pred %.3g" % (np.abs(s - sp).max(), np.abs(v - vp).max()))
     assert np.abs(s - sp).max() < (1e-6 if orig else 1e-8)
     assert np.abs(v - vp).max() < (1e-7 if orig else 1e-9)

@@ -281,3 +281,21 @@ def test_refusals(torch_mod, lead_trace):
     eng.set_classes(sc["class_of"])
     again, ast = _run(eng, sc, resume=True)
     assert np.array_equal(head, full[:5]) and np.array_equal(again, full) and np.array_equal(ast, fst)
+
+
+@pytest.mark.parametrize("cfg", ["abo20", "orig20", "abo33", "orig33"])
+def test_certified_case_table_equals_the_plain_engine(cfg, torch_mod):
+    """The class kernels on active rigid rows: the case table of tests/ab_cert_cases.py (certified against the problem
+    itself by tests/test_gpu_ab_cert.py) through two classes with the same settings, the map alternating, bit for bit against
+    the plain engine.  eepacc_ab_build_qp refuses a class handle, so this is what carries the certificate over."""
+    import ab_cert_cases as T
+    OPT, V = T.settings(cfg)
+    names, cols = T.cases(cfg)
+    B = len(names)
+    eng = _mixed([OPT, dict(OPT)], [V, dict(V)])
+    eng.set_classes((np.arange(B) % 2).astype(np.int32))
+    got = [x.cpu().numpy() for x in eng.ab_step(**cols)]
+    ref = [x.cpu().numpy() for x in _single(OPT, V).ab_step(**cols)]
+    assert int(np.abs(ref[3]).sum()) == 0
+    for name, x, r in zip(("out", "s_pred", "v_pred", "status"), got, ref):
+        assert np.array_equal(x, r), (cfg, name)
