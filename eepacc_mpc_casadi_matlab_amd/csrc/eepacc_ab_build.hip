@@ -14,22 +14,14 @@
 // products are not contracted into fused multiply-adds, so that an entry of A, lba, uba and g has the reference's
 // roundings; the a-a entries of H take the suffix sums of the speed curvature instead of a loop per entry.
 //
-// Dense variable order per stage (5): a, xi_v, xi_h, xi_s, xi_f.  Rows: eepacc_ab_build.h.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
+// Dense variable order per stage (5): a, xi_v, xi_h, xi_s, xi_f.  Rows: eepacc_ab_build.h.  The geometry of the kernel, the
+// row list and the walks over H, the bounds and A are eepacc_qp_build.h's, shared with k_fb_qp and k_bl_qp; the stage
+// quantities, the rows and the entries of H and g are this file's.
 #include "eepacc_ab_build.h"
-
-// also for the estimators of eepacc_stage.h as this file compiles them
-#pragma clang fp contract(off)
-#include "eepacc_stage.h"
+#include "eepacc_qp_build.h"
 
 namespace eepacc {
 namespace {
-
-constexpr int BT = 256;              // threads of a workgroup: four waves
-constexpr int kS = kMaxN + 1;        // stage arrays: index N is the terminal stage
 
 struct Stages {                      // per-stage quantities of the step, static LDS
     double T[kS], stv[kS], chw[kS], ds[kS];
@@ -42,24 +34,11 @@ struct Stages {                      // per-stage quantities of the step, static
     double hd[kS];                   // diagonal of the a-a block
 };
 
-struct Row {                         // one row: as s_k + av v_k + ga a_k + de a_{k-1} + sc xi_slack in [lb, ub]
-    int k, slack;                    // slack 0..3 = xi_v, xi_h, xi_s, xi_f; -1 none
-    double as, av, ga, de, sc, lb, ub;
-};
-
-// Row `type` (EEPACC_AB_ROW_*) of stage k; k == N: the two terminal rows (CreateQP_AB.m:376-387)
+// Row `type` (EEPACC_AB_ROW_*) of stage k; k == N: the two terminal rows (CreateQP_AB.m:376-387).  Slack 0..3 = xi_v, xi_h,
+// xi_s, xi_f
 __device__ inline Row ab_row(const DevCfg& C, const Stages& S, int k, int type, double a_minus1) {
-    Row R;
-    R.k = k; R.slack = -1;
-    R.as = R.av = R.ga = R.de = R.sc = 0.0;
-    R.lb = -INFINITY; R.ub = INFINITY;
-    const int N = C.N;
-    if (k == N) {
-        R.as = 1.0;
-        if (type == EEPACC_AB_ROW_SAFE1) R.ub = S.stv[N - 1] - C.h_min;
-        else { R.av = C.tau_min; R.ub = S.stv[N - 1]; }
-        return R;
-    }
+    Row R = di_row_blank(k, -1);
+    if (k == C.N) { di_row_terminal(R, C, S.stv, type == EEPACC_AB_ROW_SAFE1); return R; }
     const double T = S.T[k];
     const double A_hwp = 2.0;
     switch (type) {
@@ -103,26 +82,18 @@ __global__ void __launch_bounds__(BT) k_ab_build(const DevCfg* __restrict__ cfg,
     const DevCfg& C = *cfg;
     const int N = C.N, nV = 5 * N, tid = threadIdx.x;
     const size_t b = blockIdx.x;
-    const int ld = N | 1;                                   // odd row stride: a column of Ss is read without bank conflicts
+    const int ld = N | 1;
     double* Ss = reinterpret_cast<double*>(smem);           // [N+1][ld]
-    unsigned short* rows = reinterpret_cast<unsigned short*>(Ss + (size_t)(N + 1) * ld);   // [nC]: stage | type << 8
+    unsigned short* rows = qp_build_rows(Ss, N, 1);         // [nC]
     const double s_0 = s[b], v_0 = v[b], a_minus1 = a_prev[b], t_0 = t0[b];
 
     // ---- estimators, bounds and the sparse-form objective per stage (A2, A3, CreateQP_AB.m:150-187)
     if (tid <= N) {
         const int k = tid;
         double se, ve, st, vt;
-        if (C.paramEstSetting == 2) {
-            // EstimateVehicleTrajectory.m:81-88: [x_curr; prev(3:end); prev(end) + Ts v_prev(end)]; the handle carries
-            // the previous step's predictions, which are read and not written here
-            const double* predp = C.pred + b * 128;
-            const int idx = k < N ? k + 1 : N;
-            const double ps = predp[idx], pv = predp[64 + idx];
-            se = k == 0 ? s_0 : (k < N ? ps : ps + C.Tvec[N - 1] * pv);
-            ve = k == 0 ? v_0 : pv;
-        } else {
-            estimate_traj(C, C.paramEstSetting, C.tConstACC_ego, s_0, v_0, a_minus1, k, se, ve);
-        }
+        const double* predp = C.pred + b * 128;
+        ego_estimate(C, s_0, v_0, a_minus1, k, [&](int idx, double& ps, double& pv) { ps = predp[idx]; pv = predp[64 + idx]; },
+                     se, ve);
         estimate_traj(C, C.TVestSetting, C.tConstACC_tar, s_tv[b], v_tv[b], a_tv_prev[b], k, st, vt);
         S.stv[k] = st;
         double hv = 0.0, tv = 0.0, ta = 0.0, T = 0.0, q = 0.0;
@@ -154,13 +125,7 @@ __global__ void __launch_bounds__(BT) k_ab_build(const DevCfg* __restrict__ cfg,
     // ---- position sensitivities and free response; suffix sums and the a-a diagonal; the row catalogue
     if (tid <= N) {
         const int k = tid;
-        double R = 0.0;                                     // T_{k-1} + .. + T_{i+1}, summed downwards as the reference does
-        for (int i = k - 1; i >= 0; --i) {
-            const double Ti = S.T[i];
-            Ss[(size_t)k * ld + i] = 0.5 * Ti * Ti + R * Ti;
-            R += Ti;
-        }
-        S.ds[k] = k == 0 ? s_0 : s_0 + R * v_0;
+        S.ds[k] = di_position_row(S.T, Ss, ld, k, s_0, v_0);
         if (k < N) {
             double hd = 2.0 * C.w_a + S.q[k];                                   // :169-180
             if (k + 1 < N) hd += S.q[k + 1];
@@ -168,11 +133,10 @@ __global__ void __launch_bounds__(BT) k_ab_build(const DevCfg* __restrict__ cfg,
             // first row of the stage: the rows of the stages before it
             int r = (C.ab_route_rows ? 18 : 14) * k;
             for (int j = 0; j < k; ++j) r += C.mb_mask[j] ? 1 : 0;
-            for (int type = 0; type < EEPACC_AB_ROW_N; ++type)
-                if (ab_row_present(type, C.ab_route_rows, C.mb_mask[k])) rows[r++] = (unsigned short)(k | (type << 8));
+            fill_stage_rows(rows, r, k, EEPACC_AB_ROW_N,
+                            [&](int type, int kk) { return ab_row_present(type, C.ab_route_rows, C.mb_mask[kk]); });
         } else {
-            rows[nC - 2] = (unsigned short)(N | (EEPACC_AB_ROW_SAFE1 << 8));
-            rows[nC - 1] = (unsigned short)(N | (EEPACC_AB_ROW_SAFE2 << 8));
+            fill_terminal_rows(rows, nC, N, EEPACC_AB_ROW_SAFE1, EEPACC_AB_ROW_SAFE2);
         }
     } else if (tid == 64) {
         double acc = 0.0;
@@ -181,27 +145,20 @@ __global__ void __launch_bounds__(BT) k_ab_build(const DevCfg* __restrict__ cfg,
     }
     __syncthreads();
 
-    // ---- H, row-major: consecutive lanes write consecutive entries; (ra, rb) advance without a division
-    {
-        double* Hd = H + b * (size_t)nV * nV;
-        const int total = nV * nV, dra = BT / nV, drb = BT % nV;
-        int ra = tid / nV, rb = tid % nV;
-        for (int idx = tid; idx < total; idx += BT) {
-            const int i = ra / 5, ci = ra - 5 * i, j = rb / 5, cj = rb - 5 * j;
-            double h = 0.0;
-            if (ci == 0 && cj == 0) {
-                const int hi = i > j ? i : j, lo = i > j ? j : i;
-                if (i == j) h = S.hd[i];
-                else if (hi == lo + 1) h = -S.q[hi];
-                h += S.T[i] * S.T[j] * S.hsuf[hi + 1];
-            } else if (ra == rb && ci == 2) {
-                h = 2.0 * C.w_h;                                                // :185
-            }
-            Hd[idx] = h;
-            rb += drb; ra += dra;
-            if (rb >= nV) { rb -= nV; ++ra; }
+    // ---- H
+    write_H(H + b * (size_t)nV * nV, nV, tid, [&](int ra, int rb) {
+        const int i = ra / 5, ci = ra - 5 * i, j = rb / 5, cj = rb - 5 * j;
+        double h = 0.0;
+        if (ci == 0 && cj == 0) {
+            const int hi = i > j ? i : j, lo = i > j ? j : i;
+            if (i == j) h = S.hd[i];
+            else if (hi == lo + 1) h = -S.q[hi];
+            h += S.T[i] * S.T[j] * S.hsuf[hi + 1];
+        } else if (ra == rb && ci == 2) {
+            h = 2.0 * C.w_h;                                                    // :185
         }
-    }
+        return h;
+    });
     // ---- g: Psi'(Hs d + cs), the sum over ascending stages (:183-187 for the slacks)
     for (int col = tid; col < nV; col += BT) {
         const int i = col / 5, c = col - 5 * i;
@@ -215,39 +172,12 @@ __global__ void __launch_bounds__(BT) k_ab_build(const DevCfg* __restrict__ cfg,
         }
         g[b * (size_t)nV + col] = gv;
     }
-    // ---- lba, uba: the row's bounds less its value at the free response
-    for (int r = tid; r < nC; r += BT) {
-        const int e = rows[r];
-        const Row R = ab_row(C, S, e & 0xff, e >> 8, a_minus1);
-        const double shift = R.as * S.ds[R.k] + R.av * v_0;
-        lba[b * (size_t)nC + r] = R.lb - shift;
-        uba[b * (size_t)nC + r] = R.ub - shift;
-    }
-    // ---- A, column-major nC x nV: a wave takes 64 consecutive rows (consecutive addresses of one column) and walks the
-    // columns of its quarter of the stages, so the four waves share every block of rows evenly
-    {
-        double* Ad = A + b * (size_t)nV * nC;
-        const int wave = tid >> 6, lane = tid & 63;
-        const int i0 = wave * N / 4, i1 = (wave + 1) * N / 4;
-        for (int r0 = 0; r0 < nC; r0 += 64) {
-            const int r = r0 + lane;
-            if (r >= nC) continue;
-            const int e = rows[r];
-            const Row R = ab_row(C, S, e & 0xff, e >> 8, a_minus1);
-            const int k = R.k;
-            double* col = Ad + (size_t)(5 * i0) * nC + r;
-            for (int i = i0; i < i1; ++i) {
-                double va = 0.0;
-                if (i < k) { va = R.as * Ss[(size_t)k * ld + i]; va += R.av * S.T[i]; }
-                if (i == k) va = R.ga;
-                if (i == k - 1) va += R.de;
-                col[0] = va;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) col[(size_t)(1 + c) * nC] = (i == k && c == R.slack) ? R.sc : 0.0;
-                col += (size_t)5 * nC;
-            }
-        }
-    }
+    // ---- lba, uba, A
+    const auto decode = [&](int e) { return ab_row(C, S, row_stage(e), row_type(e), a_minus1); };
+    write_bounds(lba + b * (size_t)nC, uba + b * (size_t)nC, rows, nC, tid,
+                 [&](int e) { return di_bounds(decode(e), S.ds, v_0); });
+    write_A<1, 4>(A + b * (size_t)nV * nC, rows, N, nC, tid, decode,
+                  [&](const Row& R, int k, int i, double* x) { x[0] = di_A_entry(R, Ss, ld, S.T, k, i); });
 }
 
 }  // namespace
@@ -255,9 +185,8 @@ __global__ void __launch_bounds__(BT) k_ab_build(const DevCfg* __restrict__ cfg,
 hipError_t launch_ab_build(const DevCfg* cfg, int N, int nC, int B, const double* s, const double* v, const double* a_prev,
                            const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
                            double* H, double* g, double* A, double* lba, double* uba, hipStream_t stream) {
-    const size_t smem = (size_t)(N + 1) * (N | 1) * sizeof(double) + (size_t)nC * sizeof(unsigned short);
-    hipLaunchKernelGGL(k_ab_build, dim3(B), dim3(BT), smem, stream, cfg, nC, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev,
-                       H, g, A, lba, uba);
+    hipLaunchKernelGGL(k_ab_build, dim3(B), dim3(BT), qp_build_smem_bytes(N, nC, 1), stream, cfg, nC, s, v, a_prev, t0,
+                       s_tv, v_tv, a_tv_prev, H, g, A, lba, uba);
     return hipGetLastError();
 }
 

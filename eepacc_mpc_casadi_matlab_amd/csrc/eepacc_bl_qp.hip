@@ -1,8 +1,10 @@
 // eepacc_bl_qp.hip -- the condensed QP of one BLMPC step (bl_mode = 1) or TVMPC step (bl_mode = 2), written out as data:
 // H, g, A, lba, uba in the layout the dense QP operator reads.  The closed-loop kernels never form this problem; this
 // kernel is the boundary for callers who want it: to compare objective values on the faces of the LP, to read which
-// speed-limit, stop or headway row is tight, to hand the problem to another solver.  Geometry of k_ab_build
-// (eepacc_ab_build.hip): one workgroup of 256 threads per instance, stage quantities into LDS once.
+// speed-limit, stop or headway row is tight, to hand the problem to another solver.  The geometry of the kernel (one workgroup
+// of 256 threads per instance, stage quantities into LDS once), the row list, the walks over H, the bounds and A, and the
+// double-integrator pieces it has in common with k_ab_build (the row type, Ss, the entry of A) are eepacc_qp_build.h's; the
+// stage quantities, the rows and the entries of H and g are this file's.
 //
 // Reference, bl_mode = 1: ABO/RunOpt_BLMPC.m:182-230 with solverToUse = 1: estimators (EstimateVehicleTrajectory.m:55-88),
 // bounds (EstimateRouteAndComfortBounds.m:63-143,173-189), objective and rows of ABO/Functions/MPCs/CreateQP_BL.m:99-314
@@ -19,45 +21,22 @@
 // multiply-adds, so that an entry of A, lba, uba and g has the reference's roundings.
 //
 // Dense variable order per stage (2): a, xi_f.  Rows: eepacc_bl_qp.h.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
 #include "eepacc_bl_qp.h"
-
-// also for the estimators of eepacc_stage.h as this file compiles them
-#pragma clang fp contract(off)
-#include "eepacc_stage.h"
+#include "eepacc_qp_build.h"
 
 namespace eepacc {
 namespace {
-
-constexpr int BT = 256;              // threads of a workgroup: four waves
-constexpr int kS = kMaxN + 1;        // stage arrays: index N is the terminal stage
 
 struct Stages {                      // per-stage quantities of the step, static LDS
     double T[kS], stv[kS], ds[kS];
     double v_lim[kS], v_curv[kS], v_stop[kS], v_TL[kS], a_min[kS], a_max[kS], j_min[kS], j_max[kS];
 };
 
-struct Row {                         // one row: as s_k + av v_k + ga a_k + de a_{k-1} + sc xi_f in [lb, ub]
-    int k;
-    double as, av, ga, de, sc, lb, ub;
-};
-
-// Row `type` (EEPACC_BL_ROW_*) of stage k; k == N: the two terminal rows (CreateQP_BL.m:306-314)
+// Row `type` (EEPACC_BL_ROW_*) of stage k; k == N: the two terminal rows (CreateQP_BL.m:306-314).  The one slack of a stage
+// is xi_f, index 0
 __device__ inline Row bl_row(const DevCfg& C, const Stages& S, int k, int type, double a_minus1) {
-    Row R;
-    R.k = k;
-    R.as = R.av = R.ga = R.de = R.sc = 0.0;
-    R.lb = -INFINITY; R.ub = INFINITY;
-    const int N = C.N;
-    if (k == N) {
-        R.as = 1.0;
-        if (type == EEPACC_BL_ROW_SAFE1) R.ub = S.stv[N - 1] - C.h_min;
-        else { R.av = C.tau_min; R.ub = S.stv[N - 1]; }
-        return R;
-    }
+    Row R = di_row_blank(k, 0);
+    if (k == C.N) { di_row_terminal(R, C, S.stv, type == EEPACC_BL_ROW_SAFE1); return R; }
     const double Ts = C.Tvec[0];                                                                    // :31
     switch (type) {
     case EEPACC_BL_ROW_S: R.as = 1.0; R.lb = 0.0; R.ub = C.s_goal; break;                           // :217-228
@@ -95,9 +74,9 @@ __global__ void __launch_bounds__(BT) k_bl_qp(const DevCfg* __restrict__ cfg, in
     const int N = C.N, nV = 2 * N, tid = threadIdx.x;
     const bool tv = C.bl_mode == 2;
     const size_t b = blockIdx.x;
-    const int ld = N | 1;                                   // odd row stride: a column of Ss is read without bank conflicts
+    const int ld = N | 1;
     double* Ss = reinterpret_cast<double*>(smem);           // [N+1][ld]
-    unsigned short* rows = reinterpret_cast<unsigned short*>(Ss + (size_t)(N + 1) * ld);   // [nC]: stage | type << 8
+    unsigned short* rows = qp_build_rows(Ss, N, 1);         // [nC]
     const double s_0 = s[b], v_0 = v[b], a_minus1 = a_prev[b], t_0 = t0[b];
     const double Ts = C.Tvec[0];                                                // CreateQP_BL.m:31, CreateQP_TV.m:29
     const double q = 2.0 * C.w_j / (Ts * Ts);                                   // jerk curvature, CreateQP_BL.m:138-145
@@ -106,17 +85,9 @@ __global__ void __launch_bounds__(BT) k_bl_qp(const DevCfg* __restrict__ cfg, in
     if (tid <= N) {
         const int k = tid;
         double se, ve, st = 0.0, vt;
-        if (C.paramEstSetting == 2) {
-            // EstimateVehicleTrajectory.m:81-88: [x_curr; prev(3:end); prev(end) + Ts v_prev(end)]; the handle carries
-            // the previous step's predictions, which are read and not written here
-            const double* predp = C.pred + b * 128;
-            const int idx = k < N ? k + 1 : N;
-            const double ps = predp[idx], pv = predp[64 + idx];
-            se = k == 0 ? s_0 : (k < N ? ps : ps + C.Tvec[N - 1] * pv);
-            ve = k == 0 ? v_0 : pv;
-        } else {
-            estimate_traj(C, C.paramEstSetting, C.tConstACC_ego, s_0, v_0, a_minus1, k, se, ve);
-        }
+        const double* predp = C.pred + b * 128;
+        ego_estimate(C, s_0, v_0, a_minus1, k, [&](int idx, double& ps, double& pv) { ps = predp[idx]; pv = predp[64 + idx]; },
+                     se, ve);
         // (target-vehicle MPC: no lead vehicle, RunOpt_TVMPC.m:157 estimates its own trajectory only)
         if (!tv) estimate_traj(C, C.TVestSetting, C.tConstACC_tar, s_tv[b], v_tv[b], a_tv_prev[b], k, st, vt);
         S.stv[k] = st;
@@ -135,41 +106,26 @@ __global__ void __launch_bounds__(BT) k_bl_qp(const DevCfg* __restrict__ cfg, in
     // ---- position sensitivities and free response; the row catalogue
     if (tid <= N) {
         const int k = tid;
-        double R = 0.0;                                     // T_{k-1} + .. + T_{i+1}, summed downwards as the reference does
-        for (int i = k - 1; i >= 0; --i) {
-            const double Ti = S.T[i];
-            Ss[(size_t)k * ld + i] = 0.5 * Ti * Ti + R * Ti;
-            R += Ti;
-        }
-        S.ds[k] = k == 0 ? s_0 : s_0 + R * v_0;
+        S.ds[k] = di_position_row(S.T, Ss, ld, k, s_0, v_0);
         if (k < N) {
-            int r = bl_rows_per_stage(C.bl_mode) * k;       // first row of the stage
-            for (int type = 0; type < EEPACC_BL_ROW_N; ++type)
-                if (bl_row_present(type, C.bl_mode)) rows[r++] = (unsigned short)(k | (type << 8));
+            fill_stage_rows(rows, bl_rows_per_stage(C.bl_mode) * k, k, EEPACC_BL_ROW_N,
+                            [&](int type, int) { return bl_row_present(type, C.bl_mode); });
         } else if (!tv) {
-            rows[nC - 2] = (unsigned short)(N | (EEPACC_BL_ROW_SAFE1 << 8));
-            rows[nC - 1] = (unsigned short)(N | (EEPACC_BL_ROW_SAFE2 << 8));
+            fill_terminal_rows(rows, nC, N, EEPACC_BL_ROW_SAFE1, EEPACC_BL_ROW_SAFE2);
         }
     }
     __syncthreads();
 
-    // ---- H, row-major: consecutive lanes write consecutive entries; (ra, rb) advance without a division
-    {
-        double* Hd = H + b * (size_t)nV * nV;
-        const int total = nV * nV, dra = BT / nV, drb = BT % nV;
-        int ra = tid / nV, rb = tid % nV;
-        for (int idx = tid; idx < total; idx += BT) {
-            double h = 0.0;
-            if (((ra | rb) & 1) == 0) {                                         // a_i, a_j: CreateQP_BL.m:134-145
-                const int i = ra >> 1, j = rb >> 1;
-                if (i == j) { h = 2.0 * C.w_a + q; if (i + 1 < N) h += q; }
-                else if (i == j + 1 || j == i + 1) h = 0.0 - q;
-            }
-            Hd[idx] = h;
-            rb += drb; ra += dra;
-            if (rb >= nV) { rb -= nV; ++ra; }
+    // ---- H
+    write_H(H + b * (size_t)nV * nV, nV, tid, [&](int ra, int rb) {
+        double h = 0.0;
+        if (((ra | rb) & 1) == 0) {                                             // a_i, a_j: CreateQP_BL.m:134-145
+            const int i = ra >> 1, j = rb >> 1;
+            if (i == j) { h = 2.0 * C.w_a + q; if (i + 1 < N) h += q; }
+            else if (i == j + 1 || j == i + 1) h = 0.0 - q;
         }
-    }
+        return h;
+    });
     // ---- g: Psi' cs, the sum over ascending stages: -w_v on v_{i+1} .. v_N (:131,304), the jerk term of stage 0 (:141), w_f (:148)
     for (int col = tid; col < nV; col += BT) {
         const int i = col >> 1;
@@ -183,38 +139,12 @@ __global__ void __launch_bounds__(BT) k_bl_qp(const DevCfg* __restrict__ cfg, in
         }
         g[b * (size_t)nV + col] = gv;
     }
-    // ---- lba, uba: the row's bounds less its value at the free response
-    for (int r = tid; r < nC; r += BT) {
-        const int e = rows[r];
-        const Row R = bl_row(C, S, e & 0xff, e >> 8, a_minus1);
-        const double shift = R.as * S.ds[R.k] + R.av * v_0;
-        lba[b * (size_t)nC + r] = R.lb - shift;
-        uba[b * (size_t)nC + r] = R.ub - shift;
-    }
-    // ---- A, column-major nC x nV: a wave takes 64 consecutive rows (consecutive addresses of one column) and walks the
-    // columns of its quarter of the stages, so the four waves share every block of rows evenly
-    {
-        double* Ad = A + b * (size_t)nV * nC;
-        const int wave = tid >> 6, lane = tid & 63;
-        const int i0 = wave * N / 4, i1 = (wave + 1) * N / 4;
-        for (int r0 = 0; r0 < nC; r0 += 64) {
-            const int r = r0 + lane;
-            if (r >= nC) continue;
-            const int e = rows[r];
-            const Row R = bl_row(C, S, e & 0xff, e >> 8, a_minus1);
-            const int k = R.k;
-            double* col = Ad + (size_t)(2 * i0) * nC + r;
-            for (int i = i0; i < i1; ++i) {
-                double va = 0.0;
-                if (i < k) { va = R.as * Ss[(size_t)k * ld + i]; va += R.av * S.T[i]; }
-                if (i == k) va = R.ga;
-                if (i == k - 1) va += R.de;
-                col[0] = va;
-                col[nC] = i == k ? R.sc : 0.0;
-                col += (size_t)2 * nC;
-            }
-        }
-    }
+    // ---- lba, uba, A
+    const auto decode = [&](int e) { return bl_row(C, S, row_stage(e), row_type(e), a_minus1); };
+    write_bounds(lba + b * (size_t)nC, uba + b * (size_t)nC, rows, nC, tid,
+                 [&](int e) { return di_bounds(decode(e), S.ds, v_0); });
+    write_A<1, 1>(A + b * (size_t)nV * nC, rows, N, nC, tid, decode,
+                  [&](const Row& R, int k, int i, double* x) { x[0] = di_A_entry(R, Ss, ld, S.T, k, i); });
 }
 
 }  // namespace
@@ -222,9 +152,8 @@ __global__ void __launch_bounds__(BT) k_bl_qp(const DevCfg* __restrict__ cfg, in
 hipError_t launch_bl_qp(const DevCfg* cfg, int N, int nC, int B, const double* s, const double* v, const double* a_prev,
                         const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
                         double* H, double* g, double* A, double* lba, double* uba, hipStream_t stream) {
-    const size_t smem = (size_t)(N + 1) * (N | 1) * sizeof(double) + (size_t)nC * sizeof(unsigned short);
-    hipLaunchKernelGGL(k_bl_qp, dim3(B), dim3(BT), smem, stream, cfg, nC, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev,
-                       H, g, A, lba, uba);
+    hipLaunchKernelGGL(k_bl_qp, dim3(B), dim3(BT), qp_build_smem_bytes(N, nC, 1), stream, cfg, nC, s, v, a_prev, t0,
+                       s_tv, v_tv, a_tv_prev, H, g, A, lba, uba);
     return hipGetLastError();
 }
 

@@ -370,101 +370,123 @@ extern "C" int eepacc_run_tvmpc(eepacc_handle* h, int B, int n_steps, const doub
     return rc != EEPACC_OK ? rc : ab_run_impl(h, "eepacc_run_tvmpc", "eepacc_run_tvmpc: bad B / n_steps", B, n_steps, s0, v0, a_minus1, nullptr, nullptr, traj, status, stream);
 }
 
-// The condensed QP of an ABMPC step as data (eepacc_ab_build.hip).  Only a handle of eepacc_create with bl_mode = 0 has it.
-static int ab_qp_handle(const eepacc_handle* h, const char* who) {
-    if (!h) return fail(EEPACC_EINVAL, std::string(who) + ": NULL handle");
-    if (h->n_classes) return fail(EEPACC_ENOTSUP, std::string(who) + ": a handle of eepacc_create_classes has no single problem size (nC can differ per class)");
-    if (h->cfg.bl_mode != 0) return fail(EEPACC_ENOTSUP, std::string(who) + ": the handle was created with bl_mode = " + std::to_string(h->cfg.bl_mode) + "; only the ABMPC problem (CreateQP_AB) is built here, eepacc_bl_build_qp builds the problem of such a handle");
+// ---- the condensed QP of a step as data: eepacc_{ab,fb,bl}_qp_size, _qp_rows, _build_qp.  What the three families do alike is
+// written once, over a descriptor of the family.
+struct QpFamily {
+    const char* stem;                       // name stem of the three entry points
+    const char* on_classes;                 // refusal of a handle of eepacc_create_classes
+    bool bl_handle;                         // the family of a handle with bl_mode != 0 (else: of one with bl_mode = 0)
+    const char* on_mode;                    // refusal of a handle of the other kind, after "... bl_mode = <n>"
+    int nV_stage;                           // variables per stage
+    int (*nC)(const DevCfg&);
+    int n_types, safe1, safe2;              // row types of a stage; the two terminal rows
+    bool (*present)(const DevCfg&, int type, int k);
+    bool (*terminal_rows)(const DevCfg&);   // has terminal rows; the lead buffers are required with them
+};
+
+static const QpFamily kQpAB = {
+    "eepacc_ab", ": a handle of eepacc_create_classes has no single problem size (nC can differ per class)", false,
+    "; only the ABMPC problem (CreateQP_AB) is built here, eepacc_bl_build_qp builds the problem of such a handle",
+    5, eepacc::ab_qp_num_rows, EEPACC_AB_ROW_N, EEPACC_AB_ROW_SAFE1, EEPACC_AB_ROW_SAFE2,
+    [](const DevCfg& C, int t, int k) { return eepacc::ab_row_present(t, C.ab_route_rows, C.mb_mask[k]); },
+    [](const DevCfg&) { return true; }};
+// Only a handle of eepacc_create with bl_mode = 1 or 2 has the BLMPC / TVMPC problem.  TVMPC has no lead vehicle: no terminal
+// rows, and the three lead arrays are not read
+static const QpFamily kQpBL = {
+    "eepacc_bl", ": a handle of eepacc_create_classes has no baseline or target-vehicle problem (its classes are ABMPC settings)", true,
+    "; eepacc_ab_build_qp / eepacc_fb_build_qp build its problems, only the BLMPC and TVMPC problems (CreateQP_BL, CreateQP_TV) are built here",
+    2, eepacc::bl_qp_num_rows, EEPACC_BL_ROW_N, EEPACC_BL_ROW_SAFE1, EEPACC_BL_ROW_SAFE2,
+    [](const DevCfg& C, int t, int) { return eepacc::bl_row_present(t, C.bl_mode); },
+    [](const DevCfg& C) { return C.bl_mode != 2; }};
+static const QpFamily kQpFB = {
+    "eepacc_fb", ": a handle of eepacc_create_classes runs ABMPC only and has no FBMPC problem", false,
+    "; only the FBMPC problem (CreateQP_FB) is built here, eepacc_bl_build_qp builds the problem of such a handle",
+    6, eepacc::fb_qp_num_rows, EEPACC_FB_ROW_N, EEPACC_FB_ROW_SAFE1, EEPACC_FB_ROW_SAFE2,
+    [](const DevCfg& C, int t, int k) { return eepacc::fb_row_present(t, C.mb_mask[k]); },
+    [](const DevCfg&) { return true; }};
+
+static int qp_handle(const QpFamily& F, const eepacc_handle* h, const std::string& who) {
+    if (!h) return fail(EEPACC_EINVAL, who + ": NULL handle");
+    if (h->n_classes) return fail(EEPACC_ENOTSUP, who + F.on_classes);
+    if ((h->cfg.bl_mode != 0) != F.bl_handle)
+        return fail(EEPACC_ENOTSUP, who + ": the handle was created with bl_mode = " + std::to_string(h->cfg.bl_mode) + F.on_mode);
     return EEPACC_OK;
 }
 
-extern "C" int eepacc_ab_qp_size(const eepacc_handle* h, int* nV, int* nC) {
-    if (const int rc = ab_qp_handle(h, "eepacc_ab_qp_size")) return rc;
-    if (!nV) return fail(EEPACC_EINVAL, "eepacc_ab_qp_size: nV is NULL");
-    if (!nC) return fail(EEPACC_EINVAL, "eepacc_ab_qp_size: nC is NULL");
-    *nV = 5 * h->cfg.N;
-    *nC = eepacc::ab_qp_num_rows(h->cfg);
+static int qp_size_impl(const QpFamily& F, const eepacc_handle* h, int* nV, int* nC) {
+    const std::string who = std::string(F.stem) + "_qp_size";
+    if (const int rc = qp_handle(F, h, who)) return rc;
+    if (!nV) return fail(EEPACC_EINVAL, who + ": nV is NULL");
+    if (!nC) return fail(EEPACC_EINVAL, who + ": nC is NULL");
+    *nV = F.nV_stage * h->cfg.N;
+    *nC = F.nC(h->cfg);
     return EEPACC_OK;
 }
 
-extern "C" int eepacc_ab_qp_rows(const eepacc_handle* h, int32_t* stage, int32_t* type) {
-    if (const int rc = ab_qp_handle(h, "eepacc_ab_qp_rows")) return rc;
-    if (!stage) return fail(EEPACC_EINVAL, "eepacc_ab_qp_rows: stage is NULL");
-    if (!type) return fail(EEPACC_EINVAL, "eepacc_ab_qp_rows: type is NULL");
+static int qp_rows_impl(const QpFamily& F, const eepacc_handle* h, int32_t* stage, int32_t* type) {
+    const std::string who = std::string(F.stem) + "_qp_rows";
+    if (const int rc = qp_handle(F, h, who)) return rc;
+    if (!stage) return fail(EEPACC_EINVAL, who + ": stage is NULL");
+    if (!type) return fail(EEPACC_EINVAL, who + ": type is NULL");
     const DevCfg& C = h->cfg;
     int r = 0;
     for (int k = 0; k < C.N; ++k)
-        for (int t = 0; t < EEPACC_AB_ROW_N; ++t)
-            if (eepacc::ab_row_present(t, C.ab_route_rows, C.mb_mask[k])) { stage[r] = k; type[r] = t; ++r; }
-    stage[r] = C.N; type[r] = EEPACC_AB_ROW_SAFE1; ++r;
-    stage[r] = C.N; type[r] = EEPACC_AB_ROW_SAFE2; ++r;
+        for (int t = 0; t < F.n_types; ++t)
+            if (F.present(C, t, k)) { stage[r] = k; type[r] = t; ++r; }
+    if (F.terminal_rows(C)) {
+        stage[r] = C.N; type[r] = F.safe1; ++r;
+        stage[r] = C.N; type[r] = F.safe2; ++r;
+    }
     return EEPACC_OK;
 }
+
+// The arguments every _build_qp has, in the order of its parameter list
+struct QpBufs { const double *s, *v, *a_prev, *t0, *s_tv, *v_tv, *a_tv_prev, *H, *g, *A, *lba, *uba; };
+
+// Handle, B range, NULL buffers.  *launch: there is something to build (B > 0)
+static int build_args_check(const QpFamily& F, const eepacc_handle* h, int B, const QpBufs& b, bool* launch) {
+    const std::string who = std::string(F.stem) + "_build_qp";
+    *launch = false;
+    if (const int rc = qp_handle(F, h, who)) return rc;
+    if (B < 0 || B > h->max_batch)
+        return fail(EEPACC_EINVAL, who + ": B = " + std::to_string(B) + " is outside [0, max_batch = " + std::to_string(h->max_batch) + "]");
+    if (B == 0) return EEPACC_OK;
+    const bool lead = F.terminal_rows(h->cfg);
+    const struct { const void* p; const char* name; bool needed; } bufs[] = {
+        {b.s, "s", true}, {b.v, "v", true}, {b.a_prev, "a_prev", true}, {b.t0, "t0", true}, {b.s_tv, "s_tv", lead},
+        {b.v_tv, "v_tv", lead}, {b.a_tv_prev, "a_tv_prev", lead}, {b.H, "H", true}, {b.g, "g", true}, {b.A, "A", true},
+        {b.lba, "lba", true}, {b.uba, "uba", true}};
+    for (const auto& bf : bufs)
+        if (bf.needed && !bf.p) return fail(EEPACC_EINVAL, who + ": " + bf.name + " is NULL");
+    *launch = true;
+    return EEPACC_OK;
+}
+
+extern "C" int eepacc_ab_qp_size(const eepacc_handle* h, int* nV, int* nC) { return qp_size_impl(kQpAB, h, nV, nC); }
+extern "C" int eepacc_ab_qp_rows(const eepacc_handle* h, int32_t* stage, int32_t* type) { return qp_rows_impl(kQpAB, h, stage, type); }
 
 extern "C" int eepacc_ab_build_qp(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
                                   const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
                                   double* H, double* g, double* A, double* lba, double* uba, void* stream) {
-    if (const int rc = ab_qp_handle(h, "eepacc_ab_build_qp")) return rc;
-    if (B < 0 || B > h->max_batch)
-        return fail(EEPACC_EINVAL, "eepacc_ab_build_qp: B = " + std::to_string(B) + " is outside [0, max_batch = " + std::to_string(h->max_batch) + "]");
-    if (B == 0) return EEPACC_OK;
-    const struct { const void* p; const char* name; } bufs[] = {
-        {s, "s"}, {v, "v"}, {a_prev, "a_prev"}, {t0, "t0"}, {s_tv, "s_tv"}, {v_tv, "v_tv"}, {a_tv_prev, "a_tv_prev"},
-        {H, "H"}, {g, "g"}, {A, "A"}, {lba, "lba"}, {uba, "uba"}};
-    for (const auto& bf : bufs)
-        if (!bf.p) return fail(EEPACC_EINVAL, std::string("eepacc_ab_build_qp: ") + bf.name + " is NULL");
+    bool launch;
+    if (const int rc = build_args_check(kQpAB, h, B, {s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, H, g, A, lba, uba}, &launch)) return rc;
+    if (!launch) return EEPACC_OK;
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(eepacc::launch_ab_build(h->d_cfg, h->cfg.N, eepacc::ab_qp_num_rows(h->cfg), B, s, v, a_prev, t0, s_tv, v_tv,
                                    a_tv_prev, H, g, A, lba, uba, (hipStream_t)stream));
     return EEPACC_OK;
 }
 
-// The condensed QP of a BLMPC or TVMPC step as data (eepacc_bl_qp.hip).  Only a handle of eepacc_create with bl_mode = 1 or 2 has it.
-static int bl_qp_handle(const eepacc_handle* h, const char* who) {
-    if (!h) return fail(EEPACC_EINVAL, std::string(who) + ": NULL handle");
-    if (h->n_classes) return fail(EEPACC_ENOTSUP, std::string(who) + ": a handle of eepacc_create_classes has no baseline or target-vehicle problem (its classes are ABMPC settings)");
-    if (h->cfg.bl_mode == 0) return fail(EEPACC_ENOTSUP, std::string(who) + ": the handle was created with bl_mode = 0; eepacc_ab_build_qp / eepacc_fb_build_qp build its problems, only the BLMPC and TVMPC problems (CreateQP_BL, CreateQP_TV) are built here");
-    return EEPACC_OK;
-}
-
-extern "C" int eepacc_bl_qp_size(const eepacc_handle* h, int* nV, int* nC) {
-    if (const int rc = bl_qp_handle(h, "eepacc_bl_qp_size")) return rc;
-    if (!nV) return fail(EEPACC_EINVAL, "eepacc_bl_qp_size: nV is NULL");
-    if (!nC) return fail(EEPACC_EINVAL, "eepacc_bl_qp_size: nC is NULL");
-    *nV = 2 * h->cfg.N;
-    *nC = eepacc::bl_qp_num_rows(h->cfg);
-    return EEPACC_OK;
-}
-
-extern "C" int eepacc_bl_qp_rows(const eepacc_handle* h, int32_t* stage, int32_t* type) {
-    if (const int rc = bl_qp_handle(h, "eepacc_bl_qp_rows")) return rc;
-    if (!stage) return fail(EEPACC_EINVAL, "eepacc_bl_qp_rows: stage is NULL");
-    if (!type) return fail(EEPACC_EINVAL, "eepacc_bl_qp_rows: type is NULL");
-    const DevCfg& C = h->cfg;
-    int r = 0;
-    for (int k = 0; k < C.N; ++k)
-        for (int t = 0; t < EEPACC_BL_ROW_N; ++t)
-            if (eepacc::bl_row_present(t, C.bl_mode)) { stage[r] = k; type[r] = t; ++r; }
-    if (C.bl_mode != 2) {
-        stage[r] = C.N; type[r] = EEPACC_BL_ROW_SAFE1; ++r;
-        stage[r] = C.N; type[r] = EEPACC_BL_ROW_SAFE2; ++r;
-    }
-    return EEPACC_OK;
-}
+extern "C" int eepacc_bl_qp_size(const eepacc_handle* h, int* nV, int* nC) { return qp_size_impl(kQpBL, h, nV, nC); }
+extern "C" int eepacc_bl_qp_rows(const eepacc_handle* h, int32_t* stage, int32_t* type) { return qp_rows_impl(kQpBL, h, stage, type); }
 
 extern "C" int eepacc_bl_build_qp(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
                                   const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
                                   double* H, double* g, double* A, double* lba, double* uba, void* stream) {
-    if (const int rc = bl_qp_handle(h, "eepacc_bl_build_qp")) return rc;
-    if (B < 0 || B > h->max_batch)
-        return fail(EEPACC_EINVAL, "eepacc_bl_build_qp: B = " + std::to_string(B) + " is outside [0, max_batch = " + std::to_string(h->max_batch) + "]");
-    if (B == 0) return EEPACC_OK;
+    bool launch;
+    if (const int rc = build_args_check(kQpBL, h, B, {s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, H, g, A, lba, uba}, &launch)) return rc;
+    if (!launch) return EEPACC_OK;
     const bool tv = h->cfg.bl_mode == 2;                   // no lead vehicle: the three lead arrays are not read
-    const struct { const void* p; const char* name; bool needed; } bufs[] = {
-        {s, "s", true}, {v, "v", true}, {a_prev, "a_prev", true}, {t0, "t0", true}, {s_tv, "s_tv", !tv}, {v_tv, "v_tv", !tv},
-        {a_tv_prev, "a_tv_prev", !tv}, {H, "H", true}, {g, "g", true}, {A, "A", true}, {lba, "lba", true}, {uba, "uba", true}};
-    for (const auto& bf : bufs)
-        if (bf.needed && !bf.p) return fail(EEPACC_EINVAL, std::string("eepacc_bl_build_qp: ") + bf.name + " is NULL");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(eepacc::launch_bl_qp(h->d_cfg, h->cfg.N, eepacc::bl_qp_num_rows(h->cfg), B, s, v, a_prev, t0, tv ? nullptr : s_tv,
                                 tv ? nullptr : v_tv, tv ? nullptr : a_tv_prev, H, g, A, lba, uba, (hipStream_t)stream));
@@ -663,7 +685,7 @@ extern "C" int eepacc_qp_kkt_solve_batched(eepacc_handle* h, int B, int nV, int 
 // FBMPC (ABO/RunOpt_FBMPC.m:161-331): build kernel -> dense QP operator -> extraction, per step.
 static int fb_prepare(eepacc_handle* h, int B) {
     const int N = h->cfg.N;
-    const size_t nV = 6 * (size_t)N, nC = (size_t)h->cfg.fb_row0[N] + 2;
+    const size_t nV = 6 * (size_t)N, nC = (size_t)eepacc::fb_qp_num_rows(h->cfg);
     if (nV > EEPACC_QP_MAX_NV || nC > EEPACC_QP_MAX_NC || eepacc_qp_dense_lds_bytes((int)nV, (int)nC) > 160 * 1024)
         return fail(EEPACC_ENOTSUP, "FBMPC: horizon too long for the dense QP operator");
     if (B <= h->fb.B) return EEPACC_OK;
@@ -698,7 +720,7 @@ static int fb_prepare(eepacc_handle* h, int B) {
 static int fb_one_step(eepacc_handle* h, int B, int mode, const double* s, const double* v, const double* a_prev,
                        const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
                        double* out, double* s_pred, double* v_pred, int32_t* status, hipStream_t stream) {
-    const int N = h->cfg.N, nV = 6 * N, nC = h->cfg.fb_row0[N] + 2;
+    const int N = h->cfg.N, nV = 6 * N, nC = eepacc::fb_qp_num_rows(h->cfg);
     for (int b0 = 0; b0 < B; b0 += h->fb.chunk) {
         const int nb = (B - b0 < h->fb.chunk) ? B - b0 : h->fb.chunk;
         eepacc::eepacc_fb_args a;
@@ -768,51 +790,18 @@ extern "C" int eepacc_fb_step(eepacc_handle* h, int B, const double* s, const do
     return fb_one_step(h, B, 0, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, out, s_pred, v_pred, status, (hipStream_t)stream);
 }
 
-// The condensed QP of an FBMPC step as data (eepacc_fb_qp.hip).  Only a handle of eepacc_create with bl_mode = 0 has it.
-static int fb_qp_handle(const eepacc_handle* h, const char* who) {
-    if (!h) return fail(EEPACC_EINVAL, std::string(who) + ": NULL handle");
-    if (h->n_classes) return fail(EEPACC_ENOTSUP, std::string(who) + ": a handle of eepacc_create_classes runs ABMPC only and has no FBMPC problem");
-    if (h->cfg.bl_mode != 0) return fail(EEPACC_ENOTSUP, std::string(who) + ": the handle was created with bl_mode = " + std::to_string(h->cfg.bl_mode) + "; only the FBMPC problem (CreateQP_FB) is built here, eepacc_bl_build_qp builds the problem of such a handle");
-    return EEPACC_OK;
-}
-
-extern "C" int eepacc_fb_qp_size(const eepacc_handle* h, int* nV, int* nC) {
-    if (const int rc = fb_qp_handle(h, "eepacc_fb_qp_size")) return rc;
-    if (!nV) return fail(EEPACC_EINVAL, "eepacc_fb_qp_size: nV is NULL");
-    if (!nC) return fail(EEPACC_EINVAL, "eepacc_fb_qp_size: nC is NULL");
-    *nV = 6 * h->cfg.N;
-    *nC = h->cfg.fb_row0[h->cfg.N] + 2;
-    return EEPACC_OK;
-}
-
-extern "C" int eepacc_fb_qp_rows(const eepacc_handle* h, int32_t* stage, int32_t* type) {
-    if (const int rc = fb_qp_handle(h, "eepacc_fb_qp_rows")) return rc;
-    if (!stage) return fail(EEPACC_EINVAL, "eepacc_fb_qp_rows: stage is NULL");
-    if (!type) return fail(EEPACC_EINVAL, "eepacc_fb_qp_rows: type is NULL");
-    const DevCfg& C = h->cfg;
-    int r = 0;
-    for (int k = 0; k < C.N; ++k)
-        for (int t = 0; t < EEPACC_FB_ROW_N; ++t)
-            if (eepacc::fb_row_present(t, C.mb_mask[k])) { stage[r] = k; type[r] = t; ++r; }
-    stage[r] = C.N; type[r] = EEPACC_FB_ROW_SAFE1; ++r;
-    stage[r] = C.N; type[r] = EEPACC_FB_ROW_SAFE2; ++r;
-    return EEPACC_OK;
-}
+// The condensed QP of an FBMPC step as data (eepacc_fb_qp.hip): kQpFB above.  After the checks every family has, the model
+// and the carried state of the handle.
+extern "C" int eepacc_fb_qp_size(const eepacc_handle* h, int* nV, int* nC) { return qp_size_impl(kQpFB, h, nV, nC); }
+extern "C" int eepacc_fb_qp_rows(const eepacc_handle* h, int32_t* stage, int32_t* type) { return qp_rows_impl(kQpFB, h, stage, type); }
 
 extern "C" int eepacc_fb_build_qp(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
                                   const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
                                   const double* A22, const double* D2, double* H, double* g, double* A, double* lba,
                                   double* uba, double* A22_used, double* D2_used, void* stream) {
-    const char* who = "eepacc_fb_build_qp";
-    if (const int rc = fb_qp_handle(h, who)) return rc;
-    if (B < 0 || B > h->max_batch)
-        return fail(EEPACC_EINVAL, "eepacc_fb_build_qp: B = " + std::to_string(B) + " is outside [0, max_batch = " + std::to_string(h->max_batch) + "]");
-    if (B == 0) return EEPACC_OK;
-    const struct { const void* p; const char* name; } bufs[] = {
-        {s, "s"}, {v, "v"}, {a_prev, "a_prev"}, {t0, "t0"}, {s_tv, "s_tv"}, {v_tv, "v_tv"}, {a_tv_prev, "a_tv_prev"},
-        {H, "H"}, {g, "g"}, {A, "A"}, {lba, "lba"}, {uba, "uba"}};
-    for (const auto& bf : bufs)
-        if (!bf.p) return fail(EEPACC_EINVAL, std::string("eepacc_fb_build_qp: ") + bf.name + " is NULL");
+    bool launch;
+    if (const int rc = build_args_check(kQpFB, h, B, {s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, H, g, A, lba, uba}, &launch)) return rc;
+    if (!launch) return EEPACC_OK;
     if (!A22 != !D2)
         return fail(EEPACC_EINVAL, std::string("eepacc_fb_build_qp: ") + (A22 ? "D2" : "A22") + " is NULL while " + (A22 ? "A22" : "D2") + " is given; pass both or neither");
     const DevCfg& C = h->cfg;
@@ -820,7 +809,7 @@ extern "C" int eepacc_fb_build_qp(eepacc_handle* h, int B, const double* s, cons
         return fail(EEPACC_EINVAL, "eepacc_fb_build_qp: A22 and D2 are given, but with FBuseTaylor = 0 no model is carried (A22 = 1, D2 from the step's estimate); pass NULL");
     const int N = C.N;
     eepacc::fb_qp_args a;
-    a.cfg = h->d_cfg; a.B = B; a.nC = C.fb_row0[N] + 2;
+    a.cfg = h->d_cfg; a.B = B; a.nC = eepacc::fb_qp_num_rows(C);
     a.s = s; a.v = v; a.a_prev = a_prev; a.t0 = t0; a.s_tv = s_tv; a.v_tv = v_tv; a.a_tv_prev = a_tv_prev;
     a.H = H; a.g = g; a.A = A; a.lba = lba; a.uba = uba; a.A22_used = A22_used; a.D2_used = D2_used;
     a.A22 = a.D2 = a.sp = a.vp = eepacc::FbCarried{nullptr, 0, 0};

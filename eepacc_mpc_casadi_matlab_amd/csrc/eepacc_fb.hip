@@ -7,7 +7,9 @@
 // done as literal dense products: with B_k = T_k/(lambda m) [0 0; 1 1] only the state rows of Psi
 // are dense, and they are the columns Sv[.,i], Ss[.,i] of the speed / position sensitivities to
 // the force of stage i; the sparse-form Hessian is block tridiagonal in (v,Fm,Fb)_k.  Each
-// entry of the dense H, g, A is assembled directly from those pieces (O(N) work per entry).
+// entry of the dense H, g, A is assembled directly from those pieces (O(N) work per entry), by the
+// device functions of eepacc_fb_condense.h, which k_fb_qp (eepacc_fb_qp.hip) calls too.  The model
+// update and the measurement block are this kernel's own.
 //
 // Dense variable order per stage (6): Fm, Fb, xi_v, xi_h, xi_s, xi_f.  Rows per stage: 26, in the
 // order of CreateQP_FB.m:311-473, plus the two terminal rows :478-489.
@@ -16,6 +18,7 @@
 #include <stdint.h>
 
 #include "eepacc_fb.h"
+#include "eepacc_fb_condense.h"
 #include "eepacc_fb_rows.h"
 #include "eepacc_stage.h"
 #include "../../include/eepacc.h"
@@ -45,7 +48,7 @@ __global__ void __launch_bounds__(FT) k_fb_build(eepacc_fb_args a) {
     extern __shared__ __align__(16) double smem_d[];
     const DevCfg& C = *a.cfg;
     const int N = C.N, B = a.B, b = a.b0 + blockIdx.x, tid = threadIdx.x;
-    const int nV = 6 * N, nC = C.fb_row0[N] + 2;
+    const int nV = 6 * N, nC = fb_qp_num_rows(C);
     StageData S;
     carve(S, smem_d, N);
     const double Ts = C.Tvec[0];
@@ -120,128 +123,23 @@ __global__ void __launch_bounds__(FT) k_fb_build(eepacc_fb_args a) {
         S.A22[k] = A22; S.D2[k] = D2;
     }
     __syncthreads();
-    // ---- sensitivities of (s_k, v_k) to the force of stage i, and the free response d
-    if (tid < N) {
-        const int i = tid;
-        double ss = 0.0, sv = 0.0;
-        for (int k = 0; k <= N; ++k) {
-            if (k == i + 1) { ss = 0.0; sv = C.Tvec[i] / lm; }
-            else if (k > i + 1) { double ns = ss + C.Tvec[k - 1] * sv; sv = S.A22[k - 1] * sv; ss = ns; }
-            S.Ss[(size_t)k * N + i] = ss; S.Sv[(size_t)k * N + i] = sv;
-        }
-    } else if (tid == N) {
-        double ss = s_0, sv = v_0;
-        S.ds[0] = ss; S.dv[0] = sv;
-        for (int k = 1; k <= N; ++k) {
-            double ns = ss + C.Tvec[k - 1] * sv;
-            sv = S.A22[k - 1] * sv + S.D2[k - 1];
-            ss = ns;
-            S.ds[k] = ss; S.dv[k] = sv;
-        }
-    }
+    // ---- sensitivities of (s_k, v_k) to the force of stage i, and the free response d (eepacc_fb_condense.h)
+    if (tid < N) fb_sens_column(C, S, S.Sv, S.Ss, N, tid, lm);
+    else if (tid == N) fb_free_response(C, S, s_0, v_0);
     // ---- block-tridiagonal sparse-form Hessian over (v,Fm,Fb)_k and linear term (CreateQP_FB.m:181-215)
-    if (tid <= N) {
-        const int k = tid;
-        double D[9], O[9], cs[3];
-        for (int e = 0; e < 9; ++e) { D[e] = 0.0; O[e] = 0.0; }
-        cs[0] = cs[1] = cs[2] = 0.0;
-        if (k < N) {
-            const double w_P = C.fb_w[0], w_a = C.fb_w[1], w_j = C.fb_w[2];
-            const double* bq = C.b_quadr;
-            const double K = (30.0 / M_PI) * C.phi;
-            const double ve = S.v_est[k];
-            // power :181-184
-            D[0] += w_P * 2.0 * K * K * bq[5]; D[1] += w_P * K * bq[4]; D[3] += w_P * K * bq[4]; D[4] += w_P * 2.0 * bq[3];
-            cs[0] += w_P * K * bq[2]; cs[1] += w_P * bq[1];
-            // acceleration :187-191
-            const double fa = 2.0 * w_a / (lm * lm);
-            D[0] += fa * (za * za * ve * ve + za * zeta_rg);
-            D[1] += fa * (-za * ve); D[2] += fa * (-za * ve); D[3] += fa * (-za * ve); D[6] += fa * (-za * ve);
-            D[4] += fa; D[5] += fa; D[7] += fa; D[8] += fa;
-            cs[1] += w_a / (lm * lm) * (-2.0 * zeta_rg); cs[2] += w_a / (lm * lm) * (-2.0 * zeta_rg);
-            // jerk :194-208
-            const double Tp = C.Tvec[k];
-            const double f = 2.0 * w_j / ((lm * Tp) * (lm * Tp));
-            if (k == 0) {
-                D[4] += f; D[5] += f; D[7] += f; D[8] += f;
-                const double cc = 2.0 * w_j * (za * v_0 * v_0 + zeta_rg + lm * a_minus1) / ((lm * Tp) * (lm * Tp));
-                cs[1] -= cc; cs[2] -= cc;
-            } else {
-                const double vk = ve, vp = S.v_est[k - 1];
-                // lower-right block of the 6x6 coupling (current stage) and the coupling block O_k
-                D[0] += f * (za * za * vp * vp);
-                D[1] += f * (-za * vk); D[2] += f * (-za * vk); D[3] += f * (-za * vk); D[6] += f * (-za * vk);
-                D[4] += f; D[5] += f; D[7] += f; D[8] += f;
-                O[0] = f * (-za * za * vk * vp); O[1] = f * (za * vp); O[2] = f * (za * vp);
-                O[3] = f * (za * vk); O[4] = -f; O[5] = -f;
-                O[6] = f * (za * vk); O[7] = -f; O[8] = -f;
-            }
-            if (k + 1 < N) {
-                // upper-left block of stage k+1's coupling lands on this stage
-                const double Tn = C.Tvec[k + 1];
-                const double fn = 2.0 * w_j / ((lm * Tn) * (lm * Tn));
-                const double vk = S.v_est[k + 1], vp = ve;
-                D[0] += fn * (za * za * vk * vk);
-                D[1] += fn * (-za * vp); D[2] += fn * (-za * vp); D[3] += fn * (-za * vp); D[6] += fn * (-za * vp);
-                D[4] += fn; D[5] += fn; D[7] += fn; D[8] += fn;
-            }
-        }
-        for (int e = 0; e < 9; ++e) { S.Dblk[9 * k + e] = D[e]; S.Oblk[9 * k + e] = O[e]; }
-        for (int e = 0; e < 3; ++e) S.cs[3 * k + e] = cs[e];
-    }
+    if (tid <= N) fb_hessian_blocks(C, S, tid, v_0, a_minus1, lm, za, zeta_rg);
     __syncthreads();
     // tmp = Hs d + cs on the (v,Fm,Fb) rows
-    if (tid < 3 * N) {
-        const int k = tid / 3, c = tid % 3;
-        double t = S.Dblk[9 * k + 3 * c + 0] * S.dv[k] + S.cs[3 * k + c];
-        if (k >= 1) t += S.Oblk[9 * k + 0 * 3 + c] * S.dv[k - 1];
-        if (k + 1 < N) t += S.Oblk[9 * (k + 1) + 3 * c + 0] * S.dv[k + 1];
-        S.tmp[3 * k + c] = t;
-    }
+    if (tid < 3 * N) fb_tmp_entry(C, S, tid);
     __syncthreads();
     const size_t lb_ = blockIdx.x;                         // index inside the chunk the QP arrays hold
     double* Hd = a.H + lb_ * nV * nV;
     double* gd = a.g + lb_ * nV;
     double* Ad = a.A + lb_ * nC * nV;
-    // ---- g
-    for (int col = tid; col < nV; col += FT) {
-        const int i = col / 6, c = col % 6;
-        double gv;
-        if (c < 2) {
-            gv = S.tmp[3 * i + 1 + c];
-            for (int k = i + 1; k < N; ++k) gv += S.Sv[(size_t)k * N + i] * S.tmp[3 * k];
-        } else {
-            gv = (c == 2) ? C.fb_w[3] : (c == 3) ? 1e2 * C.fb_w[4] : (c == 4) ? C.fb_w[5] : C.fb_w[6];
-        }
-        gd[col] = gv;
-    }
-    // ---- H
-    for (int idx = tid; idx < nV * nV; idx += FT) {
-        const int ra = idx / nV, rb = idx % nV;
-        const int i = ra / 6, ci = ra % 6, j = rb / 6, cj = rb % 6;
-        double h = 0.0;
-        if (ci < 2 && cj < 2) {
-            const int k0 = (i > j ? i : j) + 1;
-            for (int k = k0; k < N; ++k) h += S.Dblk[9 * k] * S.Sv[(size_t)k * N + i] * S.Sv[(size_t)k * N + j];
-            for (int k = 1; k < N; ++k)
-                h += S.Oblk[9 * k] * (S.Sv[(size_t)(k - 1) * N + i] * S.Sv[(size_t)k * N + j] +
-                                      S.Sv[(size_t)k * N + i] * S.Sv[(size_t)(k - 1) * N + j]);
-            // v-F cross terms
-            h += S.Sv[(size_t)j * N + i] * S.Dblk[9 * j + 1 + cj];
-            if (j >= 1) h += S.Sv[(size_t)(j - 1) * N + i] * S.Oblk[9 * j + 1 + cj];
-            if (j + 1 < N) h += S.Sv[(size_t)(j + 1) * N + i] * S.Oblk[9 * (j + 1) + 3 * (1 + cj)];
-            h += S.Sv[(size_t)i * N + j] * S.Dblk[9 * i + 1 + ci];
-            if (i >= 1) h += S.Sv[(size_t)(i - 1) * N + j] * S.Oblk[9 * i + 1 + ci];
-            if (i + 1 < N) h += S.Sv[(size_t)(i + 1) * N + j] * S.Oblk[9 * (i + 1) + 3 * (1 + ci)];
-            // F-F
-            if (i == j) h += S.Dblk[9 * i + 3 * (1 + ci) + 1 + cj];
-            else if (j == i + 1) h += S.Oblk[9 * j + 3 * (1 + ci) + 1 + cj];
-            else if (i == j + 1) h += S.Oblk[9 * i + 3 * (1 + cj) + 1 + ci];
-        } else if (ra == rb && ci == 3) {
-            h = 2.0 * C.fb_w[4];
-        }
-        Hd[idx] = h;
-    }
+    // ---- g, H
+    const double h_xih = 2.0 * C.fb_w[4];
+    for (int col = tid; col < nV; col += FT) gd[col] = fb_g_entry(C, S, S.Sv, N, N, col);
+    for (int idx = tid; idx < nV * nV; idx += FT) Hd[idx] = fb_H_entry(S, S.Sv, N, N, h_xih, idx / nV, idx % nV);
     // ---- A (column-major nC x nV), lba, uba
     for (int r = tid; r < nC; r += FT) {
         // stage of row r (stages own 26 rows, 28 with the two blocked-move rows CreateQP_FB.m:346-356 after the bounds)
@@ -262,12 +160,10 @@ __global__ void __launch_bounds__(FT) k_fb_build(eepacc_fb_args a) {
         a.lba[lb_ * nC + r] = R.lb - shift;
         a.uba[lb_ * nC + r] = R.ub - shift;
         for (int i = 0; i < N; ++i) {
-            const double st = R.as * S.Ss[(size_t)k * N + i] + R.av * S.Sv[(size_t)k * N + i];
-            double cF0 = st, cF1 = st;
-            if (i == k) { cF0 += R.aFm; cF1 += R.aFb; }
-            if (i == k - 1) { cF0 += R.aFmp; cF1 += R.aFbp; }
-            Ad[(size_t)(6 * i + 0) * nC + r] = cF0;
-            Ad[(size_t)(6 * i + 1) * nC + r] = cF1;
+            double cF[2];
+            fb_A_entry(R, S.Ss + (size_t)k * N, S.Sv + (size_t)k * N, k, i, cF);
+            Ad[(size_t)(6 * i + 0) * nC + r] = cF[0];
+            Ad[(size_t)(6 * i + 1) * nC + r] = cF[1];
 #pragma unroll
             for (int c = 0; c < 4; ++c) Ad[(size_t)(6 * i + 2 + c) * nC + r] = (i == k && c == R.slack) ? R.sc : 0.0;
         }

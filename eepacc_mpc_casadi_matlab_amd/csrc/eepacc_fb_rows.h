@@ -92,6 +92,9 @@ __host__ __device__ inline bool fb_row_present(int type, int blocked) {
     return (type != EEPACC_FB_ROW_BLOCKED_FM && type != EEPACC_FB_ROW_BLOCKED_FB) || blocked != 0;
 }
 
+// Rows of the problem: those of the stages and the two terminal rows
+__host__ __device__ inline int fb_qp_num_rows(const DevCfg& C) { return C.fb_row0[C.N] + 2; }
+
 // Row `type` (EEPACC_FB_ROW_*) of stage k; k == N: the two terminal rows, EEPACC_FB_ROW_SAFE1 and _SAFE2
 template <class SD>
 __device__ RowDesc fb_row_typed(const DevCfg& C, const SD& S, int k, int type, double s_0, double v_0, double a_minus1) {

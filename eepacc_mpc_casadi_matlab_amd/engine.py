@@ -260,23 +260,39 @@ class Engine:
         _check(fn(self.h, B, n_steps, *[x.data_ptr() for x in ins + lead], traj.data_ptr(), status.data_ptr(), self._stream()))
         return traj, status
 
+    # the condensed QP of a step as data: what ab_, fb_ and bl_ do alike -------------------------
+    def _qp_size(self, fn):
+        nV, nC = C.c_int(), C.c_int()
+        _check(fn(self.h, C.byref(nV), C.byref(nC)))
+        return nV.value, nC.value
+
+    def _qp_rows(self, size_fn, rows_fn):
+        _, nC = self._qp_size(size_fn)
+        stage = np.empty(nC, dtype=np.int32); typ = np.empty(nC, dtype=np.int32)
+        _check(rows_fn(self.h, as_iptr(stage), as_iptr(typ)))
+        return stage, typ
+
+    def _qp_outputs(self, B, nV, nC):
+        """The five outputs of a _build_qp as the entry point writes them, and A as the caller sees it: the transposed view of
+        its column-major buffer."""
+        t = self.torch
+        f64 = dict(dtype=t.float64, device=self.device)
+        bufs = [t.empty(shape, **f64) for shape in ((B, nV, nV), (B, nV), (B, nV, nC), (B, nC), (B, nC))]
+        H, g, A_cm, lba, uba = bufs
+        return [x.data_ptr() for x in bufs], (H, g, A_cm.transpose(1, 2), lba, uba)
+
     # B2 ------------------------------------------------------------------------------------
     def ab_step(self, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, want_pred: bool = True):
         return self._step(self.lib.eepacc_ab_step, (s, v, a_prev, t0, s_tv, v_tv, a_tv_prev), want_pred)
 
     def ab_qp_size(self):
         """eepacc_ab_qp_size: (nV, nC) of the condensed QP of an ABMPC step of this engine."""
-        nV, nC = C.c_int(), C.c_int()
-        _check(self.lib.eepacc_ab_qp_size(self.h, C.byref(nV), C.byref(nC)))
-        return nV.value, nC.value
+        return self._qp_size(self.lib.eepacc_ab_qp_size)
 
     def ab_qp_rows(self):
         """eepacc_ab_qp_rows: (stage, type), two int32 arrays [nC]: the horizon stage of every row of the built problem (N for
         the two terminal rows) and its type as an index into _abi.AB_ROW_TYPES."""
-        _, nC = self.ab_qp_size()
-        stage = np.empty(nC, dtype=np.int32); typ = np.empty(nC, dtype=np.int32)
-        _check(self.lib.eepacc_ab_qp_rows(self.h, as_iptr(stage), as_iptr(typ)))
-        return stage, typ
+        return self._qp_rows(self.lib.eepacc_ab_qp_size, self.lib.eepacc_ab_qp_rows)
 
     def ab_build_qp(self, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev) -> AbQp:
         """eepacc_ab_build_qp: the condensed QP the reference poses at this step (ABO/RunOpt_ABMPC.m:238-252), for the inputs
@@ -286,13 +302,9 @@ class Engine:
         t = self.torch
         B = int(t.as_tensor(s).numel())
         ins = [self._d(x, B) for x in (s, v, a_prev, t0, s_tv, v_tv, a_tv_prev)]
-        nV, nC = self.ab_qp_size()
-        f64 = dict(dtype=t.float64, device=self.device)
-        H = t.empty((B, nV, nV), **f64); g = t.empty((B, nV), **f64); A_cm = t.empty((B, nV, nC), **f64)
-        lba = t.empty((B, nC), **f64); uba = t.empty((B, nC), **f64)
-        _check(self.lib.eepacc_ab_build_qp(self.h, B, *[x.data_ptr() for x in ins], H.data_ptr(), g.data_ptr(), A_cm.data_ptr(),
-                                           lba.data_ptr(), uba.data_ptr(), self._stream()))
-        return AbQp(H, g, A_cm.transpose(1, 2), lba, uba)
+        ptrs, qp = self._qp_outputs(B, *self.ab_qp_size())
+        _check(self.lib.eepacc_ab_build_qp(self.h, B, *[x.data_ptr() for x in ins], *ptrs, self._stream()))
+        return AbQp(*qp)
 
     # B1 ------------------------------------------------------------------------------------
     def run_abmpc(self, s0, v0, a_minus1, s_tv, v_tv, resume: bool = False, out=None, by_name_bl: bool = False):
@@ -319,17 +331,12 @@ class Engine:
     # the condensed QP of a baseline (Settings_BL) or target-vehicle (Settings_TV) step as data ---------------------------
     def bl_qp_size(self):
         """eepacc_bl_qp_size: (nV, nC) of the condensed QP of a BLMPC or TVMPC step of this engine."""
-        nV, nC = C.c_int(), C.c_int()
-        _check(self.lib.eepacc_bl_qp_size(self.h, C.byref(nV), C.byref(nC)))
-        return nV.value, nC.value
+        return self._qp_size(self.lib.eepacc_bl_qp_size)
 
     def bl_qp_rows(self):
         """eepacc_bl_qp_rows: (stage, type), two int32 arrays [nC]: the horizon stage of every row of the built problem (N for
         the two terminal rows of the baseline problem) and its type as an index into _abi.BL_ROW_TYPES."""
-        _, nC = self.bl_qp_size()
-        stage = np.empty(nC, dtype=np.int32); typ = np.empty(nC, dtype=np.int32)
-        _check(self.lib.eepacc_bl_qp_rows(self.h, as_iptr(stage), as_iptr(typ)))
-        return stage, typ
+        return self._qp_rows(self.lib.eepacc_bl_qp_size, self.lib.eepacc_bl_qp_rows)
 
     def bl_build_qp(self, s, v, a_prev, t0, s_tv=None, v_tv=None, a_tv_prev=None) -> BlQp:
         """eepacc_bl_build_qp: the condensed QP the reference poses at this step of RunOpt_BLMPC (:182-230) or RunOpt_TVMPC
@@ -339,13 +346,9 @@ class Engine:
         t = self.torch
         B = int(t.as_tensor(s).numel())
         ins = [None if x is None else self._d(x, B) for x in (s, v, a_prev, t0, s_tv, v_tv, a_tv_prev)]
-        nV, nC = self.bl_qp_size()
-        f64 = dict(dtype=t.float64, device=self.device)
-        H = t.empty((B, nV, nV), **f64); g = t.empty((B, nV), **f64); A_cm = t.empty((B, nV, nC), **f64)
-        lba = t.empty((B, nC), **f64); uba = t.empty((B, nC), **f64)
-        _check(self.lib.eepacc_bl_build_qp(self.h, B, *[_ptr(x) for x in ins], H.data_ptr(), g.data_ptr(), A_cm.data_ptr(),
-                                           lba.data_ptr(), uba.data_ptr(), self._stream()))
-        return BlQp(H, g, A_cm.transpose(1, 2), lba, uba)
+        ptrs, qp = self._qp_outputs(B, *self.bl_qp_size())
+        _check(self.lib.eepacc_bl_build_qp(self.h, B, *[_ptr(x) for x in ins], *ptrs, self._stream()))
+        return BlQp(*qp)
 
     # FBMPC: same two operators (ABO/RunOpt_FBMPC.m:161-331) -----------------------------------
     def fb_step(self, s, v, v_prev, a_prev, Fm_prev, Fb_prev, t0, s_tv, v_tv, a_tv_prev, want_pred: bool = True):
@@ -357,17 +360,12 @@ class Engine:
 
     def fb_qp_size(self):
         """eepacc_fb_qp_size: (nV, nC) of the condensed QP of an FBMPC step of this engine."""
-        nV, nC = C.c_int(), C.c_int()
-        _check(self.lib.eepacc_fb_qp_size(self.h, C.byref(nV), C.byref(nC)))
-        return nV.value, nC.value
+        return self._qp_size(self.lib.eepacc_fb_qp_size)
 
     def fb_qp_rows(self):
         """eepacc_fb_qp_rows: (stage, type), two int32 arrays [nC]: the horizon stage of every row of the built problem (N for
         the two terminal rows) and its type as an index into _abi.FB_ROW_TYPES."""
-        _, nC = self.fb_qp_size()
-        stage = np.empty(nC, dtype=np.int32); typ = np.empty(nC, dtype=np.int32)
-        _check(self.lib.eepacc_fb_qp_rows(self.h, as_iptr(stage), as_iptr(typ)))
-        return stage, typ
+        return self._qp_rows(self.lib.eepacc_fb_qp_size, self.lib.eepacc_fb_qp_rows)
 
     def fb_build_qp(self, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, A22=None, D2=None, want_model: bool = False):
         """eepacc_fb_build_qp: the condensed QP the reference poses at this FBMPC step (ABO/RunOpt_FBMPC.m:215-264), for the
@@ -379,16 +377,11 @@ class Engine:
         B = int(t.as_tensor(s).numel())
         ins = [self._d(x, B) for x in (s, v, a_prev, t0, s_tv, v_tv, a_tv_prev)]
         model = [None if x is None else self._d(x, self.N * B) for x in (A22, D2)]
-        nV, nC = self.fb_qp_size()
-        f64 = dict(dtype=t.float64, device=self.device)
-        H = t.empty((B, nV, nV), **f64); g = t.empty((B, nV), **f64); A_cm = t.empty((B, nV, nC), **f64)
-        lba = t.empty((B, nC), **f64); uba = t.empty((B, nC), **f64)
-        used = [t.empty((self.N, B), **f64) if want_model else None for _ in range(2)]
-        _check(self.lib.eepacc_fb_build_qp(self.h, B, *[x.data_ptr() for x in ins], _ptr(model[0]), _ptr(model[1]),
-                                           H.data_ptr(), g.data_ptr(), A_cm.data_ptr(), lba.data_ptr(), uba.data_ptr(),
+        ptrs, qp = self._qp_outputs(B, *self.fb_qp_size())
+        used = [t.empty((self.N, B), dtype=t.float64, device=self.device) if want_model else None for _ in range(2)]
+        _check(self.lib.eepacc_fb_build_qp(self.h, B, *[x.data_ptr() for x in ins], _ptr(model[0]), _ptr(model[1]), *ptrs,
                                            _ptr(used[0]), _ptr(used[1]), self._stream()))
-        q = FbQp(H, g, A_cm.transpose(1, 2), lba, uba)
-        return FbQpModel(*q, used[0], used[1]) if want_model else q
+        return FbQpModel(*qp, used[0], used[1]) if want_model else FbQp(*qp)
 
     def postprocess(self, traj):
         t = self.torch

@@ -280,8 +280,9 @@ enum {
  * EEPACC_OK.
  * The FBMPC problem: eepacc_fb_build_qp below; the BLMPC and TVMPC problems: eepacc_bl_build_qp below.  Not built: class
  * handles, the formulations of solverToUse 0 (dynamics kept as rows) and 2 (HPIPM).
- * Throughput (tools/gpu_ab_build_bench.py, the build against a plain device fill of the same bytes, profiles/ab_build_bench.json):
- * 1.53 of the fill's time at N_hor = 20 x 4096 instances, 1.80 at N_hor = 60 x 1024; DESIGN.md section 3.6a. */
+ * Throughput (tools/gpu_qp_build_bench.py --family ab, the build against a plain device fill of the same bytes,
+ * profiles/ab_build_bench.json): 1.53 of the fill's time at N_hor = 20 x 4096 instances, 1.80 at N_hor = 60 x 1024; DESIGN.md
+ * section 3.6a. */
 int  eepacc_ab_qp_size(const eepacc_handle* h, int* nV, int* nC);
 int  eepacc_ab_qp_rows(const eepacc_handle* h, int32_t* stage, int32_t* type);
 int  eepacc_ab_build_qp(eepacc_handle* h, int B,
@@ -452,7 +453,8 @@ enum {
  * memset, no atomics): the arrays do not depend on B or on timing.  EEPACC_EINVAL, with a message that names the argument: a
  * NULL buffer, only one of A22 / D2, B < 0 or B > max_batch.  EEPACC_ENOTSUP: a handle of eepacc_create_classes and a handle
  * created with bl_mode 1 or 2, whose problem eepacc_bl_build_qp builds.  B = 0 returns EEPACC_OK.
- * Throughput: see DESIGN.md section 3.6b (tools/gpu_fb_qp_bench.py times the build against a plain device fill). */
+ * Throughput: see DESIGN.md section 3.6b (tools/gpu_qp_build_bench.py --family fb times the build against a plain device
+ * fill). */
 int  eepacc_fb_qp_size(const eepacc_handle* h, int* nV, int* nC);
 int  eepacc_fb_qp_rows(const eepacc_handle* h, int32_t* stage, int32_t* type);
 int  eepacc_fb_build_qp(eepacc_handle* h, int B,
@@ -563,8 +565,9 @@ enum {
  * on B or on timing.  EEPACC_EINVAL, with a message that names the argument: a NULL buffer (the lead arrays excepted with
  * bl_mode = 2), B < 0 or B > max_batch.  EEPACC_ENOTSUP: a handle of eepacc_create_classes, and a handle created with
  * bl_mode = 0, whose problems eepacc_ab_build_qp / eepacc_fb_build_qp build.  B = 0 returns EEPACC_OK.
- * Throughput (tools/gpu_bl_qp_bench.py, the build against a plain device fill of the same bytes, profiles/bl_qp_bench.json):
- * 1.34 of the fill's time at N_hor = 20 x 4096 instances, 1.69 at N_hor = 60 x 1024; DESIGN.md section 3.6c. */
+ * Throughput (tools/gpu_qp_build_bench.py --family bl, the build against a plain device fill of the same bytes,
+ * profiles/bl_qp_bench.json): 1.34 of the fill's time at N_hor = 20 x 4096 instances, 1.69 at N_hor = 60 x 1024; DESIGN.md
+ * section 3.6c. */
 int  eepacc_bl_qp_size(const eepacc_handle* h, int* nV, int* nC);
 int  eepacc_bl_qp_rows(const eepacc_handle* h, int32_t* stage, int32_t* type);
 int  eepacc_bl_build_qp(eepacc_handle* h, int B,

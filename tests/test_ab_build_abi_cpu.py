@@ -3,11 +3,13 @@ ctypes mirror in _abi.py, and the header's row-type enum against AB_ROW_TYPES.  
 import ctypes as C
 import os
 import re
+import subprocess
 
 import pytest
 
 from conftest import ROOT
 from eepacc_mpc_casadi_matlab_amd import _abi, engine
+from eepacc_mpc_casadi_matlab_amd import build as eb
 
 HDR = open(os.path.join(ROOT, "include", "eepacc.h")).read()
 NAMES = ["eepacc_ab_qp_size", "eepacc_ab_qp_rows", "eepacc_ab_build_qp"]
@@ -75,3 +77,20 @@ def test_library_exports_and_refuses_a_null_handle():
     assert lib.eepacc_last_error().decode() == "eepacc_ab_qp_size: NULL handle"
     assert lib.eepacc_ab_build_qp(None, 1, *([None] * 12), None) == -1
     assert lib.eepacc_last_error().decode() == "eepacc_ab_build_qp: NULL handle"
+
+
+def test_kernel_file_cross_compiles_for_gfx950(tmp_path):
+    """As the FB and BL builders' CPU tests do for their units: the unit compiles for the device on its own, the kernel is in
+    the object and keeps nothing in scratch."""
+    assert "eepacc_ab_build.hip" in eb.SOURCES
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    obj = str(tmp_path / "eepacc_ab_build.o")
+    cmd = [hipcc] + eb.BASE_FLAGS + ["-x", "hip", "--cuda-device-only", "-c", os.path.join(eb.CSRC, "eepacc_ab_build.hip"), "-o", obj,
+                                     '-DEEPACC_BUILD_FLAGS=""', "-Rpass-analysis=kernel-resource-usage"]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    assert os.path.getsize(obj) > 0
+    assert "k_ab_build" in r.stderr                                     # the kernel is in the object
+    m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)
+    print(re.findall(r"remark:\s+(.*?) \[-Rpass", r.stderr))
+    assert m and int(m.group(1)) == 0

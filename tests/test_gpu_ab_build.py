@@ -18,17 +18,12 @@ from ab_cert_cases import rollout
 from conftest import make_case, load_golden, golden_step_inputs, GOLDEN_AB_VARIANTS, GOLDEN_AB_ICEMAP
 from eepacc_mpc_casadi_matlab_amd._abi import OUT, AB_ROW_TYPES
 from eepacc_mpc_casadi_matlab_amd.scenarios import make_s1, make_s2
+from qp_build_helpers import INS, _cols, _engine, _np
 
 pytestmark = pytest.mark.gpu
 
-INS = ("s", "v", "a_prev", "t0", "s_tv", "v_tv", "a_tv_prev")
 ICE = dict(W_AB=np.array(GOLDEN_AB_ICEMAP["W_AB"]), fuel_map=GOLDEN_AB_ICEMAP["fuel_map"])
 MB20 = [0, 0, 1, 0, 1, 1, 0, 0, 0, 1, 0, 1, 0, 0, 1, 1, 1, 0, 0, 1]
-
-
-def _engine(OPT, V, max_batch=128):
-    from eepacc_mpc_casadi_matlab_amd.engine import Engine
-    return Engine(OPT, V, device=0, max_batch=max_batch)
 
 
 def _case(tree, N, **kw):
@@ -37,19 +32,11 @@ def _case(tree, N, **kw):
     return OPT, V, s_tv, v_tv
 
 
-def _cols(inps):
-    return {n: np.array([float(d[n]) for d in inps]) for n in INS}
-
-
 def _s1(tree, B, seed=1234):
     """Perturbed golden states (scenarios.make_s1), valid inputs at every horizon length."""
     _, _, s_tv, v_tv = make_case(tree, 20)
     s1 = make_s1(B, load_golden(f"{tree.lower()}_abmpc"), s_tv, v_tv, seed=seed)
     return {n: np.ascontiguousarray(s1[n], dtype=np.float64) for n in INS}
-
-
-def _np(q):
-    return [x.cpu().numpy() for x in q]
 
 
 def _against_oracle(OPT, V, cols, eng=None):

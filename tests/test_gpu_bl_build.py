@@ -21,24 +21,12 @@ from conftest import make_case, load_golden, golden_step_inputs
 from eepacc_mpc_casadi_matlab_amd._abi import OUT, BL_ROW_TYPES
 from eepacc_mpc_casadi_matlab_amd.scenarios import make_s1
 from eepacc_mpc_casadi_matlab_amd.settings import Settings, SetVehicleParameters, Settings_BL, Settings_TV, default_opt
+from qp_build_helpers import INS, _cols, _engine, _np
 from bl_qp_ref import _bl_case, GEOM24, QP_WEIGHTS, STATES, KEYS, ROUND_TRIP_STEPS, cost_bar
 
 pytestmark = pytest.mark.gpu
 
-INS = KEYS
-
-
-def _engine(OPT, V, max_batch=128):
-    from eepacc_mpc_casadi_matlab_amd.engine import Engine
-    return Engine(OPT, V, device=0, max_batch=max_batch)
-
-
-def _np(q):
-    return [x.cpu().numpy() for x in q]
-
-
-def _cols(inps):
-    return {n: np.array([float(d[n]) for d in inps]) for n in INS}
+assert INS == KEYS           # bl_qp_ref's states are keyed by the builder's inputs, in argument order
 
 
 def _states(tree, B, seed=1234):

@@ -21,19 +21,19 @@ import math
 import numpy as np
 import pytest
 
+import qp_build_helpers
 from conftest import make_case, load_golden, golden_step_inputs
 from eepacc_mpc_casadi_matlab_amd._abi import OUT, FB_ROW_TYPES, SettingsPOD, Vehicle, c_double_p, as_dptr
 from eepacc_mpc_casadi_matlab_amd.scenarios import make_s1, make_s2
+from qp_build_helpers import INS, _cols, _np
 
 pytestmark = pytest.mark.gpu
 
-INS = ("s", "v", "a_prev", "t0", "s_tv", "v_tv", "a_tv_prev")
 MB20 = [0, 0, 1, 0, 1, 1, 0, 0, 0, 1, 0, 1, 0, 0, 1, 1, 1, 0, 0, 1]          # that of test_gpu_ab_build.py
 
 
 def _engine(OPT, V, max_batch=8):
-    from eepacc_mpc_casadi_matlab_amd.engine import Engine
-    return Engine(OPT, V, device=0, max_batch=max_batch)
+    return qp_build_helpers._engine(OPT, V, max_batch)
 
 
 def _case(tree, N, **kw):
@@ -42,19 +42,11 @@ def _case(tree, N, **kw):
     return OPT, V, s_tv, v_tv
 
 
-def _cols(inps):
-    return {n: np.array([float(d[n]) for d in inps]) for n in INS}
-
-
 def _s1(tree, B, seed=1234):
     """Perturbed golden states (scenarios.make_s1), valid inputs at every horizon length."""
     _, _, s_tv, v_tv = make_case(tree, 20)
     s1 = make_s1(B, load_golden(f"{tree.lower()}_abmpc"), s_tv, v_tv, seed=seed)
     return {n: np.ascontiguousarray(s1[n], dtype=np.float64) for n in INS}
-
-
-def _np(q):
-    return [x.cpu().numpy() for x in q]
 
 
 def _fb_step(eng, c):
