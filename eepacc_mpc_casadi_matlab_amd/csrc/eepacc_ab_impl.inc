@@ -6,7 +6,8 @@
 // inverted every step) and EEPACC_IMPL_CLS (settings classes: every instance has the DevCfg of its class), so that the
 // default path carries no register or instruction cost for the variants.
 // The tables of the active-set method (the inverse He of the effective Hessian, the inverse Schur block P of the working
-// set) are maintained by eepacc_schur.h, which the FBMPC kernels share; it is included once, outside these namespaces.
+// set) are maintained by eepacc_schur.h, and the steps of a dual pass that do not depend on the row catalogue are in
+// eepacc_dual_step.h; the FBMPC kernels share both, and both are included once, outside these namespaces.
 namespace eepacc {
 namespace EEPACC_IMPL_NS {
 using namespace wv;
@@ -259,8 +260,6 @@ __device__ __forceinline__ double adjoint(const Lane& L, const double* ws, const
     return g;
 }
 
-enum Ev : int { EV_NONE = 0, EV_DROP, EV_COMPL, EV_DROPH, EV_CAP, EV_CAPIN };
-
 // The quadratic slack xi_h of stage k, once above its bound, is eliminated into the objective:
 // H_eff = H + q * sum_k n_k n_k'  (n_k: a-space normal of the headway-policy row).  He holds
 // H_eff^-1 for this wave; adding / removing one stage is a Sherman-Morrison rank-one update.
@@ -459,20 +458,8 @@ __device__ __forceinline__ double gradient_side(const Lane& L, const Cfg& c, Wav
     if (lane <= N) { M.ws[lane] = s; M.wv[lane] = v; M.wa[lane] = a0; }
     WSYNC();
     if (lane > 0 && lane < N && a1 != 0.0) atomicAdd(&M.wa[lane - 1], a1);
-    if (with_lam && lane < m) {
-        const int ki = M.w_k[lane];
-        const double l = M.lam[lane];
-        atomicAdd(&M.ws[ki], l * M.e_al[lane]);
-        atomicAdd(&M.wv[ki], l * M.e_be[lane]);
-        if (ki < N && M.e_ga[lane] != 0.0) atomicAdd(&M.wa[ki], l * M.e_ga[lane]);
-        if (ki > 0 && M.e_de[lane] != 0.0) atomicAdd(&M.wa[ki - 1], l * M.e_de[lane]);
-    }
-    if (lam_q != 0.0 && lane == 0) {
-        atomicAdd(&M.ws[kq], lam_q * qal);
-        atomicAdd(&M.wv[kq], lam_q * qbe);
-        if (kq < N && qga != 0.0) atomicAdd(&M.wa[kq], lam_q * qga);
-        if (kq > 0 && qde != 0.0) atomicAdd(&M.wa[kq - 1], lam_q * qde);
-    }
+    if (with_lam) scatter_rows(M, m, N, lane, M.lam, 1.0);
+    if (lam_q != 0.0 && lane == 0) scatter_row(M, kq, N, lam_q, qal, qbe, qga, qde);
     WSYNC();
     double g = adjoint<NS>(L, M.ws, M.wv, M.wa, M.ub);
     return (lane < N) ? g + L.g0 : 0.0;
@@ -485,27 +472,10 @@ __device__ __forceinline__ double direction_side(const Lane& L, WaveMem<MMAX, NS
     const int lane = L.lane, N = L.N;
     if (lane <= N) { M.ws[lane] = 0.0; M.wv[lane] = 0.0; M.wa[lane] = 0.0; }
     WSYNC();
-    if (lane < m) {
-        const int ki = M.w_k[lane];
-        const double l = -M.rv[lane];
-        atomicAdd(&M.ws[ki], l * M.e_al[lane]);
-        atomicAdd(&M.wv[ki], l * M.e_be[lane]);
-        if (ki < N && M.e_ga[lane] != 0.0) atomicAdd(&M.wa[ki], l * M.e_ga[lane]);
-        if (ki > 0 && M.e_de[lane] != 0.0) atomicAdd(&M.wa[ki - 1], l * M.e_de[lane]);
-    }
-    if (lane == 0) {
-        atomicAdd(&M.ws[kq], qal);
-        atomicAdd(&M.wv[kq], qbe);
-        if (kq < N && qga != 0.0) atomicAdd(&M.wa[kq], qga);
-        if (kq > 0 && qde != 0.0) atomicAdd(&M.wa[kq - 1], qde);
-    }
+    scatter_rows(M, m, N, lane, M.rv, -1.0);
+    if (lane == 0) scatter_row(M, kq, N, 1.0, qal, qbe, qga, qde);
     WSYNC();
     return adjoint<NS>(L, M.ws, M.wv, M.wa, M.ub);
-}
-
-template <int MMAX, int NS>
-__device__ __forceinline__ double rows_dot(const WaveMem<MMAX, NS>& M, int i, int N) {
-    return rows_dot_img(M, i, N, M.ub, M.sub, M.vub);
 }
 
 // primal point from the multipliers: a = -Hinv (g_eff + lam_q c_q + C' lam); also refreshes the
@@ -521,46 +491,20 @@ __device__ __forceinline__ void primal_from_multipliers(Lane& L, const Cfg& c, W
     WSYNC();
     L.a = -mb_expand(L, c, he_apply<NS>(Hs, M.yv, L.N, L.lane));
     hom_traj(L, L.a, L.sh, L.vh);
-    L.am1 = dpp_zero<0x138, 0xf>(L.a);
+    L.am1 = lane_prev(L.a);
     if (L.lane < L.N) M.av[L.lane] = L.a;
     if (L.lane <= L.N) { M.shv[L.lane] = L.sh; M.vhv[L.lane] = L.vh; }
     WSYNC();
 }
 
-// primal point + iterative refinement: the multipliers come out of the explicit inverse P, whose
-// accuracy degrades with cond(S) (many active rows, stiff ORIG weights); the residual of the
-// working-set equations  C a - D lam = d  is evaluated exactly from the scans and fed back
-// through P until it is at rounding level.  Stationarity holds by construction of a.
+// primal point + iterative refinement (refine_rounds, eepacc_dual_step.h); returns the relative residual of the
+// working-set rows before any correction
 template <int MMAX, int NS>
-// returns the relative residual of the working-set rows before any correction: a measure of how good
-// the inverse Schur block P still is
 __device__ __forceinline__ double refine_primal(Lane& L, const Cfg& c, WaveMem<MMAX, NS>& M, const double* Hs, int m,
                                                 double lam_q, int kq, double qal, double qbe, double qga, double qde,
                                                 double& grad_total, int max_rounds, double res_tol) {
-    primal_from_multipliers(L, c, M, Hs, m, lam_q, kq, qal, qbe, qga, qde, grad_total);
-    if (m == 0) return 0.0;
-    double rel0 = 0.0;
-    for (int round = 0; round < max_rounds; ++round) {
-        double res = 0.0, rel = 0.0;
-        if (L.lane < m) {
-            res = rows_dot_img(M, L.lane, L.N, M.av, M.shv, M.vhv) - M.e_d[L.lane];
-            rel = fabs(res) / (1.0 + fabs(M.e_d[L.lane]));
-            M.sv[L.lane] = res;
-        }
-        int dummy = L.lane;
-        wave_argmax(rel, dummy);
-        if (round == 0) rel0 = rel;
-        if (!(rel > res_tol)) break;
-        WSYNC();
-        if (L.lane < m) {
-            double acc = 0.0;
-            for (int j = 0; j < m; ++j) acc = fma(M.P[pidx(L.lane, j)], M.sv[j], acc);
-            M.lam[L.lane] += acc;
-        }
-        WSYNC();
-        primal_from_multipliers(L, c, M, Hs, m, lam_q, kq, qal, qbe, qga, qde, grad_total);
-    }
-    return rel0;
+    return refine_rounds(M, m, L.N, L.lane, max_rounds, res_tol,
+                         [&]() __attribute__((always_inline)) { primal_from_multipliers(L, c, M, Hs, m, lam_q, kq, qal, qbe, qga, qde, grad_total); });
 }
 
 // slack of linear group g at this lane for the current point
@@ -592,7 +536,7 @@ __device__ __forceinline__ int warm_repair(Lane& L, const Cfg& c, const WaveMem<
     double sumF = 0.0, sumS = 0.0, sumV = 0.0;
     double bestF = -1e300, bestS = -1e300, bestV = -1e300;     // largest multiplier per group
     int bF = -1, bS = -1, bV = -1;
-    double worst = tol; int fix = 0x7fffffff;
+    double worst = tol; int fix = EvCode::kNoEvent;
     int pos = L.base;
 #pragma unroll
     for (int t = 0; t < kNumRowTypes; ++t) {
@@ -603,13 +547,13 @@ __device__ __forceinline__ int warm_repair(Lane& L, const Cfg& c, const WaveMem<
         double l = M.lam[pos++];
         if (g2 == G_H) {
             if (-l > tol) {
-                if (!single) { set_code(L, t, 0); changed = 1; } else if (-l > worst) { worst = -l; fix = (EV_DROP << 16) | (lane << 5) | t; }
+                if (!single) { set_code(L, t, 0); changed = 1; } else if (-l > worst) { worst = -l; fix = EvCode::pack(EV_DROP, lane, t); }
             } else if (l - c.wH > tol) {
-                if (!single) { set_code(L, t, 3); changed = 1; } else if (l - c.wH > worst) { worst = l - c.wH; fix = (EV_COMPL << 16) | (lane << 5) | t; }
+                if (!single) { set_code(L, t, 3); changed = 1; } else if (l - c.wH > worst) { worst = l - c.wH; fix = EvCode::pack(EV_COMPL, lane, t); }
             }
         } else {
             if (-l > tol) {
-                if (!single) { set_code(L, t, 0); changed = 1; l = 0.0; } else if (-l > worst) { worst = -l; fix = (EV_DROP << 16) | (lane << 5) | t; }
+                if (!single) { set_code(L, t, 0); changed = 1; l = 0.0; } else if (-l > worst) { worst = -l; fix = EvCode::pack(EV_DROP, lane, t); }
             } else if (g2 == G_F) { if (l > bestF) { bestF = l; bF = t; } }
             else if (g2 == G_S) { if (l > bestS) { bestS = l; bS = t; } }
             else if (g2 == G_V) { if (l > bestV) { bestV = l; bV = t; } }
@@ -625,7 +569,7 @@ __device__ __forceinline__ int warm_repair(Lane& L, const Cfg& c, const WaveMem<
             double w = group_w(c, g2);
             double viol = sum - w;
             if (viol > tol * (1.0 + w)) {
-                if (single) { if (viol > worst) { worst = viol; fix = (EV_CAP << 16) | (lane << 5) | g2; } }
+                if (single) { if (viol > worst) { worst = viol; fix = EvCode::pack(EV_CAP, lane, g2); } }
                 else if (!changed && !capg) capg = g2;
             }
         }
@@ -636,10 +580,10 @@ __device__ __forceinline__ int warm_repair(Lane& L, const Cfg& c, const WaveMem<
 #ifdef EEPACC_BL_TRACE
         if (lane == 0 && (gridDim.x == 1 || g_trace_on)) printf("   repair: lmax %.3e worst %.3e fix(%d,%d,%d)\n", lmax, worst, fix >> 16, (fix >> 5) & 63, fix & 31);
 #endif
-        if (fix != 0x7fffffff) {
+        if (fix != EvCode::kNoEvent) {
             changed = 1;
-            const int ek = fix >> 16;
-            el = (fix >> 5) & 63; et = fix & 31;
+            const int ek = EvCode::kind(fix);
+            el = EvCode::lane(fix); et = EvCode::type(fix);
             if (ek == EV_DROP) {
                 const int pl = rows_below(L, et);
                 drop_pos = __builtin_amdgcn_readlane(L.base + pl, __builtin_amdgcn_readfirstlane(el));
@@ -958,12 +902,7 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const Cfg& c, WaveMem<MM
             if (!have_q) warm = false;
         }
         if (!have_q) {
-            // Anti-cycling: rounding noise of the order of (largest multiplier) x eps can flip rows in
-            // and out at the tightest tolerance (seen with the ORIG weights, w_f = 1e7); the tolerance
-            // is relaxed decade by decade if the iteration count shows that this is happening (never
-            // beyond 1e-8, scaled by 1+|b|).
-            const int relax_every = 3 * N + 30;
-            const double tolv = kTolViol * (st.iters < relax_every ? 1.0 : (st.iters < 2 * relax_every ? 10.0 : (st.iters < 3 * relax_every ? 100.0 : 1000.0)));
+            const double tolv = viol_tolerance(kTolViol, st.iters, N);      // at most 1000 kTolViol = 1e-8, scaled by 1 + |b|
             int bp = find_violation(L, c, tolv > tol_floor ? tolv : tol_floor, best);
             if constexpr (kBaseline) {
                 // Resolution of a degenerate LP vertex.  At a standstill every later stage's rows are dependent and the
@@ -1006,9 +945,7 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const Cfg& c, WaveMem<MM
         }
         if (++st.events > (kBaseline ? 10 : 40) * max_iter) { st.status = 2; break; }
         const int kq = q.kq;
-        double viol = q.al * M.shv[kq] + q.be * M.vhv[kq] - q.d;
-        if (kq < N) viol += q.ga * M.av[kq];
-        if (kq > 0) viol += q.de * M.av[kq - 1];
+        const double viol = row_value(q, kq, N, M.av, M.shv, M.vhv, q.d);
         // u = He c_q and its trajectories
         double cj = mb_reduce(L, c, normal_at(L, kq, q.al, q.be, q.ga, q.de, tauv[kq]));
         if (lane < NS) M.yv[lane] = cj;
@@ -1019,28 +956,15 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const Cfg& c, WaveMem<MM
         if (lane < N) M.ub[lane] = u;
         if (lane <= N) { M.sub[lane] = su; M.vub[lane] = vu; }
         WSYNC();
-        double cu = q.al * M.sub[kq] + q.be * M.vub[kq];
-        if (kq < N) cu += q.ga * M.ub[kq];
-        if (kq > 0) cu += q.de * M.ub[kq - 1];
+        const double cu = row_value(q, kq, N, M.ub, M.sub, M.vub, 0.0);
         double sr = 0.0;
-        if (m > 0) {
-            if (lane < m) M.sv[lane] = rows_dot(M, lane, N);
-            WSYNC();
-            double r = 0.0;
-            if (lane < m) {
-                for (int j = 0; j < m; ++j) r = fma(M.P[pidx(lane, j)], M.sv[j], r);
-                M.rv[lane] = r;
-                sr = M.sv[lane] * r;
-            }
-            WSYNC();
-            sr = wave_sum(sr);
-        }
+        if (m > 0) sr = step_rates(M, m, N, lane);
         const double zz = cu - sr;
         double t2 = (zz > 1e-8 * cu) ? viol / zz : kInf;
         if (viol <= 0.0) t2 = 0.0;
         // blocking events, evaluated per (lane, type); multipliers and their rates are read from the
         // working-set list in this lane's order
-        double t1 = kInf; int ev = 0x7fffffff;
+        double t1 = kInf; int ev = EvCode::kNoEvent;
         {
             // candidate step lengths num / den (den > 0) are compared cross-multiplied against the lane's best so far
             // (t1n / t1d): one division per lane at the end instead of one per candidate
@@ -1060,10 +984,10 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const Cfg& c, WaveMem<MM
                 const bool blocks = !(pf && l < 0.0);      // primal first: a negative multiplier cannot block the step
                 if (g2 == G_H) {
                     // rigid row of the quadratic slack: 0 <= lambda <= w
-                    if (r > 0.0) { if (blocks) EEPACC_CAND(fmax(l, 0.0), r, (EV_DROP << 16) | (lane << 5) | t); }
-                    else if (r < 0.0) EEPACC_CAND(fmax(c.wH - l, 0.0), -r, (EV_COMPL << 16) | (lane << 5) | t);
+                    if (r > 0.0) { if (blocks) EEPACC_CAND(fmax(l, 0.0), r, EvCode::pack(EV_DROP, lane, t)); }
+                    else if (r < 0.0) EEPACC_CAND(fmax(c.wH - l, 0.0), -r, EvCode::pack(EV_COMPL, lane, t));
                 } else {
-                    if (r > 0.0 && blocks) EEPACC_CAND(fmax(l, 0.0), r, (EV_DROP << 16) | (lane << 5) | t);
+                    if (r > 0.0 && blocks) EEPACC_CAND(fmax(l, 0.0), r, EvCode::pack(EV_DROP, lane, t));
                     if (g2 == G_F) { sumLF += l; sumRF += r; } else if (g2 == G_S) { sumLS += l; sumRS += r; } else if (g2 == G_V) { sumLV += l; sumRV += r; }
                 }
             }
@@ -1074,18 +998,18 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const Cfg& c, WaveMem<MM
                     double srr = g2 == G_F ? sumRF : (g2 == G_S ? sumRS : sumRV);
                     double rate = -srr, margin = group_w(c, g2) - sl;
                     if (lane == kq && q.gq == g2) { rate += 1.0; margin -= lam_q; }
-                    if (rate > 0.0) EEPACC_CAND(fmax(margin, 0.0), rate, (EV_CAP << 16) | (lane << 5) | g2);
+                    if (rate > 0.0) EEPACC_CAND(fmax(margin, 0.0), rate, EvCode::pack(EV_CAP, lane, g2));
                 }
             }
-            if (lane == kq && !q.is_bound && q.gq == G_H) EEPACC_CAND(fmax(c.wH - lam_q, 0.0), 1.0, (EV_CAPIN << 16) | (lane << 5));
+            if (lane == kq && !q.is_bound && q.gq == G_H) EEPACC_CAND(fmax(c.wH - lam_q, 0.0), 1.0, EvCode::pack(EV_CAPIN, lane, 0));
             if (lane == kq && q.is_bound && q.gq == G_H) {
                 // incoming slack bound of a penalised row: the row's own multiplier
                 // w + q*xi - mu must stay >= 0 while xi rises with the step
                 const double xi_now = L.lbH - viol, den = 1.0 - c.qH * zz;
-                if (den > 0.0) EEPACC_CAND(fmax(c.wH + c.qH * xi_now - lam_q, 0.0), den, (EV_DROPH << 16) | (lane << 5) | R_HWP);
+                if (den > 0.0) EEPACC_CAND(fmax(c.wH + c.qH * xi_now - lam_q, 0.0), den, EvCode::pack(EV_DROPH, lane, R_HWP));
             }
 #undef EEPACC_CAND
-            t1 = (ev == 0x7fffffff) ? kInf : t1n / t1d;
+            t1 = (ev == EvCode::kNoEvent) ? kInf : t1n / t1d;
             wave_argmin(t1, ev);
         }
         const double tstep = fmin(t1, t2);
@@ -1115,7 +1039,7 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const Cfg& c, WaveMem<MM
             }
             finished = true;
         } else {
-            const int ek = ev >> 16, el = (ev >> 5) & 63, et = ev & 31;
+            const int ek = EvCode::kind(ev), el = EvCode::lane(ev), et = EvCode::type(ev);
             if (ek == EV_DROP) {
                 const int pl = rows_below(L, et);
                 F.drop_pos = __builtin_amdgcn_readlane(L.base + pl, __builtin_amdgcn_readfirstlane(el));
@@ -1182,7 +1106,7 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const Cfg& c, WaveMem<MM
             double sz, vz;
             hom_traj(L, z, sz, vz);
             L.a = fma(-tstep, z, L.a); L.sh = fma(-tstep, sz, L.sh); L.vh = fma(-tstep, vz, L.vh);
-            L.am1 = dpp_zero<0x138, 0xf>(L.a);
+            L.am1 = lane_prev(L.a);
             if (lane < N) M.av[lane] = L.a;
             if (lane <= N) { M.shv[lane] = L.sh; M.vhv[lane] = L.vh; }
             const double lv = (lane < m) ? fma(-tstep, M.rv[lane], M.lam[lane]) : 0.0;

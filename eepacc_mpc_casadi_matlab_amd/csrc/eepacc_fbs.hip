@@ -31,6 +31,7 @@
 #include "eepacc_stage.h"
 #include "eepacc_units.h"
 #include "eepacc_schur.h"
+#include "eepacc_dual_step.h"
 #include "eepacc_fbs.h"
 #include "../../include/eepacc.h"
 
@@ -67,7 +68,6 @@ enum FRow : int {
     kNumF = 25
 };
 enum FGroup : int { GN = 0, GF = 1, GS = 2, GV = 3, GH = 4, GW = 5 };
-enum Ev : int { EV_NONE = 0, EV_DROP, EV_COMPL, EV_DROPH, EV_CAP, EV_CAPIN };
 
 struct RC {        // wave-uniform row constants
     double tau_min, c1, g_tqmin, g_tqmax, g_rtlo, g_rthi, Lmu;
@@ -502,20 +502,8 @@ __device__ __forceinline__ double gradient_side(const Lane& L, const RC& c, FMem
     if (lane <= N) { M.ws[lane] = s; M.wv[lane] = v; M.wa[lane] = a0; }
     WSYNC();
     if (lane > 0 && lane < N && a1 != 0.0) atomicAdd(&M.wa[lane - 1], a1);
-    if (vec && lane < m) {
-        const int ki = M.w_k[lane];
-        const double l = vec[lane];
-        atomicAdd(&M.ws[ki], l * M.e_al[lane]);
-        atomicAdd(&M.wv[ki], l * M.e_be[lane]);
-        if (ki < N && M.e_ga[lane] != 0.0) atomicAdd(&M.wa[ki], l * M.e_ga[lane]);
-        if (ki > 0 && M.e_de[lane] != 0.0) atomicAdd(&M.wa[ki - 1], l * M.e_de[lane]);
-    }
-    if (lam_q != 0.0 && lane == 0) {
-        atomicAdd(&M.ws[kq], lam_q * qal);
-        atomicAdd(&M.wv[kq], lam_q * qbe);
-        if (kq < N && qga != 0.0) atomicAdd(&M.wa[kq], lam_q * qga);
-        if (kq > 0 && qde != 0.0) atomicAdd(&M.wa[kq - 1], lam_q * qde);
-    }
+    if (vec) scatter_rows(M, m, N, lane, vec, 1.0);
+    if (lam_q != 0.0 && lane == 0) scatter_row(M, kq, N, lam_q, qal, qbe, qga, qde);
     WSYNC();
     const double g = adjoint<MMAX, NS>(L, M, M.ws, M.wv, M.wa, M.ub);
     return (lane < N) ? g + (base ? L.g0 : 0.0) : 0.0;
@@ -539,30 +527,8 @@ __device__ __forceinline__ void primal_from_multipliers(Lane& L, const RC& c, FM
 template <int MMAX, int NS>
 __device__ __forceinline__ double refine_primal(Lane& L, const RC& c, FMem<MMAX, NS>& M, const double* Hs, int m, const LG& lg,
                                                 double lam_q, const Incoming& q, double& grad_total, int max_rounds, double res_tol) {
-    primal_from_multipliers(L, c, M, Hs, m, lg, lam_q, q, grad_total);
-    if (m == 0) return 0.0;
-    double rel0 = 0.0;
-    for (int round = 0; round < max_rounds; ++round) {
-        double res = 0.0, rel = 0.0;
-        if (L.lane < m) {
-            res = rows_dot_img(M, L.lane, L.N, M.av, M.shv, M.vhv) - M.e_d[L.lane];
-            rel = fabs(res) / (1.0 + fabs(M.e_d[L.lane]));
-            M.sv[L.lane] = res;
-        }
-        int dummy = L.lane;
-        wave_argmax(rel, dummy);
-        if (round == 0) rel0 = rel;
-        if (!(rel > res_tol)) break;
-        WSYNC();
-        if (L.lane < m) {
-            double acc = 0.0;
-            for (int j = 0; j < m; ++j) acc = fma(M.P[pidx(L.lane, j)], M.sv[j], acc);
-            M.lam[L.lane] += acc;
-        }
-        WSYNC();
-        primal_from_multipliers(L, c, M, Hs, m, lg, lam_q, q, grad_total);
-    }
-    return rel0;
+    return refine_rounds(M, m, L.N, L.lane, max_rounds, res_tol,
+                         [&]() __attribute__((always_inline)) { primal_from_multipliers(L, c, M, Hs, m, lg, lam_q, q, grad_total); });
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -614,7 +580,7 @@ __device__ __forceinline__ int warm_repair(Lane& L, const RC& c, const FMem<MMAX
     LocalSums S{0, 0, 0, 0, 0, 0, 0, 0};
     double bestF = -1e300, bestF0 = -1e300, bestS = -1e300, bestV = -1e300, bestW = -1e300;
     int bF = -1, bF0 = -1, bS = -1, bV = -1, bW = -1;
-    double worst = tol; int fix = 0x7fffffff;
+    double worst = tol; int fix = EvCode::kNoEvent;
     int pos = L.base;
 #pragma unroll
     for (int t = 0; t < kNumF; ++t) {
@@ -623,13 +589,13 @@ __device__ __forceinline__ int warm_repair(Lane& L, const RC& c, const FMem<MMAX
         double l = M.lam[pos++];
         if (g2 == GH) {
             if (-l > tol) {
-                if (!single) { set_code(L, t, 0); changed = 1; } else if (-l > worst) { worst = -l; fix = (EV_DROP << 16) | (lane << 5) | t; }
+                if (!single) { set_code(L, t, 0); changed = 1; } else if (-l > worst) { worst = -l; fix = EvCode::pack(EV_DROP, lane, t); }
             } else if (l - c.wH > tol) {
-                if (!single) { set_code(L, t, 3); changed = 1; } else if (l - c.wH > worst) { worst = l - c.wH; fix = (EV_COMPL << 16) | (lane << 5) | t; }
+                if (!single) { set_code(L, t, 3); changed = 1; } else if (l - c.wH > worst) { worst = l - c.wH; fix = EvCode::pack(EV_COMPL, lane, t); }
             }
         } else {
             if (-l > tol) {
-                if (!single) { set_code(L, t, 0); changed = 1; l = 0.0; } else if (-l > worst) { worst = -l; fix = (EV_DROP << 16) | (lane << 5) | t; }
+                if (!single) { set_code(L, t, 0); changed = 1; l = 0.0; } else if (-l > worst) { worst = -l; fix = EvCode::pack(EV_DROP, lane, t); }
             }
             const double aw = (lane < N) ? row_aw(t, c) : 0.0;
             if (g2 == GF) { S.LF += l; if (l > bestF) { bestF = l; bF = t; } if (aw == 0.0 && l > bestF0) { bestF0 = l; bF0 = t; } }
@@ -649,7 +615,7 @@ __device__ __forceinline__ int warm_repair(Lane& L, const RC& c, const FMem<MMAX
             const double val = g2 == GF ? Mu.vF : (g2 == GS ? Mu.vS : (g2 == GV ? Mu.vV : Mu.vW));
             const double sc = g2 == GW ? 1.0 : (1.0 + group_w(c, g2));
             if (-val > tol * sc) {
-                if (single) { if (-val / sc > worst) { worst = -val / sc; fix = (EV_CAP << 16) | (lane << 5) | g2; } }
+                if (single) { if (-val / sc > worst) { worst = -val / sc; fix = EvCode::pack(EV_CAP, lane, g2); } }
                 else if (!changed && !capg) capg = g2;
             }
         }
@@ -657,10 +623,10 @@ __device__ __forceinline__ int warm_repair(Lane& L, const RC& c, const FMem<MMAX
     int el = -1, et = capg, plain_drop = 0;
     if (single) {
         wave_argmax(worst, fix);
-        if (fix != 0x7fffffff) {
+        if (fix != EvCode::kNoEvent) {
             changed = 1;
-            const int ek = fix >> 16;
-            el = (fix >> 5) & 63; et = fix & 31;
+            const int ek = EvCode::kind(fix);
+            el = EvCode::lane(fix); et = EvCode::type(fix);
             if (ek == EV_DROP) {
                 const int pl = __popcll(codes_eq1(L.code) & ((1ull << (2 * et)) - 1ull));
                 drop_pos = bcast_i(L.base + pl, el);
@@ -823,9 +789,7 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const RC& c, FMem<MMAX, 
             warm = false;
         }
         if (!have_q) {
-            const int relax_every = 3 * N + 30;
-            const double tolv = kTolViol * (st.iters < relax_every ? 1.0 : (st.iters < 2 * relax_every ? 10.0 : (st.iters < 3 * relax_every ? 100.0 : 1000.0)));
-            const int bp = find_violation<NS>(L, c, M.ba, tolv, best);
+            const int bp = find_violation<NS>(L, c, M.ba, viol_tolerance(kTolViol, st.iters, N), best);
             FT_TOC(6);
             if (bp < 0) break;
             if (++st.iters > max_iter) { st.status = 2; break; }
@@ -838,9 +802,7 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const RC& c, FMem<MMAX, 
         }
         if (++st.events > 4 * max_iter) { st.status = 2; break; }
         const int kq = q.kq;
-        double viol = q.al * M.shv[kq] + q.be * M.vhv[kq] - q.d;
-        if (kq < N) viol += q.ga * M.av[kq];
-        if (kq > 0) viol += q.de * M.av[kq - 1];
+        const double viol = row_value(q, kq, N, M.av, M.shv, M.vhv, q.d);
         // u = He c_q and its trajectories
         const double cj = normal_at(L, kq, q.al, q.be, q.ga, q.de, bcast(L.Pi, kq), bcast(L.Th, kq));
         if (lane < NS) M.ws[lane] = cj;
@@ -851,22 +813,9 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const RC& c, FMem<MMAX, 
         if (lane < N) M.ub[lane] = ud;
         if (lane <= N) { M.sub[lane] = su; M.vub[lane] = vu; }
         WSYNC();
-        double cu = q.al * M.sub[kq] + q.be * M.vub[kq];
-        if (kq < N) cu += q.ga * M.ub[kq];
-        if (kq > 0) cu += q.de * M.ub[kq - 1];
+        const double cu = row_value(q, kq, N, M.ub, M.sub, M.vub, 0.0);
         double sr = 0.0;
-        if (m > 0) {
-            if (lane < m) M.sv[lane] = rows_dot_img(M, lane, N, M.ub, M.sub, M.vub);
-            WSYNC();
-            double r = 0.0;
-            if (lane < m) {
-                for (int j = 0; j < m; ++j) r = fma(M.P[pidx(lane, j)], M.sv[j], r);
-                M.rv[lane] = r;
-                sr = M.sv[lane] * r;
-            }
-            WSYNC();
-            sr = wave_sum(sr);
-        }
+        if (m > 0) sr = step_rates(M, m, N, lane);
         const double zz = cu - sr;
         double t2 = (zz > 1e-8 * cu) ? viol / zz : kInf;
         if (viol <= 0.0) t2 = 0.0;
@@ -889,7 +838,7 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const RC& c, FMem<MMAX, 
             vrate = -vz;
         }
         // blocking events per (lane, type / local variable)
-        double t1 = kInf; int ev = 0x7fffffff;
+        double t1 = kInf; int ev = EvCode::kNoEvent;
         {
             // candidate step lengths num / den (den > 0) are compared cross-multiplied against the lane's best so far
             // (t1n / t1d): one division per lane at the end instead of one per candidate
@@ -905,10 +854,10 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const RC& c, FMem<MMAX, 
                 const double l = M.lam[pos], r = M.rv[pos];
                 ++pos;
                 if (g2 == GH) {
-                    if (r > 0.0) EEPACC_CAND(fmax(l, 0.0), r, (EV_DROP << 16) | (lane << 5) | t);
-                    else if (r < 0.0) EEPACC_CAND(fmax(c.wH - l, 0.0), -r, (EV_COMPL << 16) | (lane << 5) | t);
+                    if (r > 0.0) EEPACC_CAND(fmax(l, 0.0), r, EvCode::pack(EV_DROP, lane, t));
+                    else if (r < 0.0) EEPACC_CAND(fmax(c.wH - l, 0.0), -r, EvCode::pack(EV_COMPL, lane, t));
                 } else {
-                    if (r > 0.0) EEPACC_CAND(fmax(l, 0.0), r, (EV_DROP << 16) | (lane << 5) | t);
+                    if (r > 0.0) EEPACC_CAND(fmax(l, 0.0), r, EvCode::pack(EV_DROP, lane, t));
                     if (g2 == GF) { S.LF += l; S.RF -= r; } else if (g2 == GS) { S.LS += l; S.RS -= r; } else if (g2 == GV) { S.LV += l; S.RV -= r; }
                     if (lane < N) { const double aw = row_aw(t, c); S.LW += aw * l; S.RW -= aw * r; }
                 }
@@ -945,21 +894,21 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const RC& c, FMem<MMAX, 
                     const double val = g2 == GF ? Mu.vF : (g2 == GS ? Mu.vS : (g2 == GV ? Mu.vV : Mu.vW));
                     const double rate = g2 == GF ? Mu.rF : (g2 == GS ? Mu.rS : (g2 == GV ? Mu.rV : Mu.rW));
                     if (rate < 0.0) {
-                        EEPACC_CAND(fmax(val, 0.0), -rate, (EV_CAP << 16) | (lane << 5) | g2);
+                        EEPACC_CAND(fmax(val, 0.0), -rate, EvCode::pack(EV_CAP, lane, g2));
                     }
                 }
             }
             if (lane == kq && !q.is_bound && q.gq == GH) {
-                EEPACC_CAND(fmax(c.wH - lam_q, 0.0), 1.0, (EV_CAPIN << 16) | (lane << 5));
+                EEPACC_CAND(fmax(c.wH - lam_q, 0.0), 1.0, EvCode::pack(EV_CAPIN, lane, 0));
             }
             if (lane == kq && q.is_bound && q.gq == GH) {
                 const double xi_now = L.lbH - viol, den = 1.0 - c.qH * zz;
                 if (den > 0.0) {
-                    EEPACC_CAND(fmax(c.wH + c.qH * xi_now - lam_q, 0.0), den, (EV_DROPH << 16) | (lane << 5) | F_HWP);
+                    EEPACC_CAND(fmax(c.wH + c.qH * xi_now - lam_q, 0.0), den, EvCode::pack(EV_DROPH, lane, F_HWP));
                 }
             }
 #undef EEPACC_CAND
-            t1 = (ev == 0x7fffffff) ? kInf : t1n / t1d;
+            t1 = (ev == EvCode::kNoEvent) ? kInf : t1n / t1d;
             wave_argmin(t1, ev);
         }
         const double tstep = fmin(t1, t2);
@@ -992,7 +941,7 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const RC& c, FMem<MMAX, 
             }
             finished = true;
         } else {
-            const int ek = ev >> 16, el = (ev >> 5) & 63, et = ev & 31;
+            const int ek = EvCode::kind(ev), el = EvCode::lane(ev), et = EvCode::type(ev);
             if (ek == EV_DROP) {
                 const int pl = __popcll(codes_eq1(L.code) & ((1ull << (2 * et)) - 1ull));
                 F.drop_pos = bcast_i(L.base + pl, el);

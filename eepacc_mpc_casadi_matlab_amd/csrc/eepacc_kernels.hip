@@ -16,6 +16,7 @@
 #include "eepacc_stage.h"
 #include "eepacc_units.h"
 #include "eepacc_schur.h"
+#include "eepacc_dual_step.h"
 #include "eepacc_ab_cols.h"
 #include "eepacc_ab.h"
 #include "../../include/eepacc.h"

@@ -1,6 +1,7 @@
 // linalg_harness.hip -- test-only device harness for the shared headers of the active-set kernels:
-// eepacc_wave.h (DPP scans, wave sums, arg-max), eepacc_units.h (pidx, rc_table, shift_codes) and eepacc_schur.h
-// (products with He, its column update and inversion, the bordered update, downdate and inversion of P, multipliers).
+// eepacc_wave.h (DPP scans, wave sums, arg-max), eepacc_units.h (pidx, rc_table, shift_codes), eepacc_schur.h
+// (products with He, its column update and inversion, the bordered update, downdate and inversion of P, multipliers)
+// and eepacc_dual_step.h (scatter into the stage images, row value, step rates, refinement rounds, event codes, tolerance).
 //
 // One small kernel per primitive: operands are staged from global memory into LDS, the header function is called the way
 // the solvers call it, the result is copied back.  A block has 1..4 waves and every wave works on its own problem, so a
@@ -16,6 +17,7 @@
 #include "eepacc_wave.h"
 #include "eepacc_units.h"
 #include "eepacc_schur.h"
+#include "eepacc_dual_step.h"
 
 using namespace eepacc;
 using namespace eepacc::wv;
@@ -232,6 +234,82 @@ __global__ void k_multipliers(const double* P, const double* img, const double* 
     for (int e = lane; e < MMAX; e += 64) { lam[q * MMAX + e] = M.lam[e]; sv[q * MMAX + e] = M.sv[e]; }
 }
 
+// ---------------------------------------------------------------------------------------------- eepacc_dual_step.h
+// the fields the routines of eepacc_dual_step.h name, laid out like the solvers' per-wave structs; map: the affine map
+// lam -> (av, shv, vhv) of the harness's recompute (rows s0 | cs | v0 | cv | a0 | ca | cb, see D_REFINE)
+template <int MMAX, int NS>
+struct DualMem {
+    double P[MMAX * (MMAX + 1) / 2];
+    double av[NS], shv[NS + 1], vhv[NS + 1];
+    double ub[NS + 1], sub[NS + 1], vub[NS + 1];
+    double ws[NS + 1], wv[NS + 1], wa[NS + 1];
+    double e_al[MMAX], e_be[MMAX], e_ga[MMAX], e_de[MMAX], e_d[MMAX];
+    double lam[MMAX], sv[MMAX], rv[MMAX];
+    double map[7][NS + 1];
+    int w_k[MMAX];
+};
+
+enum { D_SCATTER_ROWS, D_SCATTER_ROW, D_ROW_VALUE, D_STEP_RATES, D_REFINE, D_NUM };
+enum { IP_M, IP_N, IP_KQ, IP_X, IP_NUM };            // ipar: m, N, kq, (scatter_rows: 0 vec = lam, 1 vec = rv; refine: max_rounds)
+enum { DP_SCALE, DP_AL, DP_BE, DP_GA, DP_DE, DP_D, DP_NUM };      // par: sign / scale / res_tol, then the row
+
+// mem [nprob] DualMem in and out, par [nprob][DP_NUM], ipar [nprob][IP_NUM]; od, oi [nprob][64]: every lane's return
+// value and (D_REFINE) the number of calls of recompute it saw.
+// D_REFINE: one row per stage, w_k[i] = i; recompute is  shv_k = s0_k + cs_k lam_k,  vhv_k = v0_k + cv_k lam_k,
+// av_k = a0_k + ca_k lam_k + cb_k lam_{k+1}  (lam_i = 0 for i >= m).
+template <int MMAX, int NS, int OP>
+__global__ void k_dual(DualMem<MMAX, NS>* mem, const double* par, const int* ipar, double* od, int* oi, int nprob) {
+    extern __shared__ double smem[];
+    using Mem = DualMem<MMAX, NS>;
+    static_assert(sizeof(Mem) % sizeof(int) == 0, "copied as ints");
+    constexpr int WORDS = sizeof(Mem) / sizeof(int);
+    const int lane = lane_id(), q = problem_id();
+    if (q >= nprob) return;
+    Mem& M = *reinterpret_cast<Mem*>(reinterpret_cast<unsigned char*>(smem) + sizeof(Mem) * (threadIdx.x >> 6));
+    for (int e = lane; e < WORDS; e += 64) reinterpret_cast<int*>(&M)[e] = reinterpret_cast<const int*>(mem + q)[e];
+    WSYNC();
+    const int m = ipar[q * IP_NUM + IP_M], N = ipar[q * IP_NUM + IP_N], kq = ipar[q * IP_NUM + IP_KQ], x = ipar[q * IP_NUM + IP_X];
+    const double* p = par + q * DP_NUM;
+    double r = 0.0;
+    int calls = 0;
+    if constexpr (OP == D_SCATTER_ROWS) {
+        scatter_rows(M, m, N, lane, x ? M.rv : M.lam, p[DP_SCALE]);
+    } else if constexpr (OP == D_SCATTER_ROW) {
+        if (lane == 0) scatter_row(M, kq, N, p[DP_SCALE], p[DP_AL], p[DP_BE], p[DP_GA], p[DP_DE]);
+    } else if constexpr (OP == D_ROW_VALUE) {
+        const Incoming row{kq, 0, 0, 0, false, p[DP_AL], p[DP_BE], p[DP_GA], p[DP_DE], p[DP_D]};
+        r = row_value(row, kq, N, M.av, M.shv, M.vhv, row.d);
+    } else if constexpr (OP == D_STEP_RATES) {
+        if (m > 0) r = step_rates(M, m, N, lane);       // as the solvers call it
+    } else {
+        r = refine_rounds(M, m, N, lane, x, p[DP_SCALE], [&] {
+            ++calls;
+            const double l0 = lane < m ? M.lam[lane] : 0.0, l1 = lane + 1 < m ? M.lam[lane + 1] : 0.0;
+            WSYNC();
+            if (lane <= N) { M.shv[lane] = M.map[0][lane] + M.map[1][lane] * l0; M.vhv[lane] = M.map[2][lane] + M.map[3][lane] * l0; }
+            if (lane < N) M.av[lane] = M.map[4][lane] + M.map[5][lane] * l0 + M.map[6][lane] * l1;
+            WSYNC();
+        });
+    }
+    WSYNC();
+    od[q * 64 + lane] = r;
+    oi[q * 64 + lane] = calls;
+    for (int e = lane; e < WORDS; e += 64) reinterpret_cast<int*>(mem + q)[e] = reinterpret_cast<const int*>(&M)[e];
+}
+
+// in [n][3]: EvCode::pack arguments (kind, lane, t), or viol_tolerance arguments (iters, N) with tol0 [n];
+// out [n][4] = the code and its three parts; tol [n]
+__global__ void k_event_code(const int* in, int* out, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int ev = EvCode::pack(in[3 * i], in[3 * i + 1], in[3 * i + 2]);
+    out[4 * i] = ev; out[4 * i + 1] = EvCode::kind(ev); out[4 * i + 2] = EvCode::lane(ev); out[4 * i + 3] = EvCode::type(ev);
+}
+__global__ void k_viol_tolerance(const double* tol0, const int* in, double* tol, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) tol[i] = viol_tolerance(tol0[i], in[3 * i], in[3 * i + 1]);
+}
+
 // ---------------------------------------------------------------------------------------------- host side
 #define CK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return 1000 + (int)e_; } while (0)
 
@@ -381,6 +459,42 @@ int run_multipliers(const double* P, const double* img, const double* rows, cons
     return 0;
 }
 
+template <int MMAX, int NS, int OP>
+int run_dual(void* mem, const double* par, const int* ipar, double* od, int* oi, int nprob, int wpb) {
+    using Mem = DualMem<MMAX, NS>;
+    const Mem* h = static_cast<const Mem*>(mem);
+    for (int q = 0; q < nprob; ++q) {                 // every index the routines use stays inside the arrays
+        const int m = ipar[q * IP_NUM + IP_M], N = ipar[q * IP_NUM + IP_N], kq = ipar[q * IP_NUM + IP_KQ], x = ipar[q * IP_NUM + IP_X];
+        if (m < 0 || m > schur_capacity<MMAX>() || N < 1 || N > NS || kq < 0 || kq > N) return 1;
+        for (int i = 0; i < m; ++i) if (h[q].w_k[i] < 0 || h[q].w_k[i] > N) return 1;
+        if (OP == D_SCATTER_ROWS && x != 0 && x != 1) return 1;
+        if (OP == D_REFINE) {
+            if (x < 0 || x > 16 || m > N + 1) return 1;
+            for (int i = 0; i < m; ++i) if (h[q].w_k[i] != i) return 1;
+        }
+    }
+    Dev dM(mem, sizeof(Mem) * nprob), dp(par, sizeof(double) * DP_NUM * nprob), di(ipar, sizeof(int) * IP_NUM * nprob);
+    Dev dod(nullptr, sizeof(double) * 64 * nprob), doi(nullptr, sizeof(int) * 64 * nprob);
+    CK(dM.err); CK(dp.err); CK(di.err); CK(dod.err); CK(doi.err);
+    const size_t smem = sizeof(Mem) * wpb;
+    CK(allow_smem(k_dual<MMAX, NS, OP>, smem));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dual<MMAX, NS, OP>), dim3(grid_of(nprob, wpb)), dim3(64 * wpb), smem, 0,
+                       dM.as<Mem>(), dp.as<double>(), di.as<int>(), dod.as<double>(), doi.as<int>(), nprob);
+    if (int rc = finish()) return rc;
+    CK(dM.get(mem)); CK(dod.get(od)); CK(doi.get(oi));
+    return 0;
+}
+
+template <int MMAX, int NS>
+int run_dual_op(int op, void* mem, const double* par, const int* ipar, double* od, int* oi, int nprob, int wpb) {
+    if (op == D_SCATTER_ROWS) return run_dual<MMAX, NS, D_SCATTER_ROWS>(mem, par, ipar, od, oi, nprob, wpb);
+    if (op == D_SCATTER_ROW) return run_dual<MMAX, NS, D_SCATTER_ROW>(mem, par, ipar, od, oi, nprob, wpb);
+    if (op == D_ROW_VALUE) return run_dual<MMAX, NS, D_ROW_VALUE>(mem, par, ipar, od, oi, nprob, wpb);
+    if (op == D_STEP_RATES) return run_dual<MMAX, NS, D_STEP_RATES>(mem, par, ipar, od, oi, nprob, wpb);
+    if (op == D_REFINE) return run_dual<MMAX, NS, D_REFINE>(mem, par, ipar, od, oi, nprob, wpb);
+    return 1;
+}
+
 }  // namespace
 
 extern "C" {
@@ -488,6 +602,35 @@ int lh_multipliers(int mmax, int ns, const double* P, const double* img, const d
     if (mmax == 34 && ns == 32) return run_multipliers<34, 32>(P, img, rows, w_k, m, N, lam, sv, nprob, wpb);
     if (mmax == 66 && ns == 64) return run_multipliers<66, 64>(P, img, rows, w_k, m, N, lam, sv, nprob, wpb);
     return 1;
+}
+
+// sizeof(DualMem<mmax, ns>): the caller's record layout must agree
+int lh_dual_mem_size(int mmax, int ns) {
+    if (mmax == 32 && ns == 32) return (int)sizeof(DualMem<32, 32>);
+    if (mmax == 34 && ns == 32) return (int)sizeof(DualMem<34, 32>);
+    if (mmax == 66 && ns == 64) return (int)sizeof(DualMem<66, 64>);
+    return -1;
+}
+
+// op: 0 scatter_rows, 1 scatter_row (lane 0), 2 row_value, 3 step_rates, 4 refine_rounds; layouts as at k_dual
+int lh_dual(int op, int mmax, int ns, void* mem, const double* par, const int* ipar, double* od, int* oi, int nprob, int wpb) {
+    if (bad_shape(nprob, wpb)) return 1;
+    if (mmax == 32 && ns == 32) return run_dual_op<32, 32>(op, mem, par, ipar, od, oi, nprob, wpb);
+    if (mmax == 34 && ns == 32) return run_dual_op<34, 32>(op, mem, par, ipar, od, oi, nprob, wpb);
+    if (mmax == 66 && ns == 64) return run_dual_op<66, 64>(op, mem, par, ipar, od, oi, nprob, wpb);
+    return 1;
+}
+
+// in [n][3], tol0 [n] -> code [n][4] (EvCode::pack of the three and its parts) and tol [n] (viol_tolerance(tol0, in0, in1))
+int lh_step_scalars(const int* in, const double* tol0, int* code, double* tol, int n) {
+    if (n < 1 || n > 4096) return 1;
+    Dev di(in, sizeof(int) * 3 * n), dt0(tol0, sizeof(double) * n), dc(nullptr, sizeof(int) * 4 * n), dt(nullptr, sizeof(double) * n);
+    CK(di.err); CK(dt0.err); CK(dc.err); CK(dt.err);
+    hipLaunchKernelGGL(k_event_code, dim3((n + 63) / 64), dim3(64), 0, 0, di.as<int>(), dc.as<int>(), n);
+    hipLaunchKernelGGL(k_viol_tolerance, dim3((n + 63) / 64), dim3(64), 0, 0, dt0.as<double>(), di.as<int>(), dt.as<double>(), n);
+    if (int rc = finish()) return rc;
+    CK(dc.get(code)); CK(dt.get(tol));
+    return 0;
 }
 
 // rows the solvers accept in a working set of capacity mmax (their guard in rebuild_and_factor)

@@ -1,4 +1,5 @@
-"""The shared wave and working-set linear algebra (csrc/eepacc_wave.h, eepacc_units.h, eepacc_schur.h) called directly
+"""The shared wave and working-set linear algebra and the shared steps of a dual pass (csrc/eepacc_wave.h, eepacc_units.h,
+eepacc_schur.h, eepacc_dual_step.h) called directly
 on the GPU through tests/kernels/linalg_harness.hip and compared with plain numpy / mpmath references.
 
 The closed-loop tests cannot see an error in these functions: solve_qp falls back to a full schur_invert when an updated
@@ -618,6 +619,154 @@ def test_capacity_above_64_rows_is_refused(H):
         assert m > H.schur_capacity(66)
         with pytest.raises(lh.HarnessError):
             H.schur(lh.S_INVERT, 66, [tril_pack(matrix("spd", 64), 66)], [m])
+
+
+# ---------------------------------------------------------------------------------------------- eepacc_dual_step.h
+# Not covered: the candidate bookkeeping of the ratio test (EEPACC_CAND, t1n / t1d, the final division and wave_argmin).  It
+# stays written out, twice, in the two solve_qp (shared, it changed the register spills of every solver kernel:
+# profiles/dual_step_codegen.txt), so there is no routine to call and only the event-code format is tested here.
+# step_rates is called under `if (m > 0)`, as the solvers call it.
+# One problem per wave, 1..4 waves per block; the float64 restatements (linalg_harness.py, checked against dense algebra in
+# test_linalg_harness_cpu.py) are written in the kernel's order.  Integer-valued data make every sum exact in any order.
+WPBS = (1, 2, 3, 4)
+
+
+def same_bits(got, want, msg):
+    np.testing.assert_array_equal(got, want, err_msg=msg)
+    np.testing.assert_array_equal(bits(got), bits(want), err_msg=msg)       # NaN poison and the sign of a zero too
+
+
+@pytest.mark.parametrize("mmax,ns", lh.DUAL_SIZES)
+def test_scatter_rows_exact(H, mmax, ns):
+    M, cases = lh.scatter_rows_cases(H.dual_mem, mmax, ns)
+    want = [lh.scatter_rows_np(r, m, N, r["rv" if x else "lam"], sign) for r, (N, m, x, sign, _) in zip(M, cases)]
+    for wpb in WPBS:
+        out, _, _ = H.dual(lh.D_SCATTER_ROWS, mmax, ns, M, [c[1] for c in cases], [c[0] for c in cases],
+                           x=[c[2] for c in cases], scale=[c[3] for c in cases], wpb=wpb)
+        for q, c in enumerate(cases):
+            for name, w in zip(("ws", "wv", "wa"), want[q]):
+                same_bits(out[name][q], w, "%s case %s wpb %d" % (name, c, wpb))
+            if c[1] == 0:
+                for name in ("ws", "wv", "wa"):
+                    same_bits(out[name][q], M[name][q], "untouched %s" % name)
+
+
+@pytest.mark.parametrize("mmax,ns", lh.DUAL_SIZES)
+def test_scatter_row_exact(H, mmax, ns):
+    M, cases = lh.scatter_row_cases(H.dual_mem, mmax, ns)
+    want = [lh.scatter_row_np(r, kq, N, scale, *row[:4]) for r, (N, kq, scale, row) in zip(M, cases)]
+    for wpb in WPBS:
+        out, _, _ = H.dual(lh.D_SCATTER_ROW, mmax, ns, M, 0, [c[0] for c in cases], kq=[c[1] for c in cases],
+                           scale=[c[2] for c in cases], row=[c[3] for c in cases], wpb=wpb)
+        for q, c in enumerate(cases):
+            for name, w in zip(("ws", "wv", "wa"), want[q]):
+                same_bits(out[name][q], w, "%s case %s wpb %d" % (name, c, wpb))
+
+
+@pytest.mark.parametrize("mmax,ns", lh.DUAL_SIZES)
+def test_row_value_exact(H, mmax, ns):
+    M, cases = lh.row_value_cases(H.dual_mem, mmax, ns)
+    want = np.array([lh.row_value_np(row, kq, N, r["av"], r["shv"], r["vhv"]) for r, (N, kq, row) in zip(M, cases)])
+    for wpb in WPBS:
+        _, got, _ = H.dual(lh.D_ROW_VALUE, mmax, ns, M, 0, [c[0] for c in cases], kq=[c[1] for c in cases],
+                           row=[c[2] for c in cases], wpb=wpb)
+        np.testing.assert_array_equal(got, np.repeat(want[:, None], 64, 1))
+
+
+@pytest.mark.parametrize("mmax,ns", lh.DUAL_SIZES)
+def test_step_rates_exact(H, mmax, ns):
+    M, cases = lh.step_rates_int_cases(H.dual_mem, mmax, ns)
+    want = [lh.step_rates_np(r, m, N) for r, (N, m) in zip(M, cases)]
+    for wpb in WPBS:
+        out, sr, _ = H.dual(lh.D_STEP_RATES, mmax, ns, M, [c[1] for c in cases], [c[0] for c in cases], wpb=wpb)
+        for q, (N, m) in enumerate(cases):
+            sv, rv, s = want[q]
+            np.testing.assert_array_equal(sr[q], np.full(64, s), err_msg=str((N, m)))
+            np.testing.assert_array_equal(out["sv"][q, :m], sv)
+            np.testing.assert_array_equal(out["rv"][q, :m], rv)
+            assert np.isnan(out["sv"][q, m:]).all() and np.isnan(out["rv"][q, m:]).all()      # m = 0: both stay poisoned
+            if m == 0:
+                assert (bits(sr[q]) == 0).all()
+
+
+@pytest.mark.parametrize("mmax,ns,m", ((32, 32, 1), (34, 32, 34), (66, 64, 64)))
+def test_step_rates_float(H, mmax, ns, m):
+    """rv = P sv and sr = sv' rv on random data against mpmath, by the rule of the module docstring"""
+    N = ns
+    mp = mpmath.mpf
+    M = H.dual_mem(mmax, ns, len(FAMILIES))
+    for r, fam in zip(M, FAMILIES):
+        rng = np.random.default_rng(90 + m)
+        r["P"][:] = tril_pack(ref_inverse(fam, m).astype(float), mmax)
+        r["ub"][:], r["sub"][:], r["vub"][:] = rng.standard_normal((3, ns + 1)) * 10.0 ** rng.integers(-2, 3, (3, ns + 1))
+        for name in ("e_al", "e_be", "e_ga", "e_de"):
+            r[name][:m] = rng.standard_normal(m) * 10.0 ** rng.integers(-2, 3, m)
+        r["w_k"][:m] = rng.integers(0, N + 1, m)
+        r["w_k"][0], r["w_k"][m - 1] = 0, N
+    out, sr, _ = H.dual(lh.D_STEP_RATES, mmax, ns, M, m, N)
+    for q, fam in enumerate(FAMILIES):
+        r = M[q]
+        sv = []
+        for i in range(m):
+            k = int(r["w_k"][i])
+            x = mp(r["e_al"][i]) * mp(r["sub"][k]) + mp(r["e_be"][i]) * mp(r["vub"][k])
+            x += mp(r["e_ga"][i]) * mp(r["ub"][k]) if k < N else 0
+            x += mp(r["e_de"][i]) * mp(r["ub"][k - 1]) if k > 0 else 0
+            sv.append(x)
+        Po = to_obj(unpack_full(r["P"], m))
+        rv = [sum(Po[i, j] * sv[j] for j in range(m)) for i in range(m)]
+        s = sum(a * b for a, b in zip(sv, rv))
+        sv_c, rv_c, s_c = lh.step_rates_np(r, m, N)
+        check_against_reference("step_rates.rv", "MMAX %d %s m %d" % (mmax, fam, m), out["rv"][q, :m][None, :], rv_c[None, :],
+                                np.array([rv], dtype=object))
+        check_against_reference("step_rates.sr", "MMAX %d %s m %d" % (mmax, fam, m), sr[q][None, :1], np.array([[s_c]]),
+                                np.array([[s]], dtype=object))
+        assert (bits(sr[q]) == bits(sr[q])[0]).all()
+
+
+def unpack_full(P, m):
+    return tril_unpack(P, m)
+
+
+@pytest.mark.parametrize("mmax,ns", lh.DUAL_SIZES)
+def test_refine_rounds(H, mmax, ns):
+    M, cases = lh.refine_cases(H.dual_mem, mmax, ns)
+    for wpb in WPBS:
+        out, rel0, calls = H.dual(lh.D_REFINE, mmax, ns, M, [c[1] for c in cases], [c[0] for c in cases],
+                                  x=[c[3] for c in cases], scale=[c[4] for c in cases], wpb=wpb)
+        for q, (N, m, kind, mr, tol) in enumerate(cases):
+            msg = "MMAX %d case %s wpb %d" % (mmax, cases[q], wpb)
+            r = M[q].copy()
+            rel0_np, calls_np = lh.refine_rounds_np(r, m, N, mr, tol)
+            assert (calls[q] == calls_np).all(), msg
+            assert (bits(rel0[q]) == bits(rel0[q])[0]).all(), msg
+            after = out[q].copy()
+            res = lh.rows_dot_np(after, m, N, after["av"], after["shv"], after["vhv"]) - after["e_d"][:m]
+            rel_after = float(np.max(np.abs(res) / (1.0 + np.abs(after["e_d"][:m]))))
+            if kind == "exact":
+                assert calls_np == 1 and (rel0[q] == 0.0).all(), msg
+                same_bits(out["lam"][q], M["lam"][q], msg)                     # no correction
+            elif kind == "one_round":
+                assert calls_np == 2 and rel_after <= tol < rel0[q][0], msg
+            elif kind == "no_rounds":
+                assert calls_np == 1 and (rel0[q] == 0.0).all(), msg
+                same_bits(out["lam"][q], M["lam"][q], msg)
+            else:
+                assert calls_np == 1 + mr and rel_after > tol, msg
+            # rel0: a maximum of |four-term sums| / (1 + |d|); each sum rounds within 6 eps of its terms' magnitudes
+            T = np.abs(M["e_d"][q][:m]) + 4 * 150.0 * 1.5 * 3.0
+            assert abs(rel0[q][0] - rel0_np) <= 6 * EPS * float(np.max(T / (1.0 + np.abs(M["e_d"][q][:m])))), msg
+
+
+def test_event_codes_and_tolerance_exact(H):
+    packs, tols = lh.pack_cases(), lh.tolerance_cases()
+    code, _ = H.step_scalars(packs, np.zeros(len(packs)))
+    for (kind, lane, t), got in zip(packs, code):
+        assert tuple(got) == (lh.pack_np(kind, lane, t), kind, lane, t)
+    _, tol = H.step_scalars(tols, np.full(len(tols), 1e-11))
+    want = np.array([lh.viol_tolerance_np(1e-11, it, N) for it, N, _ in tols])
+    np.testing.assert_array_equal(bits(tol), bits(want))
+    assert sorted(set(want)) == [1e-11, 1e-11 * 10.0, 1e-11 * 100.0, 1e-11 * 1000.0]
 
 
 def test_print_ratios():
