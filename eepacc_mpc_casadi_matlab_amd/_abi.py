@@ -43,6 +43,14 @@ AB_BUILD_ARGTYPES = {
     "eepacc_ab_build_qp": [C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p] * 5 + [C.c_void_p],
 }
 
+# the entry points that take the horizon guesses s_est, v_est, s_tv_est (each may be None) after the seven step inputs, and
+# the closed loop that reads the lead's guess from the lead trace (B, n_steps, n_lead)
+AB_EST_ARGTYPES = {
+    "eepacc_ab_step_est": [C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p] * 3 + [C.c_void_p] * 4 + [C.c_void_p],
+    "eepacc_ab_build_qp_est": [C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p] * 3 + [C.c_void_p] * 5 + [C.c_void_p],
+    "eepacc_run_abmpc_preview": [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_void_p] * 2 + [C.c_void_p],
+}
+
 # enum EEPACC_FB_ROW_*: the row types of eepacc_fb_qp_rows, ascending in the order of the rows within a stage
 FB_ROW_TYPES = ["s", "v", "fm", "fb", "xi_v", "xi_h", "xi_s", "xi_f", "blocked_fm", "blocked_fb", "tm_min", "tm_max",
                 "axle_min", "axle_max", "fric_max", "fric_min", "a_max", "a_min", "j_max", "j_min",

@@ -10,7 +10,12 @@
 namespace eepacc {
 
 // One instantiation of eepacc_ab_impl.inc each; EEPACC_AB_VARIANTS (eepacc_kernels.hip) gives namespace and switches.
-enum class AbVariant { Plain, MoveBlocking, Baseline, Ice, IceMoveBlocking, TargetVehicle, Classes };
+enum class AbVariant { Plain, MoveBlocking, Baseline, Ice, IceMoveBlocking, TargetVehicle, Classes, Est };
+
+// The further arguments of the est kernels.  No handle has AbVariant::Est: eepacc_ab_step_est and eepacc_run_abmpc_preview run
+// a handle of AbVariant::Plain through those kernels, on the handle's own state.
+struct AbSupplied { const double *s_est, *v_est, *s_tv_est; };            // device arrays [N+1][B]; s_est and v_est both or neither
+struct AbPreview { const int32_t* idx; const double* frac; int n_lead; };   // device tables [N] (preview_tables, eepacc_cfg.h)
 
 // kernel variant of a handle: the baseline controllers (bl_mode) come before the ICE-map fuel term and move blocking.
 // AbVariant::Classes cannot be told from a DevCfg: a handle of eepacc_create_classes carries that choice itself.
@@ -27,15 +32,16 @@ int pick_chunk_steps(int n_steps, int B, int resident_waves);
 // s_tv, v_tv, a_tv_prev: null for AbVariant::TargetVehicle, whose kernels read no lead inputs.
 // AbVariant::Classes: dC is the class array DevCfg[n_classes] and class_of the device map [B] of the launch; every other
 // variant reads dC[0] alone and takes class_of = null (launch_postprocess: null selects the one-config kernel).
+// sup / pv: not null launches the est kernels (variant must be AbVariant::Plain) with these further arguments.
 hipError_t launch_ab_step(const DevCfg* dC, const int32_t* class_of, int N, AbVariant variant, int B, const double* s, const double* v,
                           const double* a_prev, const double* t0, const double* s_tv, const double* v_tv,
                           const double* a_tv_prev, unsigned long long* codes, double* out, double* s_pred, double* v_pred,
-                          int32_t* status, int32_t* iters, hipStream_t stream);
+                          int32_t* status, int32_t* iters, hipStream_t stream, const AbSupplied* sup = nullptr);
 hipError_t launch_run_abmpc(const DevCfg* dC, const int32_t* class_of, int N, AbVariant variant, int B, int k_start, int n_steps, const double* s0,
                             const double* v0, const double* a_m1, const double* s_tv, const double* v_tv,
                             double* carry, unsigned long long* codes, double* traj,
                             int32_t* status, int32_t* iters_total, int* work_counter, int* done, int* err_word, int num_cus,
-                            hipStream_t stream);
+                            hipStream_t stream, const AbPreview* pv = nullptr);
 hipError_t launch_postprocess(const DevCfg* dC, const int32_t* class_of, int B, int n_steps, const double* traj, double* rpm, double* Tm,
                               double* P, double* E, hipStream_t stream);
 

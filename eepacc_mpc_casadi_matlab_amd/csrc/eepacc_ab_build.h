@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "eepacc_device.h"
+#include "eepacc_ab.h"
 #include "../../include/eepacc.h"
 
 namespace eepacc {
@@ -25,6 +26,13 @@ inline int ab_qp_num_rows(const DevCfg& C) {
 // B workgroups of 256 threads; every entry of H [B][nV*nV], g [B][nV], A [B][nV][nC], lba, uba [B][nC] is written.
 hipError_t launch_ab_build(const DevCfg* cfg, int N, int nC, int B, const double* s, const double* v, const double* a_prev,
                            const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
-                           double* H, double* g, double* A, double* lba, double* uba, hipStream_t stream);
+                           double* H, double* g, double* A, double* lba, double* uba, hipStream_t stream,
+                           const AbSupplied* sup = nullptr);      // sup: supplied horizon guesses (eepacc_ab_build_qp_est)
+
+// the same on supplied guesses (eepacc_ab_build_est.hip); launch_ab_build goes there when sup is given
+hipError_t launch_ab_build_est(const DevCfg* cfg, int N, int nC, int B, const double* s, const double* v, const double* a_prev,
+                               const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                               double* H, double* g, double* A, double* lba, double* uba, hipStream_t stream,
+                               const AbSupplied& sup);
 
 }  // namespace eepacc

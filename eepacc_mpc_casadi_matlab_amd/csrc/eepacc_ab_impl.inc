@@ -1,9 +1,10 @@
 // eepacc_ab_impl.inc -- device code of the ABMPC kernels.  Included by eepacc_kernels.hip once per entry of its
-// EEPACC_AB_VARIANTS list, each time into its own namespace EEPACC_IMPL_NS with the five switches EEPACC_IMPL_MB (move
+// EEPACC_AB_VARIANTS list, each time into its own namespace EEPACC_IMPL_NS with the six switches EEPACC_IMPL_MB (move
 // blocking compiled out / in), EEPACC_IMPL_BL (the baseline controller's row grouping, CreateQP_BL.m: one slack for all
 // soft rows), EEPACC_IMPL_TV (with _BL: the target-vehicle MPC, CreateQP_TV.m: the baseline QP without its
 // vehicle-following rows and without lead inputs), EEPACC_IMPL_ICE (the ICE-map fuel term, whose Hessian is built and
-// inverted every step) and EEPACC_IMPL_CLS (settings classes: every instance has the DevCfg of its class), so that the
+// inverted every step), EEPACC_IMPL_CLS (settings classes: every instance has the DevCfg of its class) and EEPACC_IMPL_EST
+// (horizon guesses from the caller instead of the estimators: eepacc_ab_step_est, eepacc_run_abmpc_preview), so that the
 // default path carries no register or instruction cost for the variants.
 // The tables of the active-set method (the inverse He of the effective Hessian, the inverse Schur block P of the working
 // set) are maintained by eepacc_schur.h, and the steps of a dual pass that do not depend on the row catalogue are in
@@ -19,6 +20,8 @@ constexpr bool kTargetVeh = EEPACC_IMPL_TV;     // RunOpt_TVMPC (CreateQP_TV.m):
 static_assert(!kTargetVeh || kBaseline, "the target-vehicle MPC is a variant of the baseline controller");
 constexpr bool kClasses = EEPACC_IMPL_CLS;  // a handle of eepacc_create_classes: the kernels' Cp is its array DevCfg[n_classes]
 static_assert(!kClasses || !(kMoveBlocking || kBaseline || kIce), "settings classes are built for the plain ABMPC kernels only");
+constexpr bool kEst = EEPACC_IMPL_EST;      // the kernels take horizon guesses as further arguments (DESIGN.md section 3.4f)
+static_assert(!kEst || !(kMoveBlocking || kBaseline || kIce || kClasses), "supplied horizon guesses are built for the plain ABMPC kernels only");
 
 
 #undef PTIC
@@ -1136,6 +1139,10 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const Cfg& c, WaveMem<MM
 
 struct StepIn { double s, v, a_prev, t0, s_tv, v_tv, a_tv_prev; };
 
+// est: what the caller supplies of the horizon guesses of this lane's stage, in place of the estimators' (ego: s_est and
+// v_est, lead: stv_est).  An argument of ab_step in that variant alone.
+struct EstIn { bool ego, lead; double s_est, v_est, stv_est; };
+
 // ABO/RunOpt_ABMPC.m:287-324
 __device__ void force_allocation(const DevCfg& C, double s_meas, double v_meas, double a_qp,
                                  double& Fm, double& Fb, double& a_real) {
@@ -1253,10 +1260,11 @@ __device__ __forceinline__ int ice_build_invert_packed(const DevCfg& C, const Cf
 
 // One ABMPC step for the wave's instance (ABO/RunOpt_ABMPC.m:193-329).  `code` carries the
 // working set between steps (already shifted by the caller).
-template <int MMAX, int NS>
+template <int MMAX, int NS, class... Est>
 __device__ __forceinline__ void ab_step(const DevCfg& C, WaveMem<MMAX, NS>& M, double* Hs, const StepIn& in,
                         unsigned long long& code, StepOut& so, double& s_pred, double& v_pred,
-                        const double* predp, bool pred_in_lds, double* Hb = nullptr) {
+                        const double* predp, bool pred_in_lds, double* Hb, Est... est) {
+    static_assert(sizeof...(Est) == (kEst ? 1 : 0), "supplied guesses are an argument of the est kernels, and of them alone");
     Lane L;
 #ifdef EEPACC_AB_TIMING
     for (int i = 0; i < 24; ++i) L.prof[i] = 0;
@@ -1291,6 +1299,12 @@ __device__ __forceinline__ void ab_step(const DevCfg& C, WaveMem<MMAX, NS>& M, d
     // (target-vehicle MPC: no lead vehicle, RunOpt_TVMPC.m:157 estimates its own trajectory only)
     if constexpr (kTargetVeh) { stv_est = 0.0; vtv_est = 0.0; }
     else estimate_traj(C, C.TVestSetting, C.tConstACC_tar, in.s_tv, in.v_tv, in.a_tv_prev, lane, stv_est, vtv_est);
+    if constexpr (kEst) {
+        // CreateQP_AB takes s_est, v_est and s_tv_est as inputs: what the caller supplied stands in place of the estimate
+        const EstIn e[] = {est...};
+        if (e[0].ego) { s_est = e[0].s_est; v_est = e[0].v_est; }
+        if (e[0].lead) stv_est = e[0].stv_est;
+    }
     const double dist_hor = bcast(s_est, N) - in.s;                          // :200
     const double stv_Nm1 = kTargetVeh ? 0.0 : bcast(stv_est, N - 1);
     // bounds (A3)
@@ -1329,6 +1343,9 @@ __device__ __forceinline__ void ab_step(const DevCfg& C, WaveMem<MMAX, NS>& M, d
             if ((t == R_VLIM || t == R_VCURV || t == R_VSTOP || t == R_VTL) && !C.ab_route_rows) exists = false;
             if (kBaseline && (t == R_VINC || t == R_HWP)) exists = false;
         } else exists = (lane == N) && (t == R_SAFE1 || t == R_SAFE2);      // (CreateQP_TV.m:288-292: no terminal rows; skipped above)
+        // a supplied guess may say "no lead" (+inf) at a stage where the carried working set, made on another guess, holds a
+        // lead row: such a row does not exist, so that its code is dropped below instead of entering the solve with an infinite bound
+        if constexpr (kEst) { if ((t == R_SAFE1 || t == R_SAFE2 || t == R_HWP) && !(b[t] < kInf)) exists = false; }
         if (exists && lane == 0 && row_ga(t) == 0.0) {
             // stage-0 rows without an a-component are constants: fold into slack bounds
             exists = false;
@@ -1579,7 +1596,7 @@ __device__ WaveMem<MMAX, NS>* wave_mem(unsigned char* smem, int N, double*& He) 
 // which moves the spills of the N <= 32 kernel), and those kernels are to stay what they were.
 #undef EEPACC_AB_UNIT_CFG
 #ifdef EEPACC_IMPL_CLASS_MAP
-#define EEPACC_AB_UNIT_CFG const DevCfg& C = cfg_of(*Cp, b, class_of...);
+#define EEPACC_AB_UNIT_CFG const DevCfg& C = cfg_of(*Cp, b, extra...);
 #else
 #define EEPACC_AB_UNIT_CFG
 #endif
@@ -1592,27 +1609,61 @@ static_assert(kClasses ==
               "EEPACC_IMPL_CLASS_MAP is defined for the instantiation whose list entry sets EEPACC_IMPL_CLS, and for no other");
 template <class... ClassOf>
 __device__ __forceinline__ const DevCfg& cfg_of(const DevCfg& C0, int b, ClassOf... class_of) {
-    static_assert(sizeof...(ClassOf) == (kClasses ? 1 : 0), "the class map is an argument of the class kernels, and of them alone");
+    static_assert(kEst || sizeof...(ClassOf) == (kClasses ? 1 : 0), "the class map is an argument of the class kernels, and of them alone");
     if constexpr (kClasses) {
         const int32_t* map[] = {class_of...};
         return (&C0)[__builtin_amdgcn_readfirstlane(map[0][b])];
     } else return C0;
 }
 
-// B2: one step for B instances.  state: per instance 64 x uint64 codes (instance-major).
-template <int MMAX, int NS, int WPB, class... ClassOf>
+// est: the further arguments of the two kernels, and what this lane's stage gets of them.  Lane k loads stage k of every
+// supplied array ([N_hor+1][B]: one load per array per step, B doubles apart between lanes).  Row N_hor of s_tv_est is not
+// read: the terminal rows use s_tv_est(N) of the reference, stage N - 1 here (CreateQP_AB.m:376-387).
+__device__ __forceinline__ EstIn est_supplied(int lane, int N, int B, int b, const double* __restrict__ s_est,
+                                              const double* __restrict__ v_est, const double* __restrict__ s_tv_est) {
+    EstIn e{s_est != nullptr, s_tv_est != nullptr, 0.0, 0.0, 0.0};
+    const size_t ke = lane <= N ? lane : N, kl = lane < N ? lane : N - 1;
+    if (e.ego) { e.s_est = s_est[ke * B + b]; e.v_est = v_est[ke * B + b]; }
+    if (e.lead) e.stv_est = s_tv_est[kl * B + b];
+    return e;
+}
+// The lead's guess of the step at row kk of the launch's traces [n_lead][B], read from the traces themselves
+// (eepacc_run_abmpc_preview; scenarios.lead_preview is the specification).  Stage k looks tau_k ahead, at row
+// kk + idx[k] + frac[k] (tables of the handle, eepacc::preview_tables): the sample itself where frac is 0, else the two
+// neighbours interpolated, and past the last row that row carried on at its speed.  Products and sums are rounded one by
+// one, as the specification's are.
+__device__ __forceinline__ EstIn est_preview(const DevCfg& C, int lane, int B, int b, int kk, const double* __restrict__ s_tv,
+                                             const double* __restrict__ v_tv, const int32_t* __restrict__ idx,
+                                             const double* __restrict__ frac, int n_lead) {
+    EstIn e{false, true, 0.0, 0.0, 0.0};
+    const int k = lane < C.N ? lane : C.N - 1, last = n_lead - 1;
+    const int i = kk + idx[k];
+    const double f = frac[k];
+    if (i < last || (i == last && f == 0.0)) {
+        const double a = s_tv[(size_t)i * B + b];
+        e.stv_est = f == 0.0 ? a : __dadd_rn(__dmul_rn(1.0 - f, a), __dmul_rn(f, s_tv[(size_t)(i + 1) * B + b]));
+    } else {
+        const double dt = __dsub_rn(C.tau[k], __dmul_rn((double)(last - kk), C.Tvec[0]));
+        e.stv_est = __dadd_rn(s_tv[(size_t)last * B + b], __dmul_rn(v_tv[(size_t)last * B + b], dt));
+    }
+    return e;
+}
+
+// B2: one step for B instances.  state: per instance 64 x uint64 codes (instance-major).  extra: the class map (cls), the
+// three supplied arrays (est), nothing elsewhere.
+template <int MMAX, int NS, int WPB, class... Extra>
 __global__ void __launch_bounds__(64 * WPB, ((NS <= 32 && WPB >= 4) ? 2 : 1))
 k_ab_step(const DevCfg* __restrict__ Cp, int B,
           const double* __restrict__ s, const double* __restrict__ v, const double* __restrict__ a_prev,
           const double* __restrict__ t0, const double* __restrict__ s_tv, const double* __restrict__ v_tv,
           const double* __restrict__ a_tv_prev, unsigned long long* __restrict__ codes,
           double* __restrict__ out, double* __restrict__ s_pred, double* __restrict__ v_pred,
-          int32_t* __restrict__ status, int32_t* __restrict__ iters, ClassOf... class_of) {
+          int32_t* __restrict__ status, int32_t* __restrict__ iters, Extra... extra) {
     extern __shared__ __align__(16) unsigned char smem[];
     rc_table_init<MMAX>();
     const int b = blockIdx.x * WPB + (threadIdx.x >> 6);
     if (b >= B) return;
-    const DevCfg& C = cfg_of(*Cp, b, class_of...);
+    const DevCfg& C = cfg_of(*Cp, b, extra...);
     double* Hs;
     WaveMem<MMAX, NS>& M = *wave_mem<MMAX, NS>(smem, C.N, Hs);
     const int lane = lane_id();
@@ -1622,6 +1673,9 @@ k_ab_step(const DevCfg* __restrict__ Cp, int B,
     StepOut so;
     double sp, vp;
     double* predp = C.pred + (size_t)b * 128;
+    if constexpr (kEst)
+        ab_step<MMAX, NS>(C, M, Hs, in, code, so, sp, vp, predp, false, nullptr, est_supplied(lane, C.N, B, b, extra...));
+    else
     ab_step<MMAX, NS>(C, M, Hs, in, code, so, sp, vp, predp, false,
                       kIce ? C.hb + ((size_t)blockIdx.x * WPB + (threadIdx.x >> 6)) * (NS * NS) : nullptr);
     if (C.paramEstSetting == 2 && lane <= C.N) { predp[lane] = sp; predp[64 + lane] = vp; }
@@ -1636,7 +1690,7 @@ k_ab_step(const DevCfg* __restrict__ Cp, int B,
 // Ts and the LDS layout are fixed for the launch (Cp[0]); the settings are bound per work unit.
 // k_start > 0 resumes from the carried per-instance state (carry [6][B], see Carry; codes: shifted working set).  The
 // small-horizon kernel is compiled for 2 waves per SIMD (1: 512 registers, no scratch; measured slower).
-template <int MMAX, int NS, int WPB, class... ClassOf>
+template <int MMAX, int NS, int WPB, class... Extra>
 __global__ void __launch_bounds__(64 * WPB, ((NS <= 32 && WPB >= 4) ? 2 : 1))
 k_run_abmpc(const DevCfg* __restrict__ Cp, int B, int k_start, int n_steps,
             const double* __restrict__ s0, const double* __restrict__ v0, const double* __restrict__ a_m1,
@@ -1644,7 +1698,7 @@ k_run_abmpc(const DevCfg* __restrict__ Cp, int B, int k_start, int n_steps,
             double* __restrict__ carry, unsigned long long* __restrict__ codes,
             double* __restrict__ traj, int32_t* __restrict__ status, int32_t* __restrict__ iters_total,
             int* __restrict__ work_counter, int* __restrict__ done, int kChunkSteps,
-            int* __restrict__ err_word, int spin_limit, ClassOf... class_of) {
+            int* __restrict__ err_word, int spin_limit, Extra... extra) {
     extern __shared__ __align__(16) unsigned char smem[];
     const DevCfg& C = *Cp;                               // with classes: class 0, for what is fixed for the launch
     rc_table_init<MMAX>();
@@ -1671,6 +1725,10 @@ k_run_abmpc(const DevCfg* __restrict__ Cp, int B, int k_start, int n_steps,
             else measure(C, Ts, k_start + kk, kk, B, b, s0, v0, a_m1, s_tv, v_tv, cs, in);
             StepOut so;
             double sp, vp;
+            if constexpr (kEst)
+                ab_step<MMAX, NS>(C, M, Hs, in, code, so, sp, vp, predp, kk > kk0, nullptr,
+                                  est_preview(C, lane, B, b, kk, s_tv, v_tv, extra...));
+            else
             ab_step<MMAX, NS>(C, M, Hs, in, code, so, sp, vp, predp, kk > kk0,
                               kIce ? C.hb + ((size_t)blockIdx.x * WPB + (threadIdx.x >> 6)) * (NS * NS) : nullptr);
             if (C.paramEstSetting == 2) {
@@ -1693,11 +1751,13 @@ k_run_abmpc(const DevCfg* __restrict__ Cp, int B, int k_start, int n_steps,
 
 // the kernels of this instantiation as the host launches them: with the class map where the variant has one
 template <int MMAX, int NS, int WPB> constexpr auto step_kernel() {
-    if constexpr (kClasses) return &k_ab_step<MMAX, NS, WPB, const int32_t*>;
+    if constexpr (kEst) return &k_ab_step<MMAX, NS, WPB, const double*, const double*, const double*>;      // s_est, v_est, s_tv_est
+    else if constexpr (kClasses) return &k_ab_step<MMAX, NS, WPB, const int32_t*>;
     else return &k_ab_step<MMAX, NS, WPB>;
 }
 template <int MMAX, int NS, int WPB> constexpr auto run_kernel() {
-    if constexpr (kClasses) return &k_run_abmpc<MMAX, NS, WPB, const int32_t*>;
+    if constexpr (kEst) return &k_run_abmpc<MMAX, NS, WPB, const int32_t*, const double*, int>;             // idx, frac, n_lead
+    else if constexpr (kClasses) return &k_run_abmpc<MMAX, NS, WPB, const int32_t*>;
     else return &k_run_abmpc<MMAX, NS, WPB>;
 }
 

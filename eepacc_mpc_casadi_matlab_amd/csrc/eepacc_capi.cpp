@@ -94,6 +94,9 @@ struct eepacc_handle {
     DevMem<KpiCfg> d_kpi;                    // [max(n_classes, 1)]
     DevMem<double> d_kpi_cut;                // [max(n_classes, 1)]
     DevMem<FollowCfg> d_follow;              // [max(n_classes, 1)] what eepacc_follow_kpis reads of every class
+    // eepacc_run_abmpc_preview: where stage k looks into the lead trace (eepacc::preview_tables), made at the first call
+    DevMem<int32_t> d_pv_idx;                // [N]
+    DevMem<double> d_pv_frac;                // [N]
     eepacc::AbVariant variant() const { return n_classes ? eepacc::AbVariant::Classes : eepacc::ab_variant(cfg); }
     const int32_t* class_map() const { return n_classes ? d_class_of.p : nullptr; }
 };
@@ -297,7 +300,8 @@ static int need_tv(const eepacc_handle* h) { const int rc = not_classes(h, "eepa
 // and the launcher gets null pointers.
 static int ab_step_impl(eepacc_handle* h, const char* who, int B, const double* s, const double* v, const double* a_prev,
                         const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
-                        double* out, double* s_pred, double* v_pred, int32_t* status, void* stream) {
+                        double* out, double* s_pred, double* v_pred, int32_t* status, void* stream,
+                        const eepacc::AbSupplied* sup = nullptr) {
     const bool tv = h->cfg.bl_mode == 2;
     if (B < 0 || B > h->max_batch) return fail(EEPACC_EINVAL, "B exceeds max_batch of the handle");
     if (B == 0) return EEPACC_OK;
@@ -308,14 +312,14 @@ static int ab_step_impl(eepacc_handle* h, const char* who, int B, const double* 
     h->last_B = B;
     HIPCHK(eepacc::launch_ab_step(h->d_cfg, h->class_map(), h->cfg.N, h->variant(), B, s, v, a_prev, t0, tv ? nullptr : s_tv,
                                   tv ? nullptr : v_tv, tv ? nullptr : a_tv_prev, h->d_codes, out, s_pred, v_pred, status,
-                                  h->d_iters, (hipStream_t)stream));
+                                  h->d_iters, (hipStream_t)stream, sup));
     return EEPACC_OK;
 }
 
 // The closed loop of the same kernels; bad_sizes is the entry point's own wording of that refusal.
 static int ab_run_impl(eepacc_handle* h, const char* who, const char* bad_sizes, int B, int n_steps, const double* s0,
                        const double* v0, const double* a_minus1, const double* s_tv, const double* v_tv, double* traj,
-                       int32_t* status, void* stream) {
+                       int32_t* status, void* stream, const eepacc::AbPreview* pv = nullptr) {
     const bool tv = h->cfg.bl_mode == 2;
     if (B < 0 || B > h->max_batch || n_steps < 0) return fail(EEPACC_EINVAL, bad_sizes);
     if (B == 0 || n_steps == 0) return EEPACC_OK;
@@ -328,7 +332,7 @@ static int ab_run_impl(eepacc_handle* h, const char* who, const char* bad_sizes,
     h->last_B = B;
     HIPCHK(eepacc::launch_run_abmpc(h->d_cfg, h->class_map(), h->cfg.N, h->variant(), B, h->k_done, n_steps, s0, v0, a_minus1,
                                     tv ? nullptr : s_tv, tv ? nullptr : v_tv, h->d_carry, h->d_codes, traj, status, h->d_iters,
-                                    h->d_counter, h->d_done, h->d_err, h->num_cus, (hipStream_t)stream));
+                                    h->d_counter, h->d_done, h->d_err, h->num_cus, (hipStream_t)stream, pv));
     h->k_done += n_steps; h->carry_B = B;
     return EEPACC_OK;
 }
@@ -368,6 +372,63 @@ extern "C" int eepacc_run_tvmpc(eepacc_handle* h, int B, int n_steps, const doub
                                 const double* a_minus1, double* traj, int32_t* status, void* stream) {
     const int rc = need_tv(h);
     return rc != EEPACC_OK ? rc : ab_run_impl(h, "eepacc_run_tvmpc", "eepacc_run_tvmpc: bad B / n_steps", B, n_steps, s0, v0, a_minus1, nullptr, nullptr, traj, status, stream);
+}
+
+// ---- horizon guesses from the caller: eepacc_ab_step_est, eepacc_ab_build_qp_est, eepacc_run_abmpc_preview.  They run a plain
+// ABMPC handle (AbVariant::Plain) through the est kernels, on the handle's own state.
+static int est_handle(const eepacc_handle* h, const std::string& who) {
+    if (!h) return fail(EEPACC_EINVAL, who + ": NULL handle");
+    if (h->n_classes) return fail(EEPACC_ENOTSUP, who + ": a handle of eepacc_create_classes has no variant with supplied horizon guesses");
+    if (h->cfg.bl_mode != 0)
+        return fail(EEPACC_ENOTSUP, who + ": the handle was created with bl_mode = " + std::to_string(h->cfg.bl_mode) + "; supplied horizon guesses are built for ABMPC only, not for the baseline and target-vehicle controllers");
+    for (int k = 0; k < h->cfg.N; ++k)
+        if (h->cfg.mb_mask[k]) return fail(EEPACC_ENOTSUP, who + ": Mb[" + std::to_string(k) + "] != 0: move blocking has no variant with supplied horizon guesses");
+    if (h->cfg.ab_fuel_term == 2) return fail(EEPACC_ENOTSUP, who + ": ab_fuel_term == 2: the ICE-map fuel term has no variant with supplied horizon guesses");
+    return EEPACC_OK;
+}
+static int est_pair(const std::string& who, const double* s_est, const double* v_est) {
+    if (s_est && !v_est) return fail(EEPACC_EINVAL, who + ": s_est is given without v_est; the two are given together or both NULL");
+    if (v_est && !s_est) return fail(EEPACC_EINVAL, who + ": v_est is given without s_est; the two are given together or both NULL");
+    return EEPACC_OK;
+}
+
+extern "C" int eepacc_ab_step_est(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
+                                  const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                                  const double* s_est, const double* v_est, const double* s_tv_est,
+                                  double* out, double* s_pred, double* v_pred, int32_t* status, void* stream) {
+    const std::string who = "eepacc_ab_step_est";
+    if (const int rc = est_handle(h, who)) return rc;
+    if (B < 0 || B > h->max_batch)
+        return fail(EEPACC_EINVAL, who + ": B = " + std::to_string(B) + " is outside [0, max_batch = " + std::to_string(h->max_batch) + "]");
+    if (B == 0) return EEPACC_OK;
+    if (const int rc = est_pair(who, s_est, v_est)) return rc;
+    const eepacc::AbSupplied sup{s_est, v_est, s_tv_est};
+    return ab_step_impl(h, "eepacc_ab_step_est", B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, out, s_pred, v_pred, status, stream, &sup);
+}
+
+extern "C" int eepacc_run_abmpc_preview(eepacc_handle* h, int B, int n_steps, int n_lead, const double* s0, const double* v0,
+                                        const double* a_minus1, const double* s_tv, const double* v_tv, double* traj,
+                                        int32_t* status, void* stream) {
+    const std::string who = "eepacc_run_abmpc_preview";
+    if (const int rc = est_handle(h, who)) return rc;
+    if (B < 0 || B > h->max_batch || n_steps < 0)
+        return fail(EEPACC_EINVAL, who + ": B = " + std::to_string(B) + " must be in [0, max_batch = " + std::to_string(h->max_batch) + "] and n_steps = " + std::to_string(n_steps) + " not negative");
+    if (n_lead < n_steps)
+        return fail(EEPACC_EINVAL, who + ": n_lead = " + std::to_string(n_lead) + " is below n_steps = " + std::to_string(n_steps) + "; the lead traces hold at least the rows of the launch's steps");
+    if (B == 0 || n_steps == 0) return EEPACC_OK;
+    if (!h->d_pv_idx) {
+        const int N = h->cfg.N;
+        std::vector<int32_t> idx((size_t)N);
+        std::vector<double> frac((size_t)N);
+        eepacc::preview_tables(h->cfg.Tvec, N, idx.data(), frac.data());
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(h->d_pv_frac.alloc((size_t)N));
+        HIPCHK(hipMemcpy(h->d_pv_frac, frac.data(), (size_t)N * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(h->d_pv_idx.alloc((size_t)N));
+        HIPCHK(hipMemcpy(h->d_pv_idx, idx.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    const eepacc::AbPreview pv{h->d_pv_idx, h->d_pv_frac, n_lead};
+    return ab_run_impl(h, "eepacc_run_abmpc_preview", "eepacc_run_abmpc_preview: bad B / n_steps", B, n_steps, s0, v0, a_minus1, s_tv, v_tv, traj, status, stream, &pv);
 }
 
 // ---- the condensed QP of a step as data: eepacc_{ab,fb,bl}_qp_size, _qp_rows, _build_qp.  What the three families do alike is
@@ -474,6 +535,28 @@ extern "C" int eepacc_ab_build_qp(eepacc_handle* h, int B, const double* s, cons
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(eepacc::launch_ab_build(h->d_cfg, h->cfg.N, eepacc::ab_qp_num_rows(h->cfg), B, s, v, a_prev, t0, s_tv, v_tv,
                                    a_tv_prev, H, g, A, lba, uba, (hipStream_t)stream));
+    return EEPACC_OK;
+}
+
+extern "C" int eepacc_ab_build_qp_est(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
+                                      const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                                      const double* s_est, const double* v_est, const double* s_tv_est,
+                                      double* H, double* g, double* A, double* lba, double* uba, void* stream) {
+    const std::string who = "eepacc_ab_build_qp_est";
+    if (const int rc = est_handle(h, who)) return rc;
+    if (B < 0 || B > h->max_batch)
+        return fail(EEPACC_EINVAL, who + ": B = " + std::to_string(B) + " is outside [0, max_batch = " + std::to_string(h->max_batch) + "]");
+    if (B == 0) return EEPACC_OK;
+    const struct { const void* p; const char* name; } bufs[] = {
+        {s, "s"}, {v, "v"}, {a_prev, "a_prev"}, {t0, "t0"}, {s_tv, "s_tv"}, {v_tv, "v_tv"}, {a_tv_prev, "a_tv_prev"},
+        {H, "H"}, {g, "g"}, {A, "A"}, {lba, "lba"}, {uba, "uba"}};
+    for (const auto& bf : bufs)
+        if (!bf.p) return fail(EEPACC_EINVAL, who + ": " + bf.name + " is NULL");
+    if (const int rc = est_pair(who, s_est, v_est)) return rc;
+    const eepacc::AbSupplied sup{s_est, v_est, s_tv_est};
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(eepacc::launch_ab_build(h->d_cfg, h->cfg.N, eepacc::ab_qp_num_rows(h->cfg), B, s, v, a_prev, t0, s_tv, v_tv,
+                                   a_tv_prev, H, g, A, lba, uba, (hipStream_t)stream, &sup));
     return EEPACC_OK;
 }
 

@@ -201,6 +201,22 @@ int build_cfg(const eepacc_settings* S, const eepacc_vehicle* V, DevCfg& C, std:
     return EEPACC_OK;
 }
 
+// Where stage k of a horizon that starts at a row of a trace sampled every Tvec[0] looks into that trace: at row
+// + idx[k] + frac[k], with tau_k = sum_{i<k} Tvec[i] and p = tau_k / Tvec[0] in long double.  A stage that falls on a sample
+// up to rounding (|p - round(p)| < 1e-9, as with Tvec[k] / Ts a whole number and Ts = 0.3) gets that sample: frac = 0.
+void preview_tables(const double* Tvec, int N, int32_t* idx, double* frac) {
+    long double tau = 0.0L;
+    for (int k = 0; k < N; ++k) {
+        const long double p = tau / (long double)Tvec[0];
+        long double i = floorl(p), f = p - i;
+        if (f < 1e-9L) f = 0.0L;
+        else if (f > 1.0L - 1e-9L) { i += 1.0L; f = 0.0L; }
+        idx[k] = (int32_t)i;
+        frac[k] = (double)f;
+        tau += (long double)Tvec[k];
+    }
+}
+
 // What eepacc_kpis reads of a class (validated by build_cfg before): the power fit and driveline of the energy, the fuel
 // map and coast-down terms of ABO/Custom_plots.m:73-107 and the speed-limit table of ABO/Main.m:133.
 KpiCfg build_kpi_cfg(const eepacc_settings* S, const eepacc_vehicle* V) {

@@ -24,6 +24,10 @@ bool spd_inverse(std::vector<long double>& A, int n);
 // EEPACC_OK or the code of the first refusal, its text through set_error.
 int build_cfg(const eepacc_settings* S, const eepacc_vehicle* V, DevCfg& C, std::vector<double>& Hinv);
 
+// The tables of eepacc_run_abmpc_preview, [N] each, of a Tvec that build_cfg has accepted (positive entries): stage k of a
+// step reads the lead trace idx[k] + frac[k] rows after the step's own, frac in [0, 1) and 0 where the stage falls on a sample.
+void preview_tables(const double* Tvec, int N, int32_t* idx, double* frac);
+
 // Of settings that build_cfg has accepted.
 KpiCfg build_kpi_cfg(const eepacc_settings* S, const eepacc_vehicle* V);
 FollowCfg build_follow_cfg(const eepacc_settings* S, const eepacc_vehicle* V);

@@ -22,7 +22,7 @@
 #include "../../include/eepacc.h"
 
 // The variants of eepacc_ab_impl.inc, each compiled into its own namespace so that the default path carries no register or
-// instruction cost for the others: X(AbVariant, namespace, EEPACC_IMPL_MB, _BL, _TV, _ICE, _CLS, ...).  A new variant is a line here,
+// instruction cost for the others: X(AbVariant, namespace, EEPACC_IMPL_MB, _BL, _TV, _ICE, _CLS, _EST, ...).  A new variant is a line here,
 // its AbVariant (eepacc_ab.h) and its #include below.
 //   blc    baseline controller (RunOpt_BLMPC): the same kernels with CreateQP_BL's row grouping
 //   tvc    target-vehicle MPC (RunOpt_TVMPC): the baseline variant with CreateQP_TV's row catalogue (no vehicle-following
@@ -32,18 +32,22 @@
 //          the small ICE kernel 18 % of its throughput at N = 30 even where the handle has no Mb.
 //   cls    settings classes (eepacc_create_classes): the plain kernels with the DevCfg bound per instance, through the
 //          class map that its kernels alone take as one more argument
-#define EEPACC_AB_VARIANTS(X, ...)                                              \
-    X(Plain, nomb, false, false, false, false, false, __VA_ARGS__)              \
-    X(MoveBlocking, withmb, true, false, false, false, false, __VA_ARGS__)      \
-    X(Baseline, blc, false, true, false, false, false, __VA_ARGS__)             \
-    X(Ice, ice, false, false, false, true, false, __VA_ARGS__)                  \
-    X(IceMoveBlocking, icemb, true, false, false, true, false, __VA_ARGS__)     \
-    X(TargetVehicle, tvc, false, true, true, false, false, __VA_ARGS__)         \
-    X(Classes, cls, false, false, false, false, true, __VA_ARGS__)
+//   est    horizon guesses from the caller (eepacc_ab_step_est, eepacc_run_abmpc_preview): the plain kernels with the three
+//          supplied arrays (step) or the preview tables (closed loop) as further arguments of its kernels alone; no handle
+//          has this variant, its two entry points run a plain handle
+#define EEPACC_AB_VARIANTS(X, ...)                                                     \
+    X(Plain, nomb, false, false, false, false, false, false, __VA_ARGS__)              \
+    X(MoveBlocking, withmb, true, false, false, false, false, false, __VA_ARGS__)      \
+    X(Baseline, blc, false, true, false, false, false, false, __VA_ARGS__)             \
+    X(Ice, ice, false, false, false, true, false, false, __VA_ARGS__)                  \
+    X(IceMoveBlocking, icemb, true, false, false, true, false, false, __VA_ARGS__)     \
+    X(TargetVehicle, tvc, false, true, true, false, false, false, __VA_ARGS__)         \
+    X(Classes, cls, false, false, false, false, true, false, __VA_ARGS__)              \
+    X(Est, est, false, false, false, false, false, true, __VA_ARGS__)
 
 // an instantiation reads its switches from the list by the name of its namespace
 namespace eepacc { namespace ab_switch {
-#define EEPACC_AB_SWITCHES(E, NSP, MB_, BL_, TV_, ICE_, CLS_, ...) struct NSP { static constexpr bool MB = MB_, BL = BL_, TV = TV_, ICE = ICE_, CLS = CLS_; };
+#define EEPACC_AB_SWITCHES(E, NSP, MB_, BL_, TV_, ICE_, CLS_, EST_, ...) struct NSP { static constexpr bool MB = MB_, BL = BL_, TV = TV_, ICE = ICE_, CLS = CLS_, EST = EST_; };
 EEPACC_AB_VARIANTS(EEPACC_AB_SWITCHES)
 } }
 #define EEPACC_IMPL_MB ab_switch::EEPACC_IMPL_NS::MB
@@ -51,6 +55,7 @@ EEPACC_AB_VARIANTS(EEPACC_AB_SWITCHES)
 #define EEPACC_IMPL_TV ab_switch::EEPACC_IMPL_NS::TV
 #define EEPACC_IMPL_ICE ab_switch::EEPACC_IMPL_NS::ICE
 #define EEPACC_IMPL_CLS ab_switch::EEPACC_IMPL_NS::CLS
+#define EEPACC_IMPL_EST ab_switch::EEPACC_IMPL_NS::EST
 #define EEPACC_IMPL_NS nomb
 #include "eepacc_ab_impl.inc"
 #undef EEPACC_IMPL_NS
@@ -73,6 +78,9 @@ EEPACC_AB_VARIANTS(EEPACC_AB_SWITCHES)
 #define EEPACC_IMPL_CLASS_MAP       // the preprocessor's copy of the list's CLS switch (eepacc_ab_impl.inc checks that they agree)
 #include "eepacc_ab_impl.inc"
 #undef EEPACC_IMPL_CLASS_MAP
+#undef EEPACC_IMPL_NS
+#define EEPACC_IMPL_NS est
+#include "eepacc_ab_impl.inc"
 #undef EEPACC_IMPL_NS
 
 // ----------------------------------------------------------------------------------------------
@@ -105,13 +113,18 @@ size_t ab_smem_bytes(int N) {
 }
 
 // the kernel of the handle's variant, small or large horizon; a kernel with one parameter more than the launch has
-// arguments is a class kernel (eepacc_ab_impl.inc, cfg_of) and gets the class map as its last
+// arguments is a class kernel (eepacc_ab_impl.inc, cfg_of) and gets the class map as its last.  The est kernels have
+// three more: no handle has that variant, and launch_est below gives them theirs.
 template <class... P, class... A>
 static void launch_ab(void (*kernel)(P...), int grid, int block, size_t smem, hipStream_t stream, const int32_t* class_of, A... args) {
     if constexpr (sizeof...(P) == sizeof...(A) + 1) hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), smem, stream, args..., class_of);
-    else hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), smem, stream, args...);
+    else if constexpr (sizeof...(P) == sizeof...(A)) hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), smem, stream, args...);
 }
-#define EEPACC_LAUNCH_CASE(E, NSP, MB, BL, TV, ICE, CLS, KERNEL, MM, NSV, WPB, GRID, ...)                          \
+template <class K, class... A>
+static void launch_est(K kernel, int grid, int wpb, int N, hipStream_t stream, A... args) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * wpb), ab_smem_bytes(N), stream, args...);
+}
+#define EEPACC_LAUNCH_CASE(E, NSP, MB, BL, TV, ICE, CLS, EST, KERNEL, MM, NSV, WPB, GRID, ...)                          \
     case AbVariant::E: launch_ab(NSP::KERNEL<MM, NSV, WPB>(), GRID, 64 * WPB, ab_smem_bytes(N), stream, class_of, __VA_ARGS__); break;
 #define EEPACC_LAUNCH(KERNEL, MM, NSV, WPB, GRID, ...)                                                        \
     do { switch (variant) { EEPACC_AB_VARIANTS(EEPACC_LAUNCH_CASE, KERNEL, MM, NSV, WPB, GRID, __VA_ARGS__) } } while (0)
@@ -143,7 +156,12 @@ size_t ab_hb_doubles(int N, int B, int num_cus) {
 hipError_t launch_ab_step(const DevCfg* dC, const int32_t* class_of, int N, AbVariant variant, int B, const double* s, const double* v,
                           const double* a_prev, const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
                           unsigned long long* codes, double* out, double* s_pred, double* v_pred,
-                          int32_t* status, int32_t* iters, hipStream_t stream) {
+                          int32_t* status, int32_t* iters, hipStream_t stream, const AbSupplied* sup) {
+    if (sup) {
+        if (N > kNSSmall) launch_est(est::step_kernel<kMMaxLarge, kNSLarge, kWpbLarge>(), (B + kWpbLarge - 1) / kWpbLarge, kWpbLarge, N, stream, dC, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, codes, out, s_pred, v_pred, status, iters, sup->s_est, sup->v_est, sup->s_tv_est);
+        else launch_est(est::step_kernel<kMMaxSmall, kNSSmall, 4>(), (B + 3) / 4, 4, N, stream, dC, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, codes, out, s_pred, v_pred, status, iters, sup->s_est, sup->v_est, sup->s_tv_est);
+        return hipGetLastError();
+    }
     if (N > kNSSmall) EEPACC_LAUNCH(step_kernel, kMMaxLarge, kNSLarge, kWpbLarge, (B + kWpbLarge - 1) / kWpbLarge, dC, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, codes, out, s_pred, v_pred, status, iters);
     else EEPACC_LAUNCH(step_kernel, kMMaxSmall, kNSSmall, 4, (B + 3) / 4, dC, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, codes, out, s_pred, v_pred, status, iters);
     return hipGetLastError();
@@ -153,7 +171,7 @@ hipError_t launch_run_abmpc(const DevCfg* dC, const int32_t* class_of, int N, Ab
                             const double* s0, const double* v0, const double* a_m1, const double* s_tv, const double* v_tv,
                             double* carry, unsigned long long* codes, double* traj,
                             int32_t* status, int32_t* iters_total, int* work_counter, int* done, int* err_word, int num_cus,
-                            hipStream_t stream) {
+                            hipStream_t stream, const AbPreview* pv) {
     const bool large = N > kNSSmall;
     const int kChunkSteps = pick_chunk_steps(n_steps, B, num_cus * (large ? kWpbLarge : 4 * kBlocksSmall));
     // one chip-filling wave of blocks: LDS admits 8 (small) / 3 (large) waves per CU
@@ -161,6 +179,11 @@ hipError_t launch_run_abmpc(const DevCfg* dC, const int32_t* class_of, int N, Ab
     hipError_t e = begin_units(work_counter, done, iters_total, B, n_steps, kChunkSteps, large ? kWpbLarge : 4,
                                num_cus * (large ? 1 : kBlocksSmall), stream, ul);
     if (e != hipSuccess) return e;
+    if (pv) {
+        if (large) launch_est(est::run_kernel<kMMaxLarge, kNSLarge, kWpbLarge>(), ul.grid, kWpbLarge, N, stream, dC, B, k_start, n_steps, s0, v0, a_m1, s_tv, v_tv, carry, codes, traj, status, iters_total, work_counter, done, kChunkSteps, err_word, ul.spin_limit, pv->idx, pv->frac, pv->n_lead);
+        else launch_est(est::run_kernel<kMMaxSmall, kNSSmall, 4>(), ul.grid, 4, N, stream, dC, B, k_start, n_steps, s0, v0, a_m1, s_tv, v_tv, carry, codes, traj, status, iters_total, work_counter, done, kChunkSteps, err_word, ul.spin_limit, pv->idx, pv->frac, pv->n_lead);
+        return hipGetLastError();
+    }
     if (large)
         EEPACC_LAUNCH(run_kernel, kMMaxLarge, kNSLarge, kWpbLarge, ul.grid, dC, B, k_start, n_steps, s0, v0, a_m1, s_tv, v_tv, carry, codes, traj, status, iters_total, work_counter, done, kChunkSteps, err_word, ul.spin_limit);
     else
@@ -212,7 +235,7 @@ static hipError_t raise_smem(hipError_t e, K* kernel) {
     const int dyn = 160 * 1024 - ((MM * (MM + 1) / 2 * 2 + 255) & ~255);
     return e != hipSuccess ? e : hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, dyn);
 }
-#define EEPACC_RAISE_SMEM(E, NSP, MB, BL, TV, ICE, CLS, MM, NSV, WPB) \
+#define EEPACC_RAISE_SMEM(E, NSP, MB, BL, TV, ICE, CLS, EST, MM, NSV, WPB) \
     e = raise_smem<MM>(e, NSP::step_kernel<MM, NSV, WPB>()); e = raise_smem<MM>(e, NSP::run_kernel<MM, NSV, WPB>());
 hipError_t set_max_smem() {
     hipError_t e = hipSuccess;

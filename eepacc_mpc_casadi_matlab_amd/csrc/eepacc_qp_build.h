@@ -1,7 +1,8 @@
 // eepacc_qp_build.h -- the skeleton of a kernel that writes the condensed QP of one MPC step out as data (H, g, A, lba, uba
 // in the layout the dense QP operator reads): k_ab_build (eepacc_ab_build.hip), k_fb_qp (eepacc_fb_qp.hip) and k_bl_qp
 // (eepacc_bl_qp.hip).  One workgroup of BT threads per instance; stage quantities go into LDS once; the dynamic LDS holds the
-// sensitivity tables [N+1][N|1] and the row list.  What is here is what the three kernels do alike: the ego estimate, the row
+// sensitivity tables [N+1][N|1] and the row list.  What is here is what the three kernels do alike: the ego estimate (and the
+// guesses a caller supplies in its place, which k_ab_build alone takes so far), the row
 // list, the walks over H, the bounds and A, and for the two double-integrator controllers (AB, BL) the row type, the position
 // sensitivities and the entry of A.  The entry formulas differ per controller and stay in the units, which hand them to the
 // writers as lambdas; everything inlines.
@@ -63,6 +64,14 @@ __device__ inline void ego_estimate(const DevCfg& C, double s_0, double v_0, dou
     } else {
         estimate_traj(C, C.paramEstSetting, C.tConstACC_ego, s_0, v_0, a_minus1, k, se, ve);
     }
+}
+
+// Horizon guesses of stage k that the caller supplies instead ([N+1][B] each, as EstimateVehicleTrajectory returns them;
+// s_est and v_est both or neither; a null array keeps the estimate).  Row N of s_tv_est is not read: no row uses it.
+__device__ inline void supplied_estimates(int k, int N, size_t B, size_t b, const double* s_est, const double* v_est,
+                                          const double* s_tv_est, double& se, double& ve, double& st) {
+    if (s_est) { se = s_est[(size_t)k * B + b]; ve = v_est[(size_t)k * B + b]; }
+    if (s_tv_est && k < N) st = s_tv_est[(size_t)k * B + b];
 }
 
 // ---- H, row-major: consecutive lanes write consecutive entries; (ra, rb) advance without a division.  entry(ra, rb) -> double

@@ -13,7 +13,7 @@ from typing import Any, Dict, NamedTuple, Optional
 
 import numpy as np
 
-from ._abi import (SettingsHolder, SettingsPOD, Vehicle, make_vehicle, pack_classes, OUT, OUT_N, OUT_FIELDS, KPI_N, FKPI_N, FKPI_WEIGHTS, AB_BUILD_ARGTYPES,
+from ._abi import (SettingsHolder, SettingsPOD, Vehicle, make_vehicle, pack_classes, OUT, OUT_N, OUT_FIELDS, KPI_N, FKPI_N, FKPI_WEIGHTS, AB_BUILD_ARGTYPES, AB_EST_ARGTYPES,
                    FB_BUILD_ARGTYPES, BL_BUILD_ARGTYPES,
                    c_double_p, as_dptr, as_iptr)
 
@@ -72,7 +72,8 @@ def load_library() -> C.CDLL:
     lib.eepacc_qp_solve_batched.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [dp] * 8 + [dp, dp, dp, vp]
     lib.eepacc_qp_solve_batched_dual.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [dp] * 8 + [dp, dp] + [dp] * 3 + [dp] * 5 + [vp]
     lib.eepacc_qp_kkt_solve_batched.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int] + [dp] * 2 + [dp] * 2 + [dp] * 3 + [dp] * 3 + [dp, vp]
-    for name, argtypes in list(AB_BUILD_ARGTYPES.items()) + list(FB_BUILD_ARGTYPES.items()) + list(BL_BUILD_ARGTYPES.items()):
+    for name, argtypes in (list(AB_BUILD_ARGTYPES.items()) + list(FB_BUILD_ARGTYPES.items()) + list(BL_BUILD_ARGTYPES.items())
+                           + list(AB_EST_ARGTYPES.items())):
         getattr(lib, name).argtypes = argtypes
     lib.eepacc_synchronize.argtypes = [vp, vp]
     lib.eepacc_build_flags.restype = C.c_char_p
@@ -88,6 +89,7 @@ ABI_SYMBOLS = ["eepacc_last_error", "eepacc_version", "eepacc_sizeof_settings", 
                "eepacc_follow_kpis",
                "eepacc_last_iterations", "eepacc_qp_solve_batched", "eepacc_qp_solve_batched_dual", "eepacc_qp_kkt_solve_batched",
                "eepacc_ab_qp_size", "eepacc_ab_qp_rows", "eepacc_ab_build_qp",
+               "eepacc_ab_step_est", "eepacc_ab_build_qp_est", "eepacc_run_abmpc_preview",
                "eepacc_fb_qp_size", "eepacc_fb_qp_rows", "eepacc_fb_build_qp",
                "eepacc_bl_qp_size", "eepacc_bl_qp_rows", "eepacc_bl_build_qp",
                "eepacc_synchronize", "eepacc_build_flags"]
@@ -240,14 +242,16 @@ class Engine:
                   vp.data_ptr() if want_pred else None, status.data_ptr(), self._stream()))
         return out, sp, vp, status
 
-    def _run(self, fn, ins, lead, n_steps, resume, out):
-        """Closed loop: ins = (s0, v0, a_minus1), lead = (s_tv, v_tv) as [n_steps, B] or None with n_steps given."""
+    def _run(self, fn, ins, lead, n_steps, resume, out, lead_rows=True):
+        """Closed loop: ins = (s0, v0, a_minus1), lead = (s_tv, v_tv) as [n_steps, B] or None with n_steps given
+        (lead_rows=False: the lead has more rows than the launch has steps, and n_steps is given too)."""
         t = self.torch
         if not resume:
             self.reset()
         if lead is not None:
             lead = [t.as_tensor(x, dtype=t.float64, device=self.device).contiguous() for x in lead]
-            n_steps, B = lead[0].shape
+            B = lead[0].shape[1]
+            n_steps = lead[0].shape[0] if lead_rows else int(n_steps)
         else:
             n_steps, B, lead = int(n_steps), int(t.as_tensor(ins[0]).numel()), []
         ins = [self._d(x, B) for x in ins]
@@ -305,6 +309,49 @@ class Engine:
         ptrs, qp = self._qp_outputs(B, *self.ab_qp_size())
         _check(self.lib.eepacc_ab_build_qp(self.h, B, *[x.data_ptr() for x in ins], *ptrs, self._stream()))
         return AbQp(*qp)
+
+    # the same two with the horizon guesses supplied, and the closed loop with the lead's guess read from its trace ------
+    def _est(self, B, s_est, v_est, s_tv_est):
+        """The three supplied arrays [N+1, B] (None: the engine's estimator) as device tensors."""
+        return [None if x is None else self._d(x, (self.N + 1) * B) for x in (s_est, v_est, s_tv_est)]
+
+    def ab_step_est(self, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, s_est=None, v_est=None, s_tv_est=None,
+                    want_pred: bool = True):
+        """eepacc_ab_step_est: ab_step with the horizon guesses supplied, the contract of the reference's Simulink block
+        ACCMPC(..., s_est, v_est, s_tv_est, ...).  s_est, v_est (together or both None) and s_tv_est are [N+1, B] as
+        EstimateVehicleTrajectory returns them (the layout of the predictions ab_step returns); None keeps the engine's
+        estimator.  Reads and writes the engine state ab_step does; results as ab_step."""
+        t = self.torch
+        B = int(t.as_tensor(s).numel())
+        est = self._est(B, s_est, v_est, s_tv_est)
+        fn = lambda h, B_, *rest: self.lib.eepacc_ab_step_est(h, B_, *rest[:7], *[_ptr(x) for x in est], *rest[7:])
+        return self._step(fn, (s, v, a_prev, t0, s_tv, v_tv, a_tv_prev), want_pred)
+
+    def ab_build_qp_est(self, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, s_est=None, v_est=None, s_tv_est=None) -> AbQp:
+        """eepacc_ab_build_qp_est: the condensed QP of the step ab_step_est solves, CreateQP_AB on the supplied guesses.
+        Returns AbQp as ab_build_qp does; ab_qp_size and ab_qp_rows describe it.  qp_sens.ab_lead_gradient differentiates
+        its solution with respect to s_tv_est."""
+        t = self.torch
+        B = int(t.as_tensor(s).numel())
+        ins = [self._d(x, B) for x in (s, v, a_prev, t0, s_tv, v_tv, a_tv_prev)]
+        est = self._est(B, s_est, v_est, s_tv_est)
+        ptrs, qp = self._qp_outputs(B, *self.ab_qp_size())
+        _check(self.lib.eepacc_ab_build_qp_est(self.h, B, *[x.data_ptr() for x in ins], *[_ptr(x) for x in est], *ptrs,
+                                               self._stream()))
+        return AbQp(*qp)
+
+    def run_abmpc_preview(self, s0, v0, a_minus1, s_tv, v_tv, n_steps=None, resume: bool = False, out=None):
+        """eepacc_run_abmpc_preview: run_abmpc whose steps take the lead's horizon guess from the lead trace itself
+        (scenarios.lead_preview states the rule); the ego estimator stays the engine's.  s_tv, v_tv: [n_lead, B] with
+        n_lead >= n_steps (default n_lead): the rows of the launch's steps, then the future the last steps look into; past
+        the last row the lead is carried on at its last speed.  Returns traj [n_steps, OUT_N, B], status [n_steps, B];
+        resume / out as run_abmpc (a resumed launch passes the continued rows)."""
+        t = self.torch
+        lead = [t.as_tensor(x, dtype=t.float64, device=self.device).contiguous() for x in (s_tv, v_tv)]
+        n_lead, B = lead[0].shape
+        n_steps = n_lead if n_steps is None else int(n_steps)
+        fn = lambda h, B_, n, *rest: self.lib.eepacc_run_abmpc_preview(h, B_, n, n_lead, *rest)
+        return self._run(fn, (s0, v0, a_minus1), lead, n_steps, resume, out, lead_rows=False)
 
     # B1 ------------------------------------------------------------------------------------
     def run_abmpc(self, s0, v0, a_minus1, s_tv, v_tv, resume: bool = False, out=None, by_name_bl: bool = False):

@@ -205,6 +205,32 @@ def qp_vjp(eng, sol, H, A, gx, glam_a=None, glam_x=None):
     return gr
 
 
+def lead_gradient_from_uba(g_uba, stage, typ, N):
+    """dL/ds_tv_est [B, N+1] from dL/duba [B, nC] of a problem of Engine.ab_build_qp / ab_build_qp_est and its row table
+    (stage, typ) of Engine.ab_qp_rows.  The lead's guess enters that problem only through uba of the rows safe1, safe2 and
+    hwp, each with coefficient 1 (CreateQP_AB.m:355-371), so entry k is the sum of g_uba over those rows of stage k.  The
+    two terminal rows (stage N in the table) read s_tv_est(N) of the reference, row N - 1 of the array, and are credited
+    there; row N of the array is not read and gets 0.  numpy arrays or torch tensors."""
+    from ._abi import AB_ROW
+    stage = np.asarray(stage).reshape(-1); typ = np.asarray(typ).reshape(-1)
+    lead = (typ == AB_ROW["safe1"]) | (typ == AB_ROW["safe2"]) | (typ == AB_ROW["hwp"])
+    sel = np.zeros((stage.size, N + 1))
+    sel[np.nonzero(lead)[0], np.minimum(stage[lead], N - 1)] = 1.0
+    if isinstance(g_uba, np.ndarray):
+        return g_uba @ sel
+    return g_uba @ g_uba.new_tensor(sel)
+
+
+def ab_lead_gradient(eng, qp, sol, rows, gx):
+    """Gradient of a scalar loss on the solution x of an ABMPC step with respect to the lead prediction s_tv_est: [B, N+1]
+    (device tensor; row N_hor of s_tv_est is not read, its entry is 0).  qp: the AbQp of eng.ab_build_qp_est (or
+    ab_build_qp), sol: the QpDualResult of eng.qp_solve_batched_dual on it, rows: eng.ab_qp_rows(), gx [B, nV]: dL/dx
+    (x[0] is the applied acceleration EEPACC_OUT_AQP).  One adjoint solve (qp_vjp), then lead_gradient_from_uba.  Exactly 0
+    for a stage none of whose lead rows is in the working set; NaN where qp_vjp gives NaN."""
+    gr = qp_vjp(eng, sol, qp.H, qp.A, gx)
+    return lead_gradient_from_uba(gr["uba"], rows[0], rows[1], eng.N)
+
+
 _FUNCTION = None
 
 

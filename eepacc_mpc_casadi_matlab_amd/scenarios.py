@@ -86,3 +86,49 @@ def make_use_case_mix(cases, per_case: int, tree: str, N_hor: int, n_steps=None,
     pick = lambda key: np.array([float(OPTs[k][key]) for k in class_of])
     return dict(OPT=OPTs, V=Vs, class_of=class_of, s0=pick("s_init"), v0=pick("v_init"), a_minus1=pick("a_minus1"),
                 s_tv=s_tv, v_tv=v_tv, n_steps=n_steps)
+
+
+def preview_tables(Tvec):
+    """(idx, frac), [N] each: where stage k of a horizon looks into a trace sampled every Tvec[0], counted in rows from the
+    step's own.  p = tau_k / Tvec[0] with tau_k = sum_{i<k} Tvec[i], in numpy.longdouble; idx = floor(p), frac = p - idx,
+    snapped to 0 below 1e-9 and to the next index above 1 - 1e-9 (a stage that falls on a sample up to rounding, as with
+    Tvec[k] / Ts a whole number and Ts = 0.3, reads that sample)."""
+    LD = np.longdouble
+    T = np.asarray(Tvec, dtype=np.float64).reshape(-1)
+    idx = np.zeros(T.size, dtype=np.int32); frac = np.zeros(T.size)
+    tau = LD(0.0)
+    for k in range(T.size):
+        p = tau / LD(T[0])
+        i = np.floor(p); f = p - i
+        if f < LD("1e-9"):
+            f = LD(0.0)
+        elif f > LD(1.0) - LD("1e-9"):
+            i += 1; f = LD(0.0)
+        idx[k] = int(i); frac[k] = float(f)
+        tau = tau + LD(T[k])
+    return idx, frac
+
+
+def lead_preview(s_tv, v_tv, r, Tvec):
+    """The lead's horizon guess s_tv_est [N+1, B] of the step at row r of the traces s_tv, v_tv [n_lead, B], read from the
+    traces themselves: the specification of what eepacc_run_abmpc_preview hands its steps (Engine.ab_step_est takes the
+    result as s_tv_est).  Stage k looks tau_k ahead, at row r + idx[k] + frac[k] (preview_tables): the sample itself where
+    frac is 0 (so +inf, no lead, stays +inf), else (1 - frac) s_tv[i] + frac s_tv[i + 1], and past the last row
+    s_tv[-1] + v_tv[-1] (tau_k - (n_lead - 1 - r) Tvec[0]).  Row N is not read by the step and is left at the value of
+    row N - 1."""
+    s_tv = np.asarray(s_tv, dtype=np.float64); v_tv = np.asarray(v_tv, dtype=np.float64)
+    if s_tv.ndim == 1:
+        s_tv = s_tv[:, None]; v_tv = v_tv[:, None]
+    T = np.asarray(Tvec, dtype=np.float64).reshape(-1)
+    N, last = T.size, s_tv.shape[0] - 1
+    idx, frac = preview_tables(T)
+    tau = np.concatenate([[0.0], np.cumsum(T)])                    # running double sum, as the settings translation keeps it
+    out = np.empty((N + 1, s_tv.shape[1]))
+    for k in range(N):
+        i, f = int(r) + int(idx[k]), float(frac[k])
+        if i < last or (i == last and f == 0.0):
+            out[k] = s_tv[i] if f == 0.0 else (1.0 - f) * s_tv[i] + f * s_tv[i + 1]
+        else:
+            out[k] = s_tv[last] + v_tv[last] * (tau[k] - float(last - int(r)) * T[0])
+    out[N] = out[N - 1]
+    return out

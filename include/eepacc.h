@@ -204,8 +204,10 @@ int  eepacc_num_classes(const eepacc_handle* h);
 int  eepacc_reset(eepacc_handle* h);
 
 /* B2 -- per-step operator: one receding-horizon step of ABMPC for B instances
- * (body of the kk-loop ABO/RunOpt_ABMPC.m:193-329 after the measurement block; the same
- * contract as the Simulink MATLAB-Function block ACCMPC(...) of ABO/ACCMPC.slx chart_121).
+ * (body of the kk-loop ABO/RunOpt_ABMPC.m:193-329 after the measurement block, the estimators :193-200 included: the
+ * horizon guesses are computed from the measured state and lead sample by the handle's paramEstSetting / TVestSetting.
+ * The Simulink MATLAB-Function block ACCMPC(N_hor, Tvec, s_measured, v_measured, s_est, v_est, s_tv_est, OPTsettings, V)
+ * of ABO/ACCMPC.slx chart_121 takes those guesses as inputs: that contract is eepacc_ab_step_est's, below).
  * Inputs, device, each [B]: s, v (measured state), a_prev (a_minus1), t0, s_tv, v_tv,
  * a_tv_prev (lead acceleration estimate).  Outputs, device: out[EEPACC_OUT_N][B];
  * s_pred,v_pred [(N_hor+1)][B] = z(1:7:end), z(2:7:end) (may be NULL); status [B] int32.
@@ -215,6 +217,50 @@ int  eepacc_ab_step(eepacc_handle* h, int B,
                     const double* s_tv, const double* v_tv, const double* a_tv_prev,
                     double* out, double* s_pred, double* v_pred, int32_t* status,
                     void* stream);
+
+/* The same step with the horizon guesses supplied: the contract of the Simulink block ACCMPC(..., s_est, v_est, s_tv_est, ...)
+ * and of CreateQP_AB(OPTsettings, n_x, n_u, s_0, v_0, s_est, v_est, s_tv_est, t_0, a_minus1) (ABO/RunInit_ABMPC.m:58,
+ * RunOpt_ABMPC.m:204), for a lead prediction of the caller's own (a communicated plan, a learned predictor, a tracker).
+ * s_est, v_est, s_tv_est: device arrays [N_hor+1][B], as EstimateVehicleTrajectory returns them (the layout of s_pred / v_pred,
+ * so a prediction output can be fed back in).  s_est and v_est are given together or both NULL; NULL: the handle's
+ * paramEstSetting.  s_tv_est may be NULL: the handle's TVestSetting.  Row N_hor of s_tv_est is not read (the terminal rows
+ * use s_tv_est(N), CreateQP_AB.m:376-387).  Row 0 of s_est and v_est is used as given (the reference passes the measurement
+ * there) and is not overwritten.  +inf in s_tv_est: no lead at that stage.  With all three NULL the entries compute what
+ * eepacc_ab_step / eepacc_ab_build_qp compute.  Every other argument as in eepacc_ab_step / eepacc_ab_build_qp.
+ * eepacc_ab_step_est reads and writes exactly the handle state eepacc_ab_step does (warm start, carried predictions,
+ * iteration counts): the two can alternate on one handle.  eepacc_ab_build_qp_est reads no solver state and writes none;
+ * eepacc_ab_qp_size and eepacc_ab_qp_rows describe its output.  s_tv_est enters the problem only through uba of the rows
+ * EEPACC_AB_ROW_SAFE1, _SAFE2 and _HWP, so the derivative of the solution with respect to the lead prediction is one adjoint
+ * solve on the built problem (qp_sens.ab_lead_gradient of the Python package).
+ *
+ * eepacc_run_abmpc_preview: eepacc_run_abmpc with the lead's horizon guess read from the lead trace itself (perfect preview);
+ * the ego estimator stays the handle's.  s_tv, v_tv [n_lead][B], n_lead >= n_steps: rows 0 .. n_steps-1 are the measurements
+ * of this launch's steps as in eepacc_run_abmpc (resumed launches pass the continued rows), the rows after them the future
+ * that the last steps look into.  At the step of row r, stage k lies tau_k = sum_{i<k} Tvec[i] ahead, at row r + p with
+ * p = tau_k / Tvec[0]; idx = floor(p) and frac = p - idx are computed once per handle in long double, frac snapped to 0 below
+ * 1e-9 and to the next index above 1 - 1e-9.  The guess is the sample s_tv[r+idx] where frac = 0 (no arithmetic), else
+ * (1-frac) s_tv[r+idx] + frac s_tv[r+idx+1], and past the last row s_tv[n_lead-1] + v_tv[n_lead-1] (t - t_last).  A lead at
+ * +inf (no lead, Main.m:77-80) stays +inf.  scenarios.lead_preview of the Python package states the rule in numpy.
+ *
+ * EEPACC_ENOTSUP, the message naming the cause: a handle of eepacc_create_classes, bl_mode != 0, any Mb[k] != 0,
+ * ab_fuel_term == 2.  EEPACC_EINVAL: a NULL required buffer, s_est without v_est or the reverse, B out of range,
+ * n_lead < n_steps.  B = 0 returns EEPACC_OK.
+ * Not built: supplied guesses for FBMPC, for the baseline and target-vehicle controllers, and a preview of the ego estimate.
+ * Cost against eepacc_ab_step / eepacc_run_abmpc: tools/gpu_ab_est_bench.py, DESIGN.md section 3.4f. */
+int  eepacc_ab_step_est(eepacc_handle* h, int B,
+                        const double* s, const double* v, const double* a_prev, const double* t0,
+                        const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                        const double* s_est, const double* v_est, const double* s_tv_est,
+                        double* out, double* s_pred, double* v_pred, int32_t* status, void* stream);
+int  eepacc_ab_build_qp_est(eepacc_handle* h, int B,
+                            const double* s, const double* v, const double* a_prev, const double* t0,
+                            const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                            const double* s_est, const double* v_est, const double* s_tv_est,
+                            double* H, double* g, double* A, double* lba, double* uba, void* stream);
+int  eepacc_run_abmpc_preview(eepacc_handle* h, int B, int n_steps, int n_lead,
+                              const double* s0, const double* v0, const double* a_minus1,
+                              const double* s_tv, const double* v_tv,
+                              double* traj, int32_t* status, void* stream);
 
 /* B1 -- closed loop: optSol = RunOpt_ABMPC(OPTsettings) for B independent instances
  * (ABO/RunOpt_ABMPC.m:154-340 incl. measurement block, plant, force allocation).
