@@ -31,6 +31,19 @@ FKPI_N = len(FKPI_FIELDS)
 FKPI = {name: i for i, name in enumerate(FKPI_FIELDS)}
 FKPI_WEIGHTS = {"ab": 0, "fb": 1, "none": 2}      # EEPACC_FKPI_W_AB, _W_FB, _W_NONE
 
+# enum EEPACC_RKPI_*: rows of the table of eepacc_route_kpis, raw SI units; enum EEPACC_RLIM_*: the caps of its `limits`
+RKPI_FIELDS = ["vlim_excess_max", "vlim_excess_index", "vlim_viol_steps", "vcurv_excess_max", "vcurv_viol_steps",
+               "vstop_excess_max", "vstop_viol_steps", "vtl_excess_max", "vtl_viol_steps", "stops_passed", "stop_cross_v_max",
+               "tl_passed", "red_crossings", "red_crossings_possible", "red_cross_first_index",
+               "a_over_max", "a_under_max", "j_over_max", "j_under_max", "comfort_viol_steps", "v_min"]
+RKPI_N = len(RKPI_FIELDS)
+RKPI = {name: i for i, name in enumerate(RKPI_FIELDS)}
+RLIM_FIELDS = ["v_lim", "v_curv", "v_stop", "v_tl"]
+RLIM_N = len(RLIM_FIELDS)
+RLIM = {name: i for i, name in enumerate(RLIM_FIELDS)}
+# eepacc_route_kpis(h, B, n_steps, t_start, tol_host, traj, status, rkpi, limits, stream); device arrays travel as addresses
+ROUTE_KPIS_ARGTYPES = [C.c_void_p, C.c_int, C.c_int, C.c_double, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+
 # enum EEPACC_AB_ROW_*: the row types of eepacc_ab_qp_rows, ascending in the order of the rows within a stage
 AB_ROW_TYPES = ["s", "v", "xi_v", "xi_h", "xi_s", "xi_f", "blocked", "a_max", "a_min", "j_max", "j_min",
                 "v_lim", "v_curv", "v_stop", "v_tl", "v_inc", "safe1", "safe2", "hwp"]

@@ -20,11 +20,13 @@
 #include "eepacc_fbs.h"
 #include "eepacc_kpis.h"
 #include "eepacc_follow.h"
+#include "eepacc_route.h"
 #include "../../include/eepacc.h"
 
 using eepacc::DevCfg;
 using eepacc::KpiCfg;
 using eepacc::FollowCfg;
+using eepacc::RouteCfg;
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) { g_err = msg; return code; }
@@ -94,6 +96,7 @@ struct eepacc_handle {
     DevMem<KpiCfg> d_kpi;                    // [max(n_classes, 1)]
     DevMem<double> d_kpi_cut;                // [max(n_classes, 1)]
     DevMem<FollowCfg> d_follow;              // [max(n_classes, 1)] what eepacc_follow_kpis reads of every class
+    DevMem<RouteCfg> d_route;                // [max(n_classes, 1)] what eepacc_route_kpis reads of every class
     // eepacc_run_abmpc_preview: where stage k looks into the lead trace (eepacc::preview_tables), made at the first call
     DevMem<int32_t> d_pv_idx;                // [N]
     DevMem<double> d_pv_frac;                // [N]
@@ -116,12 +119,13 @@ static int build_cfg_fit(const eepacc_settings* S, const eepacc_vehicle* V, DevC
 }
 using eepacc::build_kpi_cfg;
 using eepacc::build_follow_cfg;
+using eepacc::build_route_cfg;
 
 // The device side of a handle.  Cs: one validated DevCfg per class with its inverse Hessian in Hinv (N x N each, class after
 // class); classes: the handle of eepacc_create_classes, which keeps a class map and runs AbVariant::Classes, also with one class.
 static int create_on_device(eepacc_handle** out, std::vector<DevCfg>& Cs, const std::vector<double>& Hinv,
-                            const std::vector<KpiCfg>& Ks, const std::vector<FollowCfg>& Fs, bool classes, int device,
-                            int max_batch) {
+                            const std::vector<KpiCfg>& Ks, const std::vector<FollowCfg>& Fs, const std::vector<RouteCfg>& Rs,
+                            bool classes, int device, int max_batch) {
     DevCfg& C = Cs[0];
     int ndev = 0;
     HIPCHK(hipGetDeviceCount(&ndev));
@@ -154,6 +158,8 @@ static int create_on_device(eepacc_handle** out, std::vector<DevCfg>& Cs, const 
     HIPCHK(h->d_kpi_cut.alloc_zero(Ks.size()));
     HIPCHK(h->d_follow.alloc(Fs.size()));
     HIPCHK(hipMemcpy(h->d_follow, Fs.data(), Fs.size() * sizeof(FollowCfg), hipMemcpyHostToDevice));
+    HIPCHK(h->d_route.alloc(Rs.size()));
+    HIPCHK(hipMemcpy(h->d_route, Rs.data(), Rs.size() * sizeof(RouteCfg), hipMemcpyHostToDevice));
     if (classes) {
         h->n_classes = (int)Cs.size();
         HIPCHK(h->d_class_of.alloc_zero(nB));
@@ -187,7 +193,7 @@ extern "C" int eepacc_create(eepacc_handle** out, const eepacc_settings* S, cons
     std::vector<double> Hinv;
     int rc = build_cfg_fit(S, V, Cs[0], Hinv);
     if (rc != EEPACC_OK) return rc;
-    return create_on_device(out, Cs, Hinv, {build_kpi_cfg(S, V)}, {build_follow_cfg(S, V)}, false, device, max_batch);
+    return create_on_device(out, Cs, Hinv, {build_kpi_cfg(S, V)}, {build_follow_cfg(S, V)}, {build_route_cfg(S, V)}, false, device, max_batch);
 }
 
 // Every class is checked like the settings of eepacc_create, and against class 0 in what selects the kernel and the launch
@@ -204,6 +210,7 @@ extern "C" int eepacc_create_classes(eepacc_handle** out, const eepacc_settings*
     std::vector<double> Hinv, Hk;
     std::vector<KpiCfg> Ks;
     std::vector<FollowCfg> Fs;
+    std::vector<RouteCfg> Rs;
     for (int k = 0; k < n_classes; ++k) {
         const std::string who = "eepacc_create_classes: class " + std::to_string(k) + ": ";
         if (S[k].N_hor != N)
@@ -221,8 +228,9 @@ extern "C" int eepacc_create_classes(eepacc_handle** out, const eepacc_settings*
         Hinv.insert(Hinv.end(), Hk.begin(), Hk.end());
         Ks.push_back(build_kpi_cfg(&S[k], &V[k]));
         Fs.push_back(build_follow_cfg(&S[k], &V[k]));
+        Rs.push_back(build_route_cfg(&S[k], &V[k]));
     }
-    return create_on_device(out, Cs, Hinv, Ks, Fs, true, device, max_batch);
+    return create_on_device(out, Cs, Hinv, Ks, Fs, Rs, true, device, max_batch);
 }
 
 extern "C" int eepacc_num_classes(const eepacc_handle* h) { return h && h->n_classes ? h->n_classes : 1; }
@@ -629,6 +637,31 @@ extern "C" int eepacc_follow_kpis(eepacc_handle* h, int B, int n_steps, int weig
     if (const int rc = classes_ready(h, "eepacc_follow_kpis", B)) return rc;
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(eepacc::launch_follow_kpis(h->d_follow, h->class_map(), weights, B, n_steps, traj, s_tv, v_tv, fkpi, (hipStream_t)stream));
+    return EEPACC_OK;
+}
+
+// Route-compliance key figures (ABO/Main.m:374-433, :486-534, EstimateRouteAndComfortBounds.m:154-189), per instance, on the
+// device.  Reads the trajectory and the handle's RouteCfg table only: no carried state.  What does not need the handle is
+// checked first.
+extern "C" int eepacc_route_kpis(eepacc_handle* h, int B, int n_steps, double t_start, const double* tol_host,
+                                 const double* traj, const int32_t* status, double* rkpi, double* limits, void* stream) {
+    if (n_steps < 1) return fail(EEPACC_EINVAL, "eepacc_route_kpis: n_steps = " + std::to_string(n_steps) + " must be at least 1");
+    if (!isfinite(t_start)) return fail(EEPACC_EINVAL, "eepacc_route_kpis: t_start is not finite");
+    if (!tol_host) return fail(EEPACC_EINVAL, "eepacc_route_kpis: tol_host is NULL");
+    static const char* const tol_name[3] = {"v_tol", "a_tol", "j_tol"};
+    for (int i = 0; i < 3; ++i)
+        if (!isfinite(tol_host[i]) || tol_host[i] < 0.0)
+            return fail(EEPACC_EINVAL, std::string("eepacc_route_kpis: tol_host[") + std::to_string(i) + "] (" + tol_name[i] + ") must be finite and not negative");
+    if (!traj) return fail(EEPACC_EINVAL, "eepacc_route_kpis: traj is NULL");
+    if (!status) return fail(EEPACC_EINVAL, "eepacc_route_kpis: status is NULL");
+    if (!rkpi) return fail(EEPACC_EINVAL, "eepacc_route_kpis: rkpi is NULL");
+    if (!h) return fail(EEPACC_EINVAL, "eepacc_route_kpis: NULL handle");
+    if (B < 0 || B > h->max_batch) return fail(EEPACC_EINVAL, "eepacc_route_kpis: B = " + std::to_string(B) + " is outside [0, max_batch = " + std::to_string(h->max_batch) + "]");
+    if (B == 0) return EEPACC_OK;
+    if (const int rc = classes_ready(h, "eepacc_route_kpis", B)) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(eepacc::launch_route_kpis(h->d_route, h->class_map(), B, n_steps, t_start, tol_host[0], tol_host[1], tol_host[2], traj, rkpi,
+                                     limits, (hipStream_t)stream));
     return EEPACC_OK;
 }
 

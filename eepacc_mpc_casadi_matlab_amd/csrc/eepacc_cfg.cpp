@@ -248,4 +248,26 @@ FollowCfg build_follow_cfg(const eepacc_settings* S, const eepacc_vehicle* V) {
     return F;
 }
 
+// What eepacc_route_kpis reads of a class: Tvec[0], the speed-limit and curve-speed tables as DevCfg has them
+// (EstimateRouteAndComfortBounds.m:106,108 for the curve speed), the stops and lights with their five constants, and the
+// comfort limits of the baseline controllers (meaningful where bl_mode != 0, copied as given otherwise).
+RouteCfg build_route_cfg(const eepacc_settings* S, const eepacc_vehicle*) {
+    RouteCfg R;
+    memset(&R, 0, sizeof(R));
+    R.Ts = S->Tvec[0];
+    R.n_speedLim = S->n_speedLim; R.n_curv = S->n_curv; R.n_stop = S->n_stop; R.n_TL = S->n_TL;
+    R.bl_mode = S->bl_mode;
+    for (int i = 0; i < S->n_speedLim; ++i) { R.s_speedLim[i] = S->s_speedLim[i]; R.v_speedLim[i] = S->v_speedLim[i]; }
+    for (int i = 0; i < S->n_curv; ++i) {
+        R.s_curv[i] = S->s_curv[i];
+        R.vcurv_tab[i] = S->alpha_TTL * pow(fabs(S->curvature[i]), -1.0 / 3.0);
+    }
+    for (int i = 0; i < S->n_stop; ++i) R.stopLoc[i] = S->stopLoc[i];
+    for (int i = 0; i < 4 * S->n_TL; ++i) R.TLLoc[i] = S->TLLoc[i];
+    R.stopRefDist = S->stopRefDist; R.stopRefVelSlope = S->stopRefVelSlope; R.stopVel = S->stopVel;
+    R.TLstopVel = S->TLstopVel; R.TLStopRegionSize = S->TLStopRegionSize;
+    R.bl_aLo = S->BL_a_LimLowVel; R.bl_aHi = S->BL_a_LimHighVel; R.bl_jLo = S->BL_j_LimLowVel; R.bl_jHi = S->BL_j_LimHighVel;
+    return R;
+}
+
 }  // namespace eepacc

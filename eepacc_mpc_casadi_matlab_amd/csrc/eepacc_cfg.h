@@ -9,6 +9,7 @@
 #include "eepacc_device.h"
 #include "eepacc_kpis_cfg.h"
 #include "eepacc_follow_cfg.h"
+#include "eepacc_route_cfg.h"
 #include "../../include/eepacc.h"
 
 namespace eepacc {
@@ -31,6 +32,7 @@ void preview_tables(const double* Tvec, int N, int32_t* idx, double* frac);
 // Of settings that build_cfg has accepted.
 KpiCfg build_kpi_cfg(const eepacc_settings* S, const eepacc_vehicle* V);
 FollowCfg build_follow_cfg(const eepacc_settings* S, const eepacc_vehicle* V);
+RouteCfg build_route_cfg(const eepacc_settings* S, const eepacc_vehicle* V);
 
 }  // namespace eepacc
 #endif

@@ -13,7 +13,7 @@ from typing import Any, Dict, NamedTuple, Optional
 
 import numpy as np
 
-from ._abi import (SettingsHolder, SettingsPOD, Vehicle, make_vehicle, pack_classes, OUT, OUT_N, OUT_FIELDS, KPI_N, FKPI_N, FKPI_WEIGHTS, AB_BUILD_ARGTYPES, AB_EST_ARGTYPES,
+from ._abi import (SettingsHolder, SettingsPOD, Vehicle, make_vehicle, pack_classes, OUT, OUT_N, OUT_FIELDS, KPI_N, FKPI_N, FKPI_WEIGHTS, RKPI_N, RLIM_N, ROUTE_KPIS_ARGTYPES, AB_BUILD_ARGTYPES, AB_EST_ARGTYPES,
                    FB_BUILD_ARGTYPES, BL_BUILD_ARGTYPES,
                    c_double_p, as_dptr, as_iptr)
 
@@ -65,6 +65,7 @@ def load_library() -> C.CDLL:
     lib.eepacc_postprocess.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, dp, vp]
     lib.eepacc_kpis.argtypes = [vp, C.c_int, C.c_int, dp, dp, c_double_p, dp, vp]
     lib.eepacc_follow_kpis.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, vp]
+    lib.eepacc_route_kpis.argtypes = ROUTE_KPIS_ARGTYPES
     lib.eepacc_last_iterations.argtypes = [vp, C.c_int, ip]
     lib.eepacc_fb_step.argtypes = [vp, C.c_int] + [dp] * 10 + [dp, dp, dp, dp, vp]
     lib.eepacc_run_fbmpc.argtypes = [vp, C.c_int, C.c_int] + [dp] * 5 + [dp, dp, vp]
@@ -86,7 +87,7 @@ ABI_SYMBOLS = ["eepacc_last_error", "eepacc_version", "eepacc_sizeof_settings", 
                "eepacc_ab_step", "eepacc_run_abmpc", "eepacc_fb_step", "eepacc_run_fbmpc",
                "eepacc_run_abmpc_host", "eepacc_run_fbmpc_host", "eepacc_bl_step", "eepacc_run_blmpc", "eepacc_run_blmpc_host",
                "eepacc_tv_step", "eepacc_run_tvmpc", "eepacc_run_tvmpc_host", "eepacc_postprocess", "eepacc_kpis",
-               "eepacc_follow_kpis",
+               "eepacc_follow_kpis", "eepacc_route_kpis",
                "eepacc_last_iterations", "eepacc_qp_solve_batched", "eepacc_qp_solve_batched_dual", "eepacc_qp_kkt_solve_batched",
                "eepacc_ab_qp_size", "eepacc_ab_qp_rows", "eepacc_ab_build_qp",
                "eepacc_ab_step_est", "eepacc_ab_build_qp_est", "eepacc_run_abmpc_preview",
@@ -484,6 +485,30 @@ class Engine:
         _check(self.lib.eepacc_follow_kpis(self.h, B, n_steps, FKPI_WEIGHTS[weights], traj.data_ptr(), status.data_ptr(),
                                            s_tv.data_ptr(), v_tv.data_ptr(), fkpi.data_ptr(), self._stream()))
         return fkpi
+
+    def route_kpis(self, traj, status, t_start=0.0, tol=(0.0, 0.0, 0.0), want_limits=False):
+        """eepacc_route_kpis: whether every instance obeyed its route (speed limit, curve speed, stop-sign profile, red lights:
+        what ABO/Main.m:374-433 and :486-534 draw for one run) and the comfort envelope, reduced on the device.  traj
+        [n_steps, OUT_N, B] and status [n_steps, B] as the run_* methods return them; t_start: the time of row 0 (k0 Ts for
+        the rows of a resumed launch); tol = (v_tol, a_tol, j_tol), what an excess must exceed to count as a violation.
+        Returns the device tensor [RKPI_N, B] (rows: _abi.RKPI_FIELDS, raw SI units), with want_limits the pair (table,
+        limits [n_steps, RLIM_N, B]: the four caps at every sample, rows _abi.RLIM_FIELDS); report.route_table and
+        report.route_limits are the same in numpy.  A line crossed between the last row of one call and the first row of
+        the next is seen by neither: concatenate the rows of a chunked run first."""
+        t = self.torch
+        traj = t.as_tensor(traj, dtype=t.float64, device=self.device).contiguous()
+        status = t.as_tensor(status, dtype=t.int32, device=self.device).contiguous()
+        if traj.dim() != 3 or traj.shape[1] != OUT_N or tuple(status.shape) != (traj.shape[0], traj.shape[2]):
+            raise ValueError("route_kpis needs traj [n_steps, %d, B] and status [n_steps, B]" % OUT_N)
+        n_steps, _, B = traj.shape
+        tol = np.ascontiguousarray(np.asarray(tol, dtype=np.float64).reshape(-1))
+        if tol.size != 3:
+            raise ValueError("tol needs the three entries (v_tol, a_tol, j_tol), got %d" % tol.size)
+        rkpi = t.empty((RKPI_N, B), dtype=t.float64, device=self.device)
+        limits = t.empty((n_steps, RLIM_N, B), dtype=t.float64, device=self.device) if want_limits else None
+        _check(self.lib.eepacc_route_kpis(self.h, B, n_steps, float(t_start), as_dptr(tol), traj.data_ptr(), status.data_ptr(),
+                                          rkpi.data_ptr(), _ptr(limits), self._stream()))
+        return (rkpi, limits) if want_limits else rkpi
 
     # B3 ------------------------------------------------------------------------------------
     def _qp_inputs(self, H, g, A, lba, uba, lbx, ubx, x0):

@@ -6,10 +6,14 @@ text block of Main.m for one controller.  ``kpi_table`` is the same for a batch,
 device operator eepacc_kpis (``Engine.kpis``); ``table_to_reports`` and ``summarise_table`` read such a table.
 ``follow_table`` is the specification of eepacc_follow_kpis (``Engine.follow_kpis``): the vehicle-following figures of
 Main.m:679-771 and the final cost_* of RunOpt_ABMPC.m:382-404 / RunOpt_FBMPC.m:373-397, per instance.
+``route_table`` and ``route_limits`` are the specification of eepacc_route_kpis (``Engine.route_kpis``): whether an
+instance obeyed its route -- speed limits, curve speeds, stop signs, traffic lights (what Main.m:374-433 and :486-534 draw
+for one run) -- and the comfort envelope, per instance.
 Host-side numpy only.
 """
 from __future__ import annotations
 
+import math
 from typing import Any, Dict
 
 import numpy as np
@@ -281,14 +285,198 @@ def follow_table(s, v, Fm, a, xi_v, xi_h, xi_s, xi_f, s_tv, v_tv, Ts, h_min, tau
     return T
 
 
+def _route_tables(OPT: Dict[str, Any]) -> Dict[str, Any]:
+    """What eepacc_route_kpis reads of a settings class (RouteCfg, csrc/eepacc_route_cfg.h), from OPTsettings: the route
+    tables as Python floats, the curve speeds alpha_TTL |curvature|^(-1/3) through the C library's pow, as the settings
+    translation computes them (inf where the curvature is 0)."""
+    vec = lambda x: [float(y) for y in np.asarray(x, dtype=np.float64).ravel()]
+    alpha = float(OPT["alpha_TTL"])
+    TL = np.asarray(OPT.get("TLLoc", np.zeros((0, 4))), dtype=np.float64).reshape(-1, 4)
+    return dict(s_speedLim=vec(OPT["s_speedLim"]), v_speedLim=vec(OPT["v_speedLim"]), s_curv=vec(OPT["s_curv"]),
+                vcurv_tab=[alpha * (math.pow(abs(c), -1.0 / 3.0) if c != 0.0 else math.inf) for c in vec(OPT["curvature"])],
+                stopLoc=vec(OPT.get("stopLoc", [])), TLLoc=[vec(r) for r in TL],
+                **{k: float(OPT[k]) for k in ("stopRefDist", "stopRefVelSlope", "stopVel", "TLstopVel", "TLStopRegionSize")})
+
+
+def _held_table(s, knots, vals):
+    """vals[j] on knots[j] <= s < knots[j+1], vals[0] before the first knot (and for a NaN), vals[-1] from the last on"""
+    out = np.full(s.shape, vals[0])
+    for x, y in zip(knots, vals):
+        out = np.where(s >= x, y, out)
+    return out
+
+
+def _is_red(t, TL):
+    """MATLAB's mod(t - TL(2), TL(3) + TL(4)) < TL(3); a cycle of length 0 returns its argument"""
+    x = t - TL[1]
+    mm = TL[2] + TL[3]
+    return (x if mm == 0.0 else x - math.floor(x / mm) * mm) < TL[2]
+
+
+def _route_limits(s, t, R):
+    """The four caps [4, B] of one sample: positions s [B] at the time t"""
+    v_lim = _held_table(s, R["s_speedLim"], R["v_speedLim"])
+    v_curv = _held_table(s, R["s_curv"], R["vcurv_tab"])
+    v_stop = np.full(s.shape, np.inf if R["stopLoc"] else 1e5)
+    for loc in R["stopLoc"]:
+        x = np.abs(loc - s) * R["stopRefVelSlope"] + R["stopVel"]
+        v_stop = np.where(x < v_stop, x, v_stop)
+    v_TL = np.full(s.shape, np.inf)
+    for TL in R["TLLoc"]:
+        if not _is_red(t, TL):
+            continue
+        d = TL[0] - s
+        ad = np.abs(d)
+        x = np.where(d < 0.0, ad * R["stopRefVelSlope"] + R["TLstopVel"],                                  # :133 behind the light
+                     np.where(ad < R["TLStopRegionSize"], R["TLstopVel"],                                  # :135 close in front
+                              np.abs(d - R["stopVel"]) * R["stopRefVelSlope"] + R["TLstopVel"]))           # :137 far in front
+        v_TL = np.where((ad < R["stopRefDist"]) & (x < v_TL), x, v_TL)
+    v_TL = np.where(v_TL == np.inf, 1e5, v_TL)
+    return np.stack([v_lim, v_curv, v_stop, v_TL])
+
+
+def _comfort_envelope(v, OPT, bl_mode):
+    """a_min, a_max, j_min, j_max [B] at the speeds v: EstimateRouteAndComfortBounds.m:154-172, or :173-189 with the
+    baseline limits of OPT (BL_*_Lim*) where bl_mode != 0.  A NaN speed takes the last branch."""
+    lo, mid = v < 5.0, v < 20.0
+    pick = lambda a, b, c: np.where(lo, a, np.where(mid, b, c))
+    if bl_mode:
+        aLo, aHi, jLo, jHi = [float(OPT[k]) for k in ("BL_a_LimLowVel", "BL_a_LimHighVel", "BL_j_LimLowVel", "BL_j_LimHighVel")]
+        a = pick(aLo, (4.0 * aLo - aHi) / 3.0 + (aHi - aLo) / 15.0 * v, aHi)
+        j = pick(jLo, (4.0 * jLo - jHi) / 3.0 + (jHi - jLo) / 15.0 * v, jHi)
+        return -a, a, -j, j
+    return (pick(-5.0, -5.5 + v / 10.0, -3.5), pick(4.0, 14.0 / 3.0 - 2.0 * v / 15.0, 2.0),
+            pick(-5.0, -35.0 / 6.0 + v / 6.0, -2.5), pick(5.0, 35.0 / 6.0 - v / 6.0, 2.5))
+
+
+def route_limits(s, Ts, t_start, OPT) -> np.ndarray:
+    """The per-sample output `limits` of eepacc_route_kpis, [n, RLIM_N, B] (rows: _abi.RLIM_FIELDS; [n, RLIM_N] for one
+    instance given as s [n]): the sign-posted speed limit, the curve speed, the stop-sign profile of ABO/Main.m:375-385 and
+    the red-light cap at every sample, at the positions s [n, B] and the times t_k = t_start + k Ts.  Definitions:
+    include/eepacc.h, eepacc_route_kpis; every product, sum and quotient is rounded once, as on the device."""
+    s = np.asarray(s, dtype=np.float64)
+    one = s.ndim == 1
+    s = s.reshape(s.shape[0], -1)
+    R = _route_tables(OPT)
+    Ts, t_start = float(Ts), float(t_start)
+    L = np.stack([_route_limits(s[k], t_start + k * Ts, R) for k in range(s.shape[0])])
+    return L[:, :, 0] if one else L
+
+
+def route_table(s, v, a, Ts, t_start, tol, OPT, bl_mode=0) -> np.ndarray:
+    """The route-compliance key figures of a batch, as a table [RKPI_N, B] (rows: _abi.RKPI_FIELDS; [RKPI_N] for one
+    instance given as vectors [n]) in raw SI units: the specification of eepacc_route_kpis (include/eepacc.h) in executable
+    form, numpy on the host, serial over the steps.
+
+    s, v, a: [n, B] rows of a closed-loop trajectory; Ts = Tvec[0]; t_start: the time of row 0; tol = (v_tol, a_tol,
+    j_tol); OPT: the settings of the instances' class (one class per call); bl_mode: that of the handle (the comfort
+    envelope of the baseline controllers where it is not 0).  With the caps v_lim, v_curv, v_stop, v_TL of route_limits at
+    every sample, the comfort envelope a_min .. j_max at v_k and the jerk j_k = (a[k+1] - a[k]) / Ts for k <= n-2:
+
+        vlim_excess_max  vlim_excess_index  vlim_viol_steps   max (v_k - v_lim_k); the first k that attains it (-1 if no
+                                                              sample is taken); the number of k with v_k - v_lim_k > v_tol
+        vcurv_excess_max vcurv_viol_steps                     the same against v_curv
+        vstop_excess_max vstop_viol_steps                     the same against v_stop
+        vtl_excess_max   vtl_viol_steps                       the same against v_TL over the samples with v_TL < 1e5
+        stops_passed     stop_cross_v_max                     pairs (k >= 1, stop j) with s[k-1] < stopLoc_j <= s[k]; the
+                                                              largest min(v[k-1], v[k]) over them
+        tl_passed  red_crossings  red_crossings_possible      such pairs with a light; those with it red at t_{k-1} and t_k;
+        red_cross_first_index                                 those with it red at either; the first k of the latter, else -1
+        a_over_max a_under_max j_over_max j_under_max         max (a_k - a_max), max (a_min - a_k), the same for the jerk
+        comfort_viol_steps                                    k with an acceleration excess > a_tol or a jerk excess > j_tol
+        v_min                                                 min v_k
+
+    Maxima and the minimum are kept by `>` and `<` from -inf and +inf, so the first of equal values wins and a NaN is
+    never taken and never counted; there are no sums: the device's table equals this one bit for bit."""
+    from ._abi import RKPI, RKPI_N
+    s, v, a = [np.asarray(x, dtype=np.float64) for x in (s, v, a)]
+    one = s.ndim == 1
+    s, v, a = [x.reshape(x.shape[0], -1) for x in (s, v, a)]
+    n, B = s.shape
+    Ts, t_start = float(Ts), float(t_start)
+    v_tol, a_tol, j_tol = [float(x) for x in tol]
+    R = _route_tables(OPT)
+    NINF = -np.inf
+    ex = np.full((4, B), NINF)                                        # excess maxima against v_lim, v_curv, v_stop, v_TL
+    viol = np.zeros((4, B))
+    index = np.full(B, -1.0)
+    stops, lights, red, red_poss, comfort = [np.zeros(B) for _ in range(5)]
+    red_first = np.full(B, -1.0)
+    cross_v, a_over, a_under, j_over, j_under = [np.full(B, NINF) for _ in range(5)]
+    v_min = np.full(B, np.inf)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for k in range(n):
+            t = t_start + k * Ts
+            caps = _route_limits(s[k], t, R)
+            for i in range(4):
+                e = v[k] - caps[i]
+                live = caps[i] < 1e5 if i == 3 else np.ones(B, dtype=bool)
+                take = live & (e > ex[i])
+                if i == 0:
+                    index = np.where(take, float(k), index)
+                ex[i] = np.where(take, e, ex[i])
+                viol[i] += live & (e > v_tol)
+            v_min = np.where(v[k] < v_min, v[k], v_min)
+            if k >= 1:
+                t_prev = t_start + (k - 1) * Ts
+                slow = np.where(v[k] < v[k - 1], v[k], v[k - 1])
+                for loc in R["stopLoc"]:
+                    c = (s[k - 1] < loc) & (loc <= s[k])
+                    stops += c
+                    cross_v = np.where(c & (slow > cross_v), slow, cross_v)
+                for TL in R["TLLoc"]:
+                    c = (s[k - 1] < TL[0]) & (TL[0] <= s[k])
+                    r0, r1 = _is_red(t_prev, TL), _is_red(t, TL)
+                    lights += c
+                    red += c & (r0 and r1)
+                    red_poss += c & (r0 or r1)
+                    red_first = np.where(c & (r0 or r1) & (red_first < 0.0), float(k), red_first)
+            a_min, a_max, j_min, j_max = _comfort_envelope(v[k], OPT, bl_mode)
+            eo, eu = a[k] - a_max, a_min - a[k]
+            a_over = np.where(eo > a_over, eo, a_over)
+            a_under = np.where(eu > a_under, eu, a_under)
+            bad = (eo > a_tol) | (eu > a_tol)
+            if k + 1 < n:
+                j = (a[k + 1] - a[k]) / Ts
+                eo, eu = j - j_max, j_min - j
+                j_over = np.where(eo > j_over, eo, j_over)
+                j_under = np.where(eu > j_under, eu, j_under)
+                bad = bad | (eo > j_tol) | (eu > j_tol)
+            comfort += bad
+    T = np.zeros((RKPI_N, B))
+    for i, name in enumerate(("vlim", "vcurv", "vstop", "vtl")):
+        T[RKPI[name + "_excess_max"]] = ex[i]
+        T[RKPI[name + "_viol_steps"]] = viol[i]
+    T[RKPI["vlim_excess_index"]] = index
+    T[RKPI["stops_passed"]] = stops
+    T[RKPI["stop_cross_v_max"]] = cross_v
+    T[RKPI["tl_passed"]] = lights
+    T[RKPI["red_crossings"]] = red
+    T[RKPI["red_crossings_possible"]] = red_poss
+    T[RKPI["red_cross_first_index"]] = red_first
+    T[RKPI["a_over_max"]] = a_over
+    T[RKPI["a_under_max"]] = a_under
+    T[RKPI["j_over_max"]] = j_over
+    T[RKPI["j_under_max"]] = j_under
+    T[RKPI["comfort_viol_steps"]] = comfort
+    T[RKPI["v_min"]] = v_min
+    return T[:, 0] if one else T
+
+
 def summarise_table(table, class_of) -> Dict[str, np.ndarray]:
     """Per-class mean, minimum and maximum of every row of a table: {"classes": the class ids that occur, ascending [K],
     "count" [K], "mean" / "min" / "max" [K, rows]} (rows of the three in the table's order: _abi.KPI_FIELDS for a table
-    of kpi_table / Engine.kpis, _abi.FKPI_FIELDS for one of follow_table / Engine.follow_kpis).
+    of kpi_table / Engine.kpis, _abi.FKPI_FIELDS for one of follow_table / Engine.follow_kpis, _abi.RKPI_FIELDS for one of
+    route_table / Engine.route_kpis).
 
     A table of follow_table holds +inf where an instance has no sample to take a minimum over (no lead, never closing).
     Such entries are kept as they are: the class's "max", and its "mean", are then +inf (never NaN: the fields that can
-    be infinite are +inf only), and "min" is taken over the class's other instances.  Read "lead_samples" beside them."""
+    be infinite are +inf only), and "min" is taken over the class's other instances.  Read "lead_samples" beside them.
+
+    A table of route_table holds -inf where an instance has nothing to take a maximum over (no stop line crossed, no
+    sample under a red light, one sample and so no jerk), and NaN nowhere.  Within one field the infinite entries all
+    have the same sign, so a class's "mean" is -inf there (never NaN) and its "min" too; "max" is taken over the class's
+    other instances.  Read "stops_passed", "vtl_viol_steps" and the indices (-1: none) beside them."""
     T = np.asarray(table.cpu() if hasattr(table, "cpu") else table, dtype=np.float64)
     class_of = np.asarray(class_of).reshape(-1)
     if class_of.size != T.shape[1]:

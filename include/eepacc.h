@@ -728,6 +728,82 @@ enum {
 int  eepacc_follow_kpis(eepacc_handle* h, int B, int n_steps, int weights, const double* traj, const int32_t* status,
                         const double* s_tv, const double* v_tv, double* fkpi, void* stream);
 
+/* Route-compliance key figures of a closed-loop run, per instance, on the device: whether the ego obeyed its route -- the
+ * sign-posted speed limit, the curve speed, the stop-sign profile and the red lights, which the reference shows only as
+ * pictures of one run (speed over distance, ABO/Main.m:374-433; distance over time against the red phases, :486-534) -- and
+ * whether it stayed inside the comfort envelope of EstimateRouteAndComfortBounds.m:154-189.  It judges what the plant did:
+ * the slacks xi_s, xi_f of traj say what the QP planned.  Inputs, device: traj [n_steps][EEPACC_OUT_N][B] and status
+ * [n_steps][B] as every eepacc_run_* entry point writes them; rows S, V and A of traj are read; status is not read (it is
+ * kept for symmetry with eepacc_kpis and eepacc_follow_kpis and must not be NULL).  t_start: the time of row 0, 0 for a run
+ * from eepacc_reset and k0 Ts for the rows of a resumed launch.  tol_host [3], host: v_tol, a_tol, j_tol, finite and >= 0;
+ * it may be reused when the call returns.  Outputs, device: rkpi [EEPACC_RKPI_N][B], batch-major, raw SI units; limits
+ * [n_steps][EEPACC_RLIM_N][B], or NULL: the four caps below at every sample, for redrawing the two figures per instance. */
+enum {
+    EEPACC_RLIM_V_LIM = 0,   /* the sign-posted speed limit at s_k */
+    EEPACC_RLIM_V_CURV,      /* the curve speed at s_k             */
+    EEPACC_RLIM_V_STOP,      /* the stop-sign profile at s_k       */
+    EEPACC_RLIM_V_TL,        /* the red-light cap at s_k, t_k      */
+    EEPACC_RLIM_N
+};
+/* With n = n_steps, Ts = Tvec[0] and t_k = t_start + k Ts (one rounded product, one rounded sum), the caps at sample k are
+ * these.  The table judges a run and is not bug-compatible with the planner: every deviation from the controller's own
+ * look-up, EstimateRouteAndComfortBounds.m (line numbers below; route_bounds of csrc/eepacc_stage.h restates it), is named.
+ *   v_lim   v_speedLim[j] on s_speedLim[j] <= s < s_speedLim[j+1]; v_speedLim[0] before the first knot (and for a NaN),
+ *           v_speedLim[last] from the last knot on.  Deviation: :93 takes the position s_speedLim(end) as the limit there.
+ *   v_curv  alpha_TTL |curvature[j]|^(-1/3) on the same half-open intervals of s_curv, first and last held outside.
+ *           Deviation: :107 has open intervals and falls through to the last entry for a position exactly on a knot.
+ *   v_stop  min_j (|stopLoc_j - s| stopRefVelSlope + stopVel), the profile of Main.m:375-385; 1e5 without stops.
+ *           Deviation: :116-123 applies the term within stopRefDist only and lets the last stop in range win.
+ *   v_TL    the minimum, over the lights j that are red at t_k and have |TLLoc_j - s| < stopRefDist, of the three-branch cap
+ *           of :133-139; 1e5 if there is none.  Light j is red at t when mod(t - TLLoc(j,2), TLLoc(j,3) + TLLoc(j,4)) <
+ *           TLLoc(j,3), mod being MATLAB's (a cycle of length 0 returns its argument).  Deviations: the phase is taken at the
+ *           sample's own time, not at the t_0 + i Tvec(i) of :130; of several lights the lowest cap counts, not the last.
+ *   comfort a_min, a_max, j_min, j_max at v_k from :154-172; on a handle created with bl_mode != 0 the baseline branch
+ *           :173-189 with the handle's BL_*_Lim* (a NaN speed takes the branch of v >= 20).  j_k = (a[k+1] - a[k]) / Ts, k <= n-2. */
+enum {
+    EEPACC_RKPI_VLIM_EXCESS_MAX = 0,     /* max_k (v_k - v_lim_k)                                                            */
+    EEPACC_RKPI_VLIM_EXCESS_INDEX,       /* the first k that attains it; -1.0 if no sample could be taken (all NaN)          */
+    EEPACC_RKPI_VLIM_VIOL_STEPS,         /* number of k with v_k - v_lim_k > v_tol                                           */
+    EEPACC_RKPI_VCURV_EXCESS_MAX,        /* the same against v_curv                                                          */
+    EEPACC_RKPI_VCURV_VIOL_STEPS,
+    EEPACC_RKPI_VSTOP_EXCESS_MAX,        /* the same against v_stop                                                          */
+    EEPACC_RKPI_VSTOP_VIOL_STEPS,
+    EEPACC_RKPI_VTL_EXCESS_MAX,          /* the same against v_TL, over the samples with v_TL < 1e5 only; -inf and 0 if none */
+    EEPACC_RKPI_VTL_VIOL_STEPS,
+    EEPACC_RKPI_STOPS_PASSED,            /* number of pairs (k >= 1, stop j) with s[k-1] < stopLoc_j <= s[k]                 */
+    EEPACC_RKPI_STOP_CROSS_V_MAX,        /* max over them of min(v[k-1], v[k]); -inf if there is none                        */
+    EEPACC_RKPI_TL_PASSED,               /* number of pairs (k >= 1, light j) with s[k-1] < TLLoc_j <= s[k]                  */
+    EEPACC_RKPI_RED_CROSSINGS,           /* those with the light red at t_{k-1} and at t_k                                   */
+    EEPACC_RKPI_RED_CROSSINGS_POSSIBLE,  /* those with the light red at t_{k-1} or at t_k                                    */
+    EEPACC_RKPI_RED_CROSS_FIRST_INDEX,   /* the first k of the latter; -1.0 if there is none                                 */
+    EEPACC_RKPI_A_OVER_MAX,              /* max_k (a_k - a_max(v_k))                                                         */
+    EEPACC_RKPI_A_UNDER_MAX,             /* max_k (a_min(v_k) - a_k)                                                         */
+    EEPACC_RKPI_J_OVER_MAX,              /* max_{k<=n-2} (j_k - j_max(v_k)); -inf at n = 1                                   */
+    EEPACC_RKPI_J_UNDER_MAX,             /* max_{k<=n-2} (j_min(v_k) - j_k); -inf at n = 1                                   */
+    EEPACC_RKPI_COMFORT_VIOL_STEPS,      /* number of k with an acceleration excess > a_tol or a jerk excess > j_tol         */
+    EEPACC_RKPI_V_MIN,                   /* min_k v_k (a measured speed can fall below zero)            */
+    EEPACC_RKPI_N
+};
+/* Exactness: every figure is a maximum, a minimum, a count or an index, and there are no sums.  Maxima and the minimum are
+ * kept by `>` and `<` from -inf and +inf, so where values are equal the first one wins, within a slice and across slices, and
+ * a NaN is never taken and never counted.  Every product, sum and quotient is rounded once (contraction is off for the unit).
+ * All fields, and limits, therefore equal the numpy specification report.route_table / report.route_limits bit for bit.
+ *
+ * Limit: a stop line or light crossed between the last row of one call and the first row of the next is seen by neither call,
+ * and neither is the jerk between those two rows.  A run made in chunks concatenates its rows first.
+ *
+ * Works on every kind of handle; the route tables, the five stop / light constants and the baseline limits come from a table
+ * of the operator's own with one entry per class, built at creation.  On a handle of eepacc_create_classes every instance is
+ * judged on the route of its class (eepacc_set_classes must have been called for this B).  Asynchronous on stream; reads and
+ * writes no carried state of the handle.  The geometry is that of eepacc_kpis (EEPACC_KPI_WAVES, EEPACC_KPI_MIN_SLICE): a line
+ * crossed between k-1 and k belongs to the slice that holds k, limits is written by the slice that owns the sample, and the
+ * slices are joined by one wave in slice order without atomics, so a result depends on n_steps and the inputs only, not on B,
+ * the instance's position, timing or the kind of handle.  EEPACC_EINVAL, with a message that names the argument: a NULL
+ * traj, status, tol_host or rkpi, n_steps < 1, B < 0 or B > max_batch, a tolerance that is negative or not finite, t_start not
+ * finite, a class map that is not set or was set for another B.  B = 0 returns EEPACC_OK.  Throughput: not measured. */
+int  eepacc_route_kpis(eepacc_handle* h, int B, int n_steps, double t_start, const double* tol_host,
+                       const double* traj, const int32_t* status, double* rkpi, double* limits, void* stream);
+
 /* Solver statistics of the last launch, device [B]: active-set iterations used. */
 int  eepacc_last_iterations(eepacc_handle* h, int B, int32_t* iters_host);
 
