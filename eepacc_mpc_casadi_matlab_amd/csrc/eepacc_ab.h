@@ -10,7 +10,7 @@
 namespace eepacc {
 
 // One instantiation of eepacc_ab_impl.inc each; EEPACC_AB_VARIANTS (eepacc_kernels.hip) gives namespace and switches.
-enum class AbVariant { Plain, MoveBlocking, Baseline, Ice, IceMoveBlocking, TargetVehicle, Classes, Est };
+enum class AbVariant { Plain, MoveBlocking, Baseline, Ice, IceMoveBlocking, TargetVehicle, Classes, ClassesBL, ClassesTV, Est };
 
 // The further arguments of the est kernels.  No handle has AbVariant::Est: eepacc_ab_step_est and eepacc_run_abmpc_preview run
 // a handle of AbVariant::Plain through those kernels, on the handle's own state.
@@ -18,7 +18,8 @@ struct AbSupplied { const double *s_est, *v_est, *s_tv_est; };            // dev
 struct AbPreview { const int32_t* idx; const double* frac; int n_lead; };   // device tables [N] (preview_tables, eepacc_cfg.h)
 
 // kernel variant of a handle: the baseline controllers (bl_mode) come before the ICE-map fuel term and move blocking.
-// AbVariant::Classes cannot be told from a DevCfg: a handle of eepacc_create_classes carries that choice itself.
+// AbVariant::Classes, ClassesBL and ClassesTV cannot be told from a DevCfg: a handle of eepacc_create_classes /
+// eepacc_create_classes_bl carries that choice itself (ClassesBL: bl_mode = 1 in every class, ClassesTV: bl_mode = 2).
 inline AbVariant ab_variant(const DevCfg& C) {
     if (C.bl_mode) return C.bl_mode == 2 ? AbVariant::TargetVehicle : AbVariant::Baseline;
     if (C.ab_fuel_term == 2) return C.mb_any ? AbVariant::IceMoveBlocking : AbVariant::Ice;
@@ -30,8 +31,8 @@ size_t ab_hb_doubles(int N, int B, int num_cus);
 hipError_t set_max_smem();
 int pick_chunk_steps(int n_steps, int B, int resident_waves);
 // s_tv, v_tv, a_tv_prev: null for AbVariant::TargetVehicle, whose kernels read no lead inputs.
-// AbVariant::Classes: dC is the class array DevCfg[n_classes] and class_of the device map [B] of the launch; every other
-// variant reads dC[0] alone and takes class_of = null (launch_postprocess: null selects the one-config kernel).
+// AbVariant::Classes, ClassesBL, ClassesTV: dC is the class array DevCfg[n_classes] and class_of the device map [B] of the
+// launch (ClassesTV takes null lead inputs like TargetVehicle); every other variant reads dC[0] alone and takes class_of = null (launch_postprocess: null selects the one-config kernel).
 // sup / pv: not null launches the est kernels (variant must be AbVariant::Plain) with these further arguments.
 hipError_t launch_ab_step(const DevCfg* dC, const int32_t* class_of, int N, AbVariant variant, int B, const double* s, const double* v,
                           const double* a_prev, const double* t0, const double* s_tv, const double* v_tv,

@@ -18,8 +18,8 @@ constexpr bool kBaseline = EEPACC_IMPL_BL;
 constexpr bool kIce = EEPACC_IMPL_ICE;      // ICE-map fuel term (CreateQP_AB.m:154-159): the Hessian changes every step
 constexpr bool kTargetVeh = EEPACC_IMPL_TV;     // RunOpt_TVMPC (CreateQP_TV.m): a baseline variant (kBaseline is set too)
 static_assert(!kTargetVeh || kBaseline, "the target-vehicle MPC is a variant of the baseline controller");
-constexpr bool kClasses = EEPACC_IMPL_CLS;  // a handle of eepacc_create_classes: the kernels' Cp is its array DevCfg[n_classes]
-static_assert(!kClasses || !(kMoveBlocking || kBaseline || kIce), "settings classes are built for the plain ABMPC kernels only");
+constexpr bool kClasses = EEPACC_IMPL_CLS;  // a handle of eepacc_create_classes / _classes_bl: the kernels' Cp is its array DevCfg[n_classes]
+static_assert(!kClasses || !(kMoveBlocking || kIce), "settings classes are built for the plain ABMPC kernels and the two baseline variants only");
 constexpr bool kEst = EEPACC_IMPL_EST;      // the kernels take horizon guesses as further arguments (DESIGN.md section 3.4f)
 static_assert(!kEst || !(kMoveBlocking || kBaseline || kIce || kClasses), "supplied horizon guesses are built for the plain ABMPC kernels only");
 

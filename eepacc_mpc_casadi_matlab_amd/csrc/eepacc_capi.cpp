@@ -100,7 +100,11 @@ struct eepacc_handle {
     // eepacc_run_abmpc_preview: where stage k looks into the lead trace (eepacc::preview_tables), made at the first call
     DevMem<int32_t> d_pv_idx;                // [N]
     DevMem<double> d_pv_frac;                // [N]
-    eepacc::AbVariant variant() const { return n_classes ? eepacc::AbVariant::Classes : eepacc::ab_variant(cfg); }
+    // a class handle's kernels follow from the controller its classes share (eepacc_create_classes: ABMPC, _classes_bl: bl_mode 1 or 2)
+    eepacc::AbVariant variant() const {
+        if (!n_classes) return eepacc::ab_variant(cfg);
+        return cfg.bl_mode == 0 ? eepacc::AbVariant::Classes : cfg.bl_mode == 2 ? eepacc::AbVariant::ClassesTV : eepacc::AbVariant::ClassesBL;
+    }
     const int32_t* class_map() const { return n_classes ? d_class_of.p : nullptr; }
 };
 
@@ -197,29 +201,38 @@ extern "C" int eepacc_create(eepacc_handle** out, const eepacc_settings* S, cons
 }
 
 // Every class is checked like the settings of eepacc_create, and against class 0 in what selects the kernel and the launch
-// geometry, before the device is touched.
-extern "C" int eepacc_create_classes(eepacc_handle** out, const eepacc_settings* S, const eepacc_vehicle* V,
-                                     int n_classes, int device, int max_batch) {
-    if (!out || !S || !V || max_batch < 1) return fail(EEPACC_EINVAL, "eepacc_create_classes: bad arguments");
+// geometry, before the device is touched.  The two creation entries share this body: entry names the caller in the messages,
+// baseline says which controllers its classes hold (false: ABMPC, bl_mode = 0 in every class; true: bl_mode = 1 in every class
+// or 2 in every class).
+static int create_classes_impl(const std::string& entry, bool baseline, eepacc_handle** out, const eepacc_settings* S,
+                               const eepacc_vehicle* V, int n_classes, int device, int max_batch) {
+    if (!out || !S || !V || max_batch < 1) return fail(EEPACC_EINVAL, entry + ": bad arguments");
     *out = nullptr;
     if (n_classes < 1 || n_classes > EEPACC_MAX_CLASSES)
-        return fail(EEPACC_EINVAL, "eepacc_create_classes: n_classes must be in [1, " + std::to_string(EEPACC_MAX_CLASSES) + "]");
+        return fail(EEPACC_EINVAL, entry + ": n_classes must be in [1, " + std::to_string(EEPACC_MAX_CLASSES) + "]");
     const int N = S[0].N_hor;
-    if (N < 2 || N > eepacc::kMaxN) return fail(EEPACC_EINVAL, "eepacc_create_classes: class 0: N_hor must be in [2, 63]");
+    if (N < 2 || N > eepacc::kMaxN) return fail(EEPACC_EINVAL, entry + ": class 0: N_hor must be in [2, 63]");
+    if (baseline && S[0].bl_mode != 1 && S[0].bl_mode != 2)
+        return fail(EEPACC_EINVAL, entry + ": class 0: bl_mode = " + std::to_string(S[0].bl_mode) + " must be 1 (RunOpt_BLMPC) or 2 (RunOpt_TVMPC); eepacc_create_classes takes ABMPC classes (bl_mode = 0)");
     std::vector<DevCfg> Cs((size_t)n_classes);
     std::vector<double> Hinv, Hk;
     std::vector<KpiCfg> Ks;
     std::vector<FollowCfg> Fs;
     std::vector<RouteCfg> Rs;
     for (int k = 0; k < n_classes; ++k) {
-        const std::string who = "eepacc_create_classes: class " + std::to_string(k) + ": ";
+        const std::string who = entry + ": class " + std::to_string(k) + ": ";
         if (S[k].N_hor != N)
             return fail(EEPACC_EINVAL, who + "N_hor = " + std::to_string(S[k].N_hor) + " differs from class 0 (" + std::to_string(N) + "); the classes of a handle share the horizon");
-        if (S[k].bl_mode != 0) return fail(EEPACC_ENOTSUP, who + "bl_mode != 0: the baseline and target-vehicle controllers have no class variant");
-        if (S[k].ab_fuel_term == 2) return fail(EEPACC_ENOTSUP, who + "ab_fuel_term == 2: the ICE-map fuel term has no class variant");
-        if (S[k].Mb)
-            for (int j = 0; j < N; ++j)
-                if (S[k].Mb[j] != 0) return fail(EEPACC_ENOTSUP, who + "Mb[" + std::to_string(j) + "] != 0: move blocking has no class variant");
+        if (baseline) {
+            if (S[k].bl_mode != S[0].bl_mode)
+                return fail(EEPACC_EINVAL, who + "bl_mode = " + std::to_string(S[k].bl_mode) + " differs from class 0 (" + std::to_string(S[0].bl_mode) + "); the classes of a handle share the controller");
+        } else {
+            if (S[k].bl_mode != 0) return fail(EEPACC_ENOTSUP, who + "bl_mode != 0: the baseline and target-vehicle controllers have no class variant here; eepacc_create_classes_bl takes their classes");
+            if (S[k].ab_fuel_term == 2) return fail(EEPACC_ENOTSUP, who + "ab_fuel_term == 2: the ICE-map fuel term has no class variant");
+            if (S[k].Mb)
+                for (int j = 0; j < N; ++j)
+                    if (S[k].Mb[j] != 0) return fail(EEPACC_ENOTSUP, who + "Mb[" + std::to_string(j) + "] != 0: move blocking has no class variant");
+        }
         const int rc = build_cfg_fit(&S[k], &V[k], Cs[(size_t)k], Hk);
         if (rc != EEPACC_OK) return fail(rc, who + g_err);
         for (int j = 0; j < N; ++j)
@@ -231,6 +244,15 @@ extern "C" int eepacc_create_classes(eepacc_handle** out, const eepacc_settings*
         Rs.push_back(build_route_cfg(&S[k], &V[k]));
     }
     return create_on_device(out, Cs, Hinv, Ks, Fs, Rs, true, device, max_batch);
+}
+
+extern "C" int eepacc_create_classes(eepacc_handle** out, const eepacc_settings* S, const eepacc_vehicle* V,
+                                     int n_classes, int device, int max_batch) {
+    return create_classes_impl("eepacc_create_classes", false, out, S, V, n_classes, device, max_batch);
+}
+extern "C" int eepacc_create_classes_bl(eepacc_handle** out, const eepacc_settings* S, const eepacc_vehicle* V,
+                                        int n_classes, int device, int max_batch) {
+    return create_classes_impl("eepacc_create_classes_bl", true, out, S, V, n_classes, device, max_batch);
 }
 
 extern "C" int eepacc_num_classes(const eepacc_handle* h) { return h && h->n_classes ? h->n_classes : 1; }
@@ -274,10 +296,20 @@ extern "C" int eepacc_set_classes(eepacc_handle* h, int B, const int32_t* class_
     return eepacc_reset(h);
 }
 
-// A handle of eepacc_create_classes runs the ABMPC entry points only, and only with the B its class map was set for.
-static int not_classes(const eepacc_handle* h, const char* who) {
-    if (h && h->n_classes)
+// A handle of eepacc_create_classes runs the ABMPC entry points only, one of eepacc_create_classes_bl those of its controller
+// (BLMPC under both names, or TVMPC), and both only with the B their class map was set for.
+// ab_classes_refused: the answer of a handle of eepacc_create_classes to an entry it does not run (every other handle passes);
+// not_classes: the answer of any class handle, for the entries that no class handle runs (FBMPC, the dense QP operator).
+static int ab_classes_refused(const eepacc_handle* h, const char* who) {
+    if (h && h->n_classes && h->cfg.bl_mode == 0)
         return fail(EEPACC_ENOTSUP, std::string(who) + ": a handle of eepacc_create_classes runs ABMPC only (eepacc_ab_step, eepacc_run_abmpc, eepacc_run_abmpc_host)");
+    return EEPACC_OK;
+}
+static int not_classes(const eepacc_handle* h, const char* who) {
+    if (const int rc = ab_classes_refused(h, who)) return rc;
+    if (h && h->n_classes)
+        return fail(EEPACC_ENOTSUP, std::string(who) + ": a handle of eepacc_create_classes_bl runs the entry points of its controller only (" +
+                                        (h->cfg.bl_mode == 2 ? "eepacc_tv_step, eepacc_run_tvmpc, eepacc_run_tvmpc_host)" : "eepacc_ab_step / eepacc_bl_step, eepacc_run_abmpc / eepacc_run_blmpc and their _host forms)"));
     return EEPACC_OK;
 }
 static int classes_ready(const eepacc_handle* h, const char* who, int B) {
@@ -301,8 +333,9 @@ static int need_mode(const eepacc_handle* h, int bl_mode, const char* name) {
         return fail(EEPACC_EINVAL, "this handle was not created with bl_mode = " + std::to_string(bl_mode) + " (" + name + ")");
     return EEPACC_OK;
 }
-static int need_bl(const eepacc_handle* h) { const int rc = not_classes(h, "eepacc_bl_step / eepacc_run_blmpc"); return rc ? rc : need_mode(h, 1, "RunOpt_BLMPC"); }
-static int need_tv(const eepacc_handle* h) { const int rc = not_classes(h, "eepacc_tv_step / eepacc_run_tvmpc"); return rc ? rc : need_mode(h, 2, "RunOpt_TVMPC"); }
+// (a handle of eepacc_create_classes holds ABMPC classes: not served, as before; one of eepacc_create_classes_bl answers by its mode)
+static int need_bl(const eepacc_handle* h) { const int rc = ab_classes_refused(h, "eepacc_bl_step / eepacc_run_blmpc"); return rc ? rc : need_mode(h, 1, "RunOpt_BLMPC"); }
+static int need_tv(const eepacc_handle* h) { const int rc = ab_classes_refused(h, "eepacc_tv_step / eepacc_run_tvmpc"); return rc ? rc : need_mode(h, 2, "RunOpt_TVMPC"); }
 
 // One step of the ABMPC kernels of the handle's variant.  A target-vehicle handle has no lead inputs: its kernels read none
 // and the launcher gets null pointers.
@@ -386,7 +419,7 @@ extern "C" int eepacc_run_tvmpc(eepacc_handle* h, int B, int n_steps, const doub
 // ABMPC handle (AbVariant::Plain) through the est kernels, on the handle's own state.
 static int est_handle(const eepacc_handle* h, const std::string& who) {
     if (!h) return fail(EEPACC_EINVAL, who + ": NULL handle");
-    if (h->n_classes) return fail(EEPACC_ENOTSUP, who + ": a handle of eepacc_create_classes has no variant with supplied horizon guesses");
+    if (h->n_classes) return fail(EEPACC_ENOTSUP, who + ": a handle of eepacc_create_classes / eepacc_create_classes_bl has no variant with supplied horizon guesses");
     if (h->cfg.bl_mode != 0)
         return fail(EEPACC_ENOTSUP, who + ": the handle was created with bl_mode = " + std::to_string(h->cfg.bl_mode) + "; supplied horizon guesses are built for ABMPC only, not for the baseline and target-vehicle controllers");
     for (int k = 0; k < h->cfg.N; ++k)
@@ -476,6 +509,8 @@ static const QpFamily kQpFB = {
 
 static int qp_handle(const QpFamily& F, const eepacc_handle* h, const std::string& who) {
     if (!h) return fail(EEPACC_EINVAL, who + ": NULL handle");
+    if (h->n_classes && h->cfg.bl_mode != 0)
+        return fail(EEPACC_ENOTSUP, who + ": a handle of eepacc_create_classes_bl has no single problem to build (its classes have settings of their own)");
     if (h->n_classes) return fail(EEPACC_ENOTSUP, who + F.on_classes);
     if ((h->cfg.bl_mode != 0) != F.bl_handle)
         return fail(EEPACC_ENOTSUP, who + ": the handle was created with bl_mode = " + std::to_string(h->cfg.bl_mode) + F.on_mode);
@@ -883,8 +918,8 @@ extern "C" int eepacc_fb_step(eepacc_handle* h, int B, const double* s, const do
                               const double* s_tv, const double* v_tv, const double* a_tv_prev,
                               double* out, double* s_pred, double* v_pred, int32_t* status, void* stream) {
     (void)v_prev; (void)Fm_prev; (void)Fb_prev;   // accepted and unused, as in CreateQP_FB.m:1 (inputs v_minus1, Fm_minus1, Fb_minus1)
+    if (const int rc = not_classes(h, "eepacc_fb_step")) return rc;      // (any class handle, a target-vehicle one included: not supported)
     if (const int rc = not_tv(h, "eepacc_fb_step")) return rc;
-    if (const int rc = not_classes(h, "eepacc_fb_step")) return rc;
     if (B < 0 || B > h->max_batch) return fail(EEPACC_EINVAL, "B exceeds max_batch of the handle");
     if (B == 0) return EEPACC_OK;
     if (!s || !v || !a_prev || !t0 || !s_tv || !v_tv || !a_tv_prev || !out || !status)
@@ -964,8 +999,8 @@ extern "C" int eepacc_fb_build_qp(eepacc_handle* h, int B, const double* s, cons
 extern "C" int eepacc_run_fbmpc(eepacc_handle* h, int B, int n_steps, const double* s0, const double* v0,
                                 const double* a_minus1, const double* s_tv, const double* v_tv,
                                 double* traj, int32_t* status, void* stream) {
+    if (const int rc = not_classes(h, "eepacc_run_fbmpc")) return rc;      // (any class handle, a target-vehicle one included: not supported)
     if (const int rc = not_tv(h, "eepacc_run_fbmpc")) return rc;
-    if (const int rc = not_classes(h, "eepacc_run_fbmpc")) return rc;
     if (B < 0 || B > h->max_batch || n_steps < 0) return fail(EEPACC_EINVAL, "eepacc_run_fbmpc: bad B / n_steps");
     if (B == 0 || n_steps == 0) return EEPACC_OK;
     if (!s0 || !v0 || !a_minus1 || !s_tv || !v_tv || !traj || !status)

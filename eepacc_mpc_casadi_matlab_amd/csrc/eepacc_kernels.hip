@@ -32,6 +32,9 @@
 //          the small ICE kernel 18 % of its throughput at N = 30 even where the handle has no Mb.
 //   cls    settings classes (eepacc_create_classes): the plain kernels with the DevCfg bound per instance, through the
 //          class map that its kernels alone take as one more argument
+//   blcls  the baseline controller with settings classes (eepacc_create_classes_bl, bl_mode = 1 in every class): blc with the
+//          DevCfg bound per instance as in cls
+//   tvcls  the target-vehicle MPC with settings classes (eepacc_create_classes_bl, bl_mode = 2 in every class): tvc likewise
 //   est    horizon guesses from the caller (eepacc_ab_step_est, eepacc_run_abmpc_preview): the plain kernels with the three
 //          supplied arrays (step) or the preview tables (closed loop) as further arguments of its kernels alone; no handle
 //          has this variant, its two entry points run a plain handle
@@ -43,6 +46,8 @@
     X(IceMoveBlocking, icemb, true, false, false, true, false, false, __VA_ARGS__)     \
     X(TargetVehicle, tvc, false, true, true, false, false, false, __VA_ARGS__)         \
     X(Classes, cls, false, false, false, false, true, false, __VA_ARGS__)              \
+    X(ClassesBL, blcls, false, true, false, false, true, false, __VA_ARGS__)           \
+    X(ClassesTV, tvcls, false, true, true, false, true, false, __VA_ARGS__)            \
     X(Est, est, false, false, false, false, false, true, __VA_ARGS__)
 
 // an instantiation reads its switches from the list by the name of its namespace
@@ -76,6 +81,12 @@ EEPACC_AB_VARIANTS(EEPACC_AB_SWITCHES)
 #undef EEPACC_IMPL_NS
 #define EEPACC_IMPL_NS cls
 #define EEPACC_IMPL_CLASS_MAP       // the preprocessor's copy of the list's CLS switch (eepacc_ab_impl.inc checks that they agree)
+#include "eepacc_ab_impl.inc"
+#undef EEPACC_IMPL_NS
+#define EEPACC_IMPL_NS blcls
+#include "eepacc_ab_impl.inc"
+#undef EEPACC_IMPL_NS
+#define EEPACC_IMPL_NS tvcls
 #include "eepacc_ab_impl.inc"
 #undef EEPACC_IMPL_CLASS_MAP
 #undef EEPACC_IMPL_NS

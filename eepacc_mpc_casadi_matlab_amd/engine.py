@@ -48,6 +48,7 @@ def load_library() -> C.CDLL:
         raise EepaccError("ctypes mirror of include/eepacc.h is out of date (struct size mismatch)")
     lib.eepacc_create.argtypes = [C.POINTER(vp), C.POINTER(SettingsPOD), C.POINTER(Vehicle), C.c_int, C.c_int]
     lib.eepacc_create_classes.argtypes = [C.POINTER(vp), C.POINTER(SettingsPOD), C.POINTER(Vehicle), C.c_int, C.c_int, C.c_int]
+    lib.eepacc_create_classes_bl.argtypes = lib.eepacc_create_classes.argtypes
     lib.eepacc_set_classes.argtypes = [vp, C.c_int, ip]
     lib.eepacc_num_classes.argtypes = [vp]
     lib.eepacc_destroy.argtypes = [vp]
@@ -83,7 +84,7 @@ def load_library() -> C.CDLL:
 
 
 ABI_SYMBOLS = ["eepacc_last_error", "eepacc_version", "eepacc_sizeof_settings", "eepacc_sizeof_vehicle", "eepacc_create", "eepacc_destroy", "eepacc_reset",
-               "eepacc_create_classes", "eepacc_set_classes", "eepacc_num_classes",
+               "eepacc_create_classes", "eepacc_create_classes_bl", "eepacc_set_classes", "eepacc_num_classes",
                "eepacc_ab_step", "eepacc_run_abmpc", "eepacc_fb_step", "eepacc_run_fbmpc",
                "eepacc_run_abmpc_host", "eepacc_run_fbmpc_host", "eepacc_bl_step", "eepacc_run_blmpc", "eepacc_run_blmpc_host",
                "eepacc_tv_step", "eepacc_run_tvmpc", "eepacc_run_tvmpc_host", "eepacc_postprocess", "eepacc_kpis",
@@ -177,15 +178,21 @@ class Engine:
 
     @classmethod
     def from_classes(cls, OPT_list, V_list, device: int = 0, max_batch: int = 4096) -> "Engine":
-        """eepacc_create_classes: one engine for instances of several settings classes (ABMPC only).  OPT_list[k], V_list[k]
-        are the settings and the vehicle of class k; N_hor and Tvec must agree.  set_classes() says which class every
-        instance of the next launches belongs to; ab_step, run_abmpc, run_abmpc_host and postprocess then work as on an
-        ordinary engine, every other controller is refused."""
+        """eepacc_create_classes / eepacc_create_classes_bl: one engine for instances of several settings classes.
+        OPT_list[k], V_list[k] are the settings and the vehicle of class k; N_hor and Tvec must agree.  With ABMPC settings
+        (bl_mode 0 or absent) set_classes() says which class every instance of the next launches belongs to; ab_step,
+        run_abmpc, run_abmpc_host, postprocess and the key figures then work as on an ordinary engine, every other controller
+        is refused.  Where every class has the same bl_mode 1 (settings.Settings_BL) or 2 (Settings_TV) the engine is one of
+        eepacc_create_classes_bl and serves run_blmpc / ab_step / run_blmpc_host, or tv_step / run_tvmpc / run_tvmpc_host,
+        in the same way; classes that disagree in bl_mode raise ValueError."""
+        if len(OPT_list) != len(V_list) or len(OPT_list) < 1:
+            raise ValueError("from_classes needs one vehicle per settings class and at least one class")
+        modes = sorted({int(o.get("bl_mode", 0)) for o in OPT_list})
+        if len(modes) > 1:
+            raise ValueError("from_classes: the classes disagree in bl_mode (%s); an engine has one controller" % modes)
         import torch
         if not torch.cuda.is_available():
             raise EepaccError("no GPU visible: the EEPACC engine has no CPU path")
-        if len(OPT_list) != len(V_list) or len(OPT_list) < 1:
-            raise ValueError("from_classes needs one vehicle per settings class and at least one class")
         self = cls.__new__(cls)
         self.torch = torch
         self.lib = load_library()
@@ -195,7 +202,8 @@ class Engine:
         self.device = torch.device("cuda", device)
         self.max_batch = int(max_batch)
         h = C.c_void_p()
-        _check(self.lib.eepacc_create_classes(C.byref(h), S, self.veh, len(OPT_list), device, max_batch))
+        create = self.lib.eepacc_create_classes_bl if modes[0] in (1, 2) else self.lib.eepacc_create_classes
+        _check(create(C.byref(h), S, self.veh, len(OPT_list), device, max_batch))
         self.h = h
         return self
 
@@ -751,6 +759,58 @@ def generate_lead_and_run(OPTsettings: Dict[str, Any], V: Optional[Dict[str, flo
     run = {"ab": ego.run_abmpc, "fb": ego.run_fbmpc, "bl": ego.run_blmpc}[kind]
     traj, status = run(full(s_init, OPTsettings["s_init"]), full(v_init, OPTsettings["v_init"]),
                        full(a_minus1, OPTsettings["a_minus1"]), s_tv, v_tv)
+    return traj, status, s_tv, v_tv
+
+
+def generate_lead_and_run_mix(mix: Dict[str, Any], kind: str = "ab", engines=None, device: int = 0):
+    """ABO/Main.m:82-89 for a whole use-case mix (scenarios.make_use_case_mix): a target-vehicle class engine generates every
+    instance's lead along the route of its own class in one launch, TVlength[class_of] is subtracted on the device (:88) and
+    the traces are handed to the ABMPC (kind "ab") or BLMPC (kind "bl") class engine as device tensors, with no host copy in
+    between.  Instances of a use case that brings its own lead (8, 9, 10) or has IncludeTV false keep the rows the mix gave
+    them; every other instance follows the generated vehicle, which starts from its class's TVinitDist, TVinitVel, a_minus1.
+
+    kind "bl" takes a mix made with controller="bl", or applies settings.Settings_BL to the classes of an ABMPC mix.
+    engines = (tv_engine, ego_engine) reuses class handles (their class maps are set here).  The controllers share the sample
+    grid, so a class whose TV_Ts differs from the Tvec[0] of its ABMPC settings is refused, not resampled.
+    Returns (traj, status, s_tv, v_tv): the ego closed loop and the [n_steps, B] lead traces it was fed."""
+    from .settings import Settings_BL
+    if kind not in ("ab", "bl"):
+        raise ValueError("kind must be 'ab' or 'bl'")
+    OPTs, Vs, class_of = list(mix["OPT"]), list(mix["V"]), np.asarray(mix["class_of"], dtype=np.int32)
+    for k, o in enumerate(OPTs):
+        if mix["TV"][k] is None:
+            raise ValueError("class %d has no target-vehicle settings: its TV_Ts differed from Tvec[0] when the mix was made "
+                             "(ABO/Main.m:82-89 takes the lead trace sample for sample); refused" % k)
+        # against the ABMPC grid the class's target-vehicle view was made on, as generate_lead_and_run does for every kind
+        # (the Tvec of a Settings_BL class is BL_Ts)
+        Ts = float(np.asarray(mix["TV"][k]["Tvec"]).ravel()[0])
+        if float(o["TV_Ts"]) != Ts:
+            raise ValueError("class %d: TV_Ts = %g differs from Tvec[0] = %g: the lead trace would have to be resampled "
+                             "(ABO/Main.m:82-89 takes it sample for sample); refused" % (k, float(o["TV_Ts"]), Ts))
+    modes = {int(o.get("bl_mode", 0)) for o in OPTs}
+    if kind == "bl" and modes == {0}:
+        OPTs = [Settings_BL(o) for o in OPTs]
+    elif modes != ({1} if kind == "bl" else {0}):
+        raise ValueError("kind %r does not fit the classes of the mix (bl_mode %s)" % (kind, sorted(modes)))
+    TVs = list(mix["TV"])
+    B, n_steps = int(class_of.size), int(mix["n_steps"])
+    if engines is None:
+        tv = Engine.from_classes(TVs, Vs, device=device, max_batch=B)
+        ego = Engine.from_classes(OPTs, Vs, device=device, max_batch=B)
+    else:
+        tv, ego = engines
+    tv.set_classes(class_of)
+    ego.set_classes(class_of)
+    t = tv.torch
+    f64 = dict(dtype=t.float64, device=tv.device)
+    per = lambda key: t.as_tensor(np.array([float(TVs[k][key]) for k in class_of]), **f64)
+    lead, _ = tv.run_tvmpc(per("TVinitDist"), per("TVinitVel"), per("a_minus1"), n_steps)
+    generated = np.array([int(o.get("useCaseNum", 0)) not in (8, 9, 10) and bool(o.get("IncludeTV", True)) for o in OPTs])
+    gen = t.as_tensor(generated[class_of], device=tv.device)[None, :]
+    s_tv = t.where(gen, lead[:, OUT["s"], :] - per("TVlength")[None, :], t.as_tensor(mix["s_tv"], **f64)).contiguous()      # Main.m:88
+    v_tv = t.where(gen, lead[:, OUT["v"], :], t.as_tensor(mix["v_tv"], **f64)).contiguous()
+    run = ego.run_blmpc if kind == "bl" else ego.run_abmpc
+    traj, status = run(mix["s0"], mix["v0"], mix["a_minus1"], s_tv, v_tv)
     return traj, status, s_tv, v_tv
 
 

@@ -49,16 +49,22 @@ def make_s1(B: int, golden: dict, s_tv: np.ndarray, v_tv: np.ndarray, Ts: float 
                 a_tv_prev=np.where(k > 0, (vtv - vtv_prev) / Ts, 0.0), k=k)
 
 
-def make_use_case_mix(cases, per_case: int, tree: str, N_hor: int, n_steps=None, argonne_lead=None):
+def make_use_case_mix(cases, per_case: int, tree: str, N_hor: int, n_steps=None, argonne_lead=None, controller: str = "ab"):
     """Several GetUseCase scenarios as the settings classes of one launch (Engine.from_classes): class k is cases[k], every
     class has per_case instances, interleaved (class_of = 0, 1, 2, ..., 0, 1, 2, ...).  Each instance starts from its use
     case's own s_init, v_init, a_minus1 and follows its use case's lead: the recorded one of 8 and 9 (argonne_lead =
     (t, v_mph), the two columns of the measurement file), the cut-in of 10, none otherwise (s_tv = inf, v_tv = 0,
     Main.m:77-80).  n_steps defaults to the shortest simulated time of the chosen cases (t_sim / Ts + 1).
+    controller "ab": OPT holds the settings themselves (ABMPC); "bl": settings.Settings_BL of every case, the classes of a
+    baseline engine.
 
     Returns a dict: OPT (settings per class), V (vehicle per class), class_of [B], s0, v0, a_minus1 [B],
-    s_tv, v_tv [n_steps][B], n_steps."""
-    from .settings import Settings, SetVehicleParameters, default_opt
+    s_tv, v_tv [n_steps][B], n_steps, and TV: settings.Settings_TV per class (the classes of the engine that generates a lead
+    along every route, engine.generate_lead_and_run_mix) with the class's TVlength, TVinitDist, TVinitVel; None for a class
+    whose TV_Ts differs from its Tvec[0], which has no such view."""
+    from .settings import Settings, SetVehicleParameters, Settings_BL, Settings_TV, default_opt
+    if controller not in ("ab", "bl"):
+        raise ValueError("controller must be 'ab' or 'bl'")
     cases = [int(c) for c in cases]
     if not cases or per_case < 1:
         raise ValueError("make_use_case_mix needs at least one use case and per_case >= 1")
@@ -84,8 +90,9 @@ def make_use_case_mix(cases, per_case: int, tree: str, N_hor: int, n_steps=None,
             s_tv[:, class_of == k] = np.asarray(o["s_tv"], dtype=np.float64)[:n_steps, None]
             v_tv[:, class_of == k] = np.asarray(o["v_tv"], dtype=np.float64)[:n_steps, None]
     pick = lambda key: np.array([float(OPTs[k][key]) for k in class_of])
-    return dict(OPT=OPTs, V=Vs, class_of=class_of, s0=pick("s_init"), v0=pick("v_init"), a_minus1=pick("a_minus1"),
-                s_tv=s_tv, v_tv=v_tv, n_steps=n_steps)
+    TV = [Settings_TV(o) if float(o["TV_Ts"]) == float(np.asarray(o["Tvec"]).ravel()[0]) else None for o in OPTs]
+    return dict(OPT=[Settings_BL(o) for o in OPTs] if controller == "bl" else OPTs, V=Vs, class_of=class_of, s0=pick("s_init"),
+                v0=pick("v_init"), a_minus1=pick("a_minus1"), s_tv=s_tv, v_tv=v_tv, n_steps=n_steps, TV=TV)
 
 
 def preview_tables(Tvec):

@@ -176,7 +176,8 @@ void eepacc_destroy(eepacc_handle* h);
  * run in one launch.  Every class is validated like the settings of eepacc_create, before the device is touched.  What
  * selects the kernel and the launch geometry must agree: N_hor and every entry of Tvec equal those of class 0
  * (EEPACC_EINVAL otherwise), and no class may have move blocking (Mb all zero or NULL), ab_fuel_term = 2 or bl_mode != 0
- * (EEPACC_ENOTSUP); the message names the class and the field.  Everything else may differ per class: the route tables,
+ * (EEPACC_ENOTSUP; eepacc_create_classes_bl below takes the classes of the baseline and target-vehicle controllers); the
+ * message names the class and the field.  Everything else may differ per class: the route tables,
  * ab_route_rows, ab_fuel_term 0 or 1, W_AB, tau_min, h_min, s_goal, the estimator modes and time constants,
  * N_integratePlant, state_bound_tol, b_fifthOrder and the whole vehicle.  n_classes must be in [1, EEPACC_MAX_CLASSES].
  *
@@ -188,6 +189,30 @@ void eepacc_destroy(eepacc_handle* h);
 #define EEPACC_MAX_CLASSES 4096
 int  eepacc_create_classes(eepacc_handle** out, const eepacc_settings* S, const eepacc_vehicle* V,
                            int n_classes, int device, int max_batch);
+
+/* Settings classes for the baseline controller (bl_mode = 1, RunOpt_BLMPC) and the target-vehicle controller (bl_mode = 2,
+ * RunOpt_TVMPC): the yardstick of the twelve use cases in one BLMPC launch, and a lead vehicle per route (ABO/Main.m:82-89)
+ * in one TVMPC launch.  eepacc_create_classes keeps refusing bl_mode != 0; this entry takes those classes.  Every class is
+ * validated like the settings of eepacc_create before the device is touched, the message naming the class and the field.
+ * bl_mode of class 0 must be 1 or 2 (0: EEPACC_EINVAL, use eepacc_create_classes) and every class must have class 0's
+ * bl_mode, N_hor and Tvec (EEPACC_EINVAL otherwise); n_classes must be in [1, EEPACC_MAX_CLASSES].  Everything else may
+ * differ per class: the route tables, W_BL, BL_a_Lim*, BL_j_Lim*, bl_lp_eps, bl_prox_iter, tau_min, h_min, s_goal,
+ * paramEstSetting, TVestSetting and the time constants, N_integratePlant, state_bound_tol, b_fifthOrder and the whole
+ * vehicle.
+ *
+ * A handle with bl_mode = 1 runs eepacc_ab_step / eepacc_bl_step, eepacc_run_abmpc / eepacc_run_blmpc (also resumed in
+ * chunks) and their _host forms; one with bl_mode = 2 runs eepacc_tv_step, eepacc_run_tvmpc and eepacc_run_tvmpc_host.  Both
+ * run eepacc_postprocess, eepacc_kpis, eepacc_follow_kpis, eepacc_route_kpis (each instance with the tables of its class),
+ * eepacc_set_classes, eepacc_num_classes, eepacc_reset, eepacc_synchronize and eepacc_last_iterations, and a launch needs
+ * the class map of its B as on a handle of eepacc_create_classes.  The results of an instance are bit for bit those of a
+ * handle created by eepacc_create from the settings of its class.
+ *
+ * Refused with EEPACC_ENOTSUP: FBMPC, the dense QP operator, every _qp_size / _qp_rows / _build_qp, the _est entries and
+ * eepacc_run_abmpc_preview.  A bl_mode = 2 handle on an ABMPC / BLMPC entry and a bl_mode = 1 handle on a TVMPC entry answer
+ * EEPACC_EINVAL, as the handles of eepacc_create with those modes do.  A handle of eepacc_create_classes (ABMPC classes)
+ * on eepacc_bl_* / eepacc_tv_* stays EEPACC_ENOTSUP. */
+int  eepacc_create_classes_bl(eepacc_handle** out, const eepacc_settings* S, const eepacc_vehicle* V,
+                              int n_classes, int device, int max_batch);
 
 /* class_of_host [B], host, values in [0, n_classes): the class of instance i in the launches that follow.  The map is
  * copied to the device (after waiting for the device's pending work) and the carried loop state is reset like

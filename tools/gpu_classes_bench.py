@@ -1,4 +1,6 @@
-"""Closed-loop ABMPC throughput of a handle with settings classes (eepacc_create_classes, kernels `cls`) in ONE process.
+"""Closed-loop throughput of a handle with settings classes in ONE process: ABMPC (eepacc_create_classes, kernels `cls`,
+--kind ab, the default), the baseline controller (eepacc_create_classes_bl with bl_mode = 1, kernels `blcls`, --kind bl) or the
+target-vehicle controller (bl_mode = 2, kernels `tvcls`, --kind tv).
 
 (1) mixed:     the twelve GetUseCase scenarios of the ORIG tree, --batch instances in all (341 or 342 per use case at 4096),
                as ONE launch on a class handle, against the same instances as twelve launches on twelve ordinary handles,
@@ -12,6 +14,12 @@ is the median QP steps/s, the spread (max - min) / median of the same side.  The
 for bit before any timing.
 
   python tools/gpu_classes_bench.py --out profiles/classes_bench.json
+  python tools/gpu_classes_bench.py --kind bl --out profiles/classes_bench.json      # adds the key "bl" to the file, "tv" likewise; a run keeps the other kinds
+
+--kind bl runs Settings_BL of the same instances and workloads through run_blmpc (one class: `blcls` against `blc`); --kind tv
+runs Settings_TV of them through run_tvmpc, which takes no lead (one class: `tvcls` against `tvc`), every vehicle starting at
+its class's TVinitDist with the initial speeds described below.  A mixed launch counts as a gain only where it exceeds the
+twelve launches by more than the spreads printed beside it; the one-class ratio is reported without a bar.
 
 The use-case instances start from their use case's own initial state; without a lead of their own (all but 8, 9, 10)
 they differ inside a use case by the initial speed, spread over 0.5 .. 1 of the use case's speed limit at s = 0.  The
@@ -48,6 +56,7 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--kind", choices=("ab", "bl", "tv"), default="ab")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     sys.path.insert(0, ROOT)
@@ -55,7 +64,7 @@ def main():
     import torch
     from eepacc_mpc_casadi_matlab_amd.engine import Engine
     from eepacc_mpc_casadi_matlab_amd.scenarios import make_s2, make_use_case_mix
-    from eepacc_mpc_casadi_matlab_amd.settings import Settings, SetVehicleParameters
+    from eepacc_mpc_casadi_matlab_amd.settings import Settings, SetVehicleParameters, Settings_BL, Settings_TV
 
     if not torch.cuda.is_available():
         raise SystemExit("no GPU: nothing is measured without one")
@@ -88,6 +97,13 @@ def main():
 
     results = []
 
+    def launch(eng, p, rows, resume, out=None):
+        """One closed-loop launch of the controller of --kind over the rows of p's lead (tv: as many steps, no lead)."""
+        if a.kind == "tv":
+            return eng.run_tvmpc(p["s0"], p["v0"], p["am1"], rows.stop - rows.start, resume=resume, out=out)
+        run = eng.run_blmpc if a.kind == "bl" else eng.run_abmpc
+        return run(p["s0"], p["v0"], p["am1"], p["stv"][rows], p["vtv"][rows], resume=resume, out=out)
+
     # (1) the twelve use cases ------------------------------------------------------------------------------------------
     rec = np.load(os.path.join(golden, "argonne_61505019_lead.npz"))
     cases = list(range(1, 13))
@@ -106,30 +122,35 @@ def main():
         else:
             v0[cls == k] = frac[cls == k] * float(o["v_speedLim"][0])
     s0, am1 = mix["s0"][:B], mix["a_minus1"][:B]
+    OPTs = {"ab": mix["OPT"], "bl": [Settings_BL(o) for o in mix["OPT"]], "tv": mix["TV"]}[a.kind]
+    if a.kind == "tv":                                          # the generated vehicles: every one from its class's TVinitDist
+        s0 = np.array([float(OPTs[k]["TVinitDist"]) for k in cls])
+        v0 = 0.8 * frac * np.array([float(OPTs[k]["v_speedLim"][0]) for k in cls])
     stv, vtv = dev(s_tv), dev(v_tv)
     idx = [np.nonzero(cls == k)[0] for k in range(12)]
-    mixed = Engine.from_classes(mix["OPT"], mix["V"], device=0, max_batch=B)
+    mixed = Engine.from_classes(OPTs, mix["V"], device=0, max_batch=B)
     mixed.set_classes(cls)
-    singles = [Engine(o, v, device=0, max_batch=len(i)) for o, v, i in zip(mix["OPT"], mix["V"], idx)]
+    whole = dict(s0=s0, v0=v0, am1=am1, stv=stv, vtv=vtv)
+    singles = [Engine(o, v, device=0, max_batch=len(i)) for o, v, i in zip(OPTs, mix["V"], idx)]
     part = [dict(s0=s0[i], v0=v0[i], am1=am1[i], stv=stv[:, i].contiguous(), vtv=vtv[:, i].contiguous(),
                  traj=torch.empty((K, 12, len(i)), dtype=torch.float64, device="cuda"),
                  stat=torch.empty((K, len(i)), dtype=torch.int32, device="cuda"), dev_idx=torch.as_tensor(i, device="cuda")) for i in idx]
 
     def run_mixed():
-        mixed.run_abmpc(s0, v0, am1, stv[:W], vtv[:W])
+        launch(mixed, whole, slice(0, W), False)
         mixed.synchronize()
         t0 = time.perf_counter()
-        mixed.run_abmpc(s0, v0, am1, stv[W:], vtv[W:], resume=True, out=(traj, stat))
+        launch(mixed, whole, slice(W, W + K), True, out=(traj, stat))
         mixed.synchronize()
         return time.perf_counter() - t0
 
     def run_twelve():
         for e, p in zip(singles, part):
-            e.run_abmpc(p["s0"], p["v0"], p["am1"], p["stv"][:W], p["vtv"][:W])
+            launch(e, p, slice(0, W), False)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for e, p in zip(singles, part):                         # twelve launches back to back on one stream
-            e.run_abmpc(p["s0"], p["v0"], p["am1"], p["stv"][W:], p["vtv"][W:], resume=True, out=(p["traj"], p["stat"]))
+            launch(e, p, slice(W, W + K), True, out=(p["traj"], p["stat"]))
         for e in singles:
             e.synchronize()
         dt = time.perf_counter() - t0
@@ -140,27 +161,40 @@ def main():
     results.append(compare("twelve_use_cases", dict(mixed_one_launch=run_mixed, twelve_launches=run_twelve), B))
     del mixed, singles, part
 
-    # (2) one class through the class kernels, bench.py's ABMPC workload ------------------------------------------------
+    # (2) one class through the class kernels, bench.py's ABMPC workload (bl, tv: that controller's view of its settings) ------
     lead = np.load(os.path.join(golden, "lead_TO01_EAD.npz"))["V_TO_2Hz"]
     OPT, V = Settings(tree="ABO", N_hor=N), SetVehicleParameters("ABO")
+    OPT = {"ab": lambda o: o, "bl": Settings_BL, "tv": Settings_TV}[a.kind](OPT)
     sc = make_s2(B, W + K, lead)
     stv, vtv = dev(sc["s_tv"]), dev(sc["v_tv"])
+    whole = dict(s0=np.full(B, float(OPT["TVinitDist"])) if a.kind == "tv" else sc["s0"], v0=sc["v0"], am1=sc["a_minus1"], stv=stv, vtv=vtv)
     one = Engine.from_classes([OPT], [V], device=0, max_batch=B)
     one.set_classes(np.zeros(B, dtype=np.int32))
     plain = Engine(OPT, V, device=0, max_batch=B)
 
     def runner(eng):
         def run():
-            eng.run_abmpc(sc["s0"], sc["v0"], sc["a_minus1"], stv[:W], vtv[:W])
+            launch(eng, whole, slice(0, W), False)
             eng.synchronize()
             t0 = time.perf_counter()
-            eng.run_abmpc(sc["s0"], sc["v0"], sc["a_minus1"], stv[W:], vtv[W:], resume=True, out=(traj, stat))
+            launch(eng, whole, slice(W, W + K), True, out=(traj, stat))
             eng.synchronize()
             return time.perf_counter() - t0
         return run
 
     results.append(compare("one_class_bench_workload", dict(class_kernels=runner(one), ordinary_handle=runner(plain)), B))
     out = dict(source_hash=source_hash(), device=torch.cuda.get_device_name(0), results=results)
+    # one file holds the three kinds: ABMPC at the top level, as before, the others under the keys "bl" and "tv"; a run
+    # replaces its own kind and keeps what the file has of the others
+    have = {}
+    if a.out and os.path.exists(a.out):
+        with open(a.out) as f:
+            have = json.load(f)
+    if a.kind == "ab":
+        out.update({k: have[k] for k in ("bl", "tv") if k in have})
+    else:
+        have[a.kind] = out
+        out = have
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
