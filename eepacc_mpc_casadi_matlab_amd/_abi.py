@@ -63,6 +63,9 @@ AB_EST_ARGTYPES = {
     "eepacc_ab_build_qp_est": [C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p] * 3 + [C.c_void_p] * 5 + [C.c_void_p],
     "eepacc_run_abmpc_preview": [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_void_p] * 2 + [C.c_void_p],
 }
+# the baseline controller's counterparts (a handle with bl_mode = 1): arguments and order are those of the AB entries
+BL_EST_ARGTYPES = {name.replace("eepacc_ab_", "eepacc_bl_").replace("abmpc", "blmpc"): list(argtypes)
+                   for name, argtypes in AB_EST_ARGTYPES.items()}
 
 # enum EEPACC_FB_ROW_*: the row types of eepacc_fb_qp_rows, ascending in the order of the rows within a stage
 FB_ROW_TYPES = ["s", "v", "fm", "fb", "xi_v", "xi_h", "xi_s", "xi_f", "blocked_fm", "blocked_fb", "tm_min", "tm_max",

@@ -10,10 +10,11 @@
 namespace eepacc {
 
 // One instantiation of eepacc_ab_impl.inc each; EEPACC_AB_VARIANTS (eepacc_kernels.hip) gives namespace and switches.
-enum class AbVariant { Plain, MoveBlocking, Baseline, Ice, IceMoveBlocking, TargetVehicle, Classes, ClassesBL, ClassesTV, Est };
+enum class AbVariant { Plain, MoveBlocking, Baseline, Ice, IceMoveBlocking, TargetVehicle, Classes, ClassesBL, ClassesTV, Est, BlEst };
 
-// The further arguments of the est kernels.  No handle has AbVariant::Est: eepacc_ab_step_est and eepacc_run_abmpc_preview run
-// a handle of AbVariant::Plain through those kernels, on the handle's own state.
+// The further arguments of the est and blest kernels.  No handle has AbVariant::Est or BlEst: eepacc_ab_step_est and
+// eepacc_run_abmpc_preview run a handle of AbVariant::Plain through the est kernels, eepacc_bl_step_est and
+// eepacc_run_blmpc_preview one of AbVariant::Baseline through the blest kernels, on the handle's own state.
 struct AbSupplied { const double *s_est, *v_est, *s_tv_est; };            // device arrays [N+1][B]; s_est and v_est both or neither
 struct AbPreview { const int32_t* idx; const double* frac; int n_lead; };   // device tables [N] (preview_tables, eepacc_cfg.h)
 
@@ -33,7 +34,8 @@ int pick_chunk_steps(int n_steps, int B, int resident_waves);
 // s_tv, v_tv, a_tv_prev: null for AbVariant::TargetVehicle, whose kernels read no lead inputs.
 // AbVariant::Classes, ClassesBL, ClassesTV: dC is the class array DevCfg[n_classes] and class_of the device map [B] of the
 // launch (ClassesTV takes null lead inputs like TargetVehicle); every other variant reads dC[0] alone and takes class_of = null (launch_postprocess: null selects the one-config kernel).
-// sup / pv: not null launches the est kernels (variant must be AbVariant::Plain) with these further arguments.
+// sup / pv: not null launches the est kernels (variant AbVariant::Plain) or the blest kernels (AbVariant::Baseline) with
+// these further arguments; no other variant has such kernels.
 hipError_t launch_ab_step(const DevCfg* dC, const int32_t* class_of, int N, AbVariant variant, int B, const double* s, const double* v,
                           const double* a_prev, const double* t0, const double* s_tv, const double* v_tv,
                           const double* a_tv_prev, unsigned long long* codes, double* out, double* s_pred, double* v_pred,

@@ -21,7 +21,7 @@ static_assert(!kTargetVeh || kBaseline, "the target-vehicle MPC is a variant of 
 constexpr bool kClasses = EEPACC_IMPL_CLS;  // a handle of eepacc_create_classes / _classes_bl: the kernels' Cp is its array DevCfg[n_classes]
 static_assert(!kClasses || !(kMoveBlocking || kIce), "settings classes are built for the plain ABMPC kernels and the two baseline variants only");
 constexpr bool kEst = EEPACC_IMPL_EST;      // the kernels take horizon guesses as further arguments (DESIGN.md section 3.4f)
-static_assert(!kEst || !(kMoveBlocking || kBaseline || kIce || kClasses), "supplied horizon guesses are built for the plain ABMPC kernels only");
+static_assert(!kEst || !(kMoveBlocking || kTargetVeh || kIce || kClasses), "supplied horizon guesses are built for the plain ABMPC kernels and the baseline controller (blest) only");
 
 
 #undef PTIC
@@ -1345,6 +1345,9 @@ __device__ __forceinline__ void ab_step(const DevCfg& C, WaveMem<MMAX, NS>& M, d
         } else exists = (lane == N) && (t == R_SAFE1 || t == R_SAFE2);      // (CreateQP_TV.m:288-292: no terminal rows; skipped above)
         // a supplied guess may say "no lead" (+inf) at a stage where the carried working set, made on another guess, holds a
         // lead row: such a row does not exist, so that its code is dropped below instead of entering the solve with an infinite bound
+        // (blest: SAFE1 and SAFE2 belong to the one slack group; a group whose pivot is dropped here is back at its bound, the
+        // state every shifted code of lane 0 is left in already, and the violation search, slide_limit and the LP's proximal
+        // re-solves read L.valid, so none of them sees the row)
         if constexpr (kEst) { if ((t == R_SAFE1 || t == R_SAFE2 || t == R_HWP) && !(b[t] < kInf)) exists = false; }
         if (exists && lane == 0 && row_ga(t) == 0.0) {
             // stage-0 rows without an a-component are constants: fold into slack bounds

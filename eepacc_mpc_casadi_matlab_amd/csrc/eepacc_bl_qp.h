@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "eepacc_device.h"
+#include "eepacc_ab.h"
 #include "../../include/eepacc.h"
 
 namespace eepacc {
@@ -23,5 +24,11 @@ inline int bl_qp_num_rows(const DevCfg& C) { return bl_rows_per_stage(C.bl_mode)
 hipError_t launch_bl_qp(const DevCfg* cfg, int N, int nC, int B, const double* s, const double* v, const double* a_prev,
                         const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
                         double* H, double* g, double* A, double* lba, double* uba, hipStream_t stream);
+
+// the same on supplied guesses (eepacc_bl_qp_est.hip, eepacc_bl_build_qp_est): cfg has bl_mode = 1
+hipError_t launch_bl_qp_est(const DevCfg* cfg, int N, int nC, int B, const double* s, const double* v, const double* a_prev,
+                            const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                            double* H, double* g, double* A, double* lba, double* uba, hipStream_t stream,
+                            const AbSupplied& sup);
 
 }  // namespace eepacc

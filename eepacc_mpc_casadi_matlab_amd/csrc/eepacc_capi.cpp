@@ -415,13 +415,23 @@ extern "C" int eepacc_run_tvmpc(eepacc_handle* h, int B, int n_steps, const doub
     return rc != EEPACC_OK ? rc : ab_run_impl(h, "eepacc_run_tvmpc", "eepacc_run_tvmpc: bad B / n_steps", B, n_steps, s0, v0, a_minus1, nullptr, nullptr, traj, status, stream);
 }
 
-// ---- horizon guesses from the caller: eepacc_ab_step_est, eepacc_ab_build_qp_est, eepacc_run_abmpc_preview.  They run a plain
-// ABMPC handle (AbVariant::Plain) through the est kernels, on the handle's own state.
-static int est_handle(const eepacc_handle* h, const std::string& who) {
+// ---- horizon guesses from the caller: eepacc_ab_step_est, eepacc_ab_build_qp_est, eepacc_run_abmpc_preview run a plain ABMPC
+// handle (AbVariant::Plain) through the est kernels, eepacc_bl_step_est, eepacc_bl_build_qp_est, eepacc_run_blmpc_preview a
+// handle of the baseline controller (bl_mode = 1, AbVariant::Baseline) through the blest kernels: on the handle's own state.
+// bl: the entry belongs to the baseline controller.
+static int est_handle(const eepacc_handle* h, const std::string& who, bool bl = false) {
     if (!h) return fail(EEPACC_EINVAL, who + ": NULL handle");
     if (h->n_classes) return fail(EEPACC_ENOTSUP, who + ": a handle of eepacc_create_classes / eepacc_create_classes_bl has no variant with supplied horizon guesses");
-    if (h->cfg.bl_mode != 0)
-        return fail(EEPACC_ENOTSUP, who + ": the handle was created with bl_mode = " + std::to_string(h->cfg.bl_mode) + "; supplied horizon guesses are built for ABMPC only, not for the baseline and target-vehicle controllers");
+    const std::string mode = ": the handle was created with bl_mode = " + std::to_string(h->cfg.bl_mode);
+    if (h->cfg.bl_mode == 2)
+        return fail(EEPACC_ENOTSUP, who + mode + " (RunOpt_TVMPC); the target-vehicle controller has no lead and hands its bounds a zero speed estimate, so supplied horizon guesses are not built for it");
+    if (bl) {
+        if (h->cfg.bl_mode == 0)
+            return fail(EEPACC_ENOTSUP, who + mode + "; eepacc_ab_step_est, eepacc_ab_build_qp_est and eepacc_run_abmpc_preview take the supplied horizon guesses of an ABMPC handle");
+        return EEPACC_OK;       // (the baseline kernels have neither move blocking nor the ICE-map fuel term: ab_variant)
+    }
+    if (h->cfg.bl_mode == 1)
+        return fail(EEPACC_ENOTSUP, who + mode + " (RunOpt_BLMPC); eepacc_bl_step_est, eepacc_bl_build_qp_est and eepacc_run_blmpc_preview take the supplied horizon guesses of the baseline controller");
     for (int k = 0; k < h->cfg.N; ++k)
         if (h->cfg.mb_mask[k]) return fail(EEPACC_ENOTSUP, who + ": Mb[" + std::to_string(k) + "] != 0: move blocking has no variant with supplied horizon guesses");
     if (h->cfg.ab_fuel_term == 2) return fail(EEPACC_ENOTSUP, who + ": ab_fuel_term == 2: the ICE-map fuel term has no variant with supplied horizon guesses");
@@ -433,25 +443,35 @@ static int est_pair(const std::string& who, const double* s_est, const double* v
     return EEPACC_OK;
 }
 
-extern "C" int eepacc_ab_step_est(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
-                                  const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
-                                  const double* s_est, const double* v_est, const double* s_tv_est,
-                                  double* out, double* s_pred, double* v_pred, int32_t* status, void* stream) {
-    const std::string who = "eepacc_ab_step_est";
-    if (const int rc = est_handle(h, who)) return rc;
+static int step_est_impl(bool bl, const std::string& who, eepacc_handle* h, int B, const double* s, const double* v,
+                         const double* a_prev, const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                         const double* s_est, const double* v_est, const double* s_tv_est,
+                         double* out, double* s_pred, double* v_pred, int32_t* status, void* stream) {
+    if (const int rc = est_handle(h, who, bl)) return rc;
     if (B < 0 || B > h->max_batch)
         return fail(EEPACC_EINVAL, who + ": B = " + std::to_string(B) + " is outside [0, max_batch = " + std::to_string(h->max_batch) + "]");
     if (B == 0) return EEPACC_OK;
     if (const int rc = est_pair(who, s_est, v_est)) return rc;
     const eepacc::AbSupplied sup{s_est, v_est, s_tv_est};
-    return ab_step_impl(h, "eepacc_ab_step_est", B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, out, s_pred, v_pred, status, stream, &sup);
+    return ab_step_impl(h, who.c_str(), B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, out, s_pred, v_pred, status, stream, &sup);
+}
+extern "C" int eepacc_ab_step_est(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
+                                  const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                                  const double* s_est, const double* v_est, const double* s_tv_est,
+                                  double* out, double* s_pred, double* v_pred, int32_t* status, void* stream) {
+    return step_est_impl(false, "eepacc_ab_step_est", h, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, s_est, v_est, s_tv_est, out, s_pred, v_pred, status, stream);
+}
+extern "C" int eepacc_bl_step_est(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
+                                  const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                                  const double* s_est, const double* v_est, const double* s_tv_est,
+                                  double* out, double* s_pred, double* v_pred, int32_t* status, void* stream) {
+    return step_est_impl(true, "eepacc_bl_step_est", h, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, s_est, v_est, s_tv_est, out, s_pred, v_pred, status, stream);
 }
 
-extern "C" int eepacc_run_abmpc_preview(eepacc_handle* h, int B, int n_steps, int n_lead, const double* s0, const double* v0,
-                                        const double* a_minus1, const double* s_tv, const double* v_tv, double* traj,
-                                        int32_t* status, void* stream) {
-    const std::string who = "eepacc_run_abmpc_preview";
-    if (const int rc = est_handle(h, who)) return rc;
+static int run_preview_impl(bool bl, const std::string& who, eepacc_handle* h, int B, int n_steps, int n_lead, const double* s0,
+                            const double* v0, const double* a_minus1, const double* s_tv, const double* v_tv, double* traj,
+                            int32_t* status, void* stream) {
+    if (const int rc = est_handle(h, who, bl)) return rc;
     if (B < 0 || B > h->max_batch || n_steps < 0)
         return fail(EEPACC_EINVAL, who + ": B = " + std::to_string(B) + " must be in [0, max_batch = " + std::to_string(h->max_batch) + "] and n_steps = " + std::to_string(n_steps) + " not negative");
     if (n_lead < n_steps)
@@ -469,7 +489,17 @@ extern "C" int eepacc_run_abmpc_preview(eepacc_handle* h, int B, int n_steps, in
         HIPCHK(hipMemcpy(h->d_pv_idx, idx.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice));
     }
     const eepacc::AbPreview pv{h->d_pv_idx, h->d_pv_frac, n_lead};
-    return ab_run_impl(h, "eepacc_run_abmpc_preview", "eepacc_run_abmpc_preview: bad B / n_steps", B, n_steps, s0, v0, a_minus1, s_tv, v_tv, traj, status, stream, &pv);
+    return ab_run_impl(h, who.c_str(), (who + ": bad B / n_steps").c_str(), B, n_steps, s0, v0, a_minus1, s_tv, v_tv, traj, status, stream, &pv);
+}
+extern "C" int eepacc_run_abmpc_preview(eepacc_handle* h, int B, int n_steps, int n_lead, const double* s0, const double* v0,
+                                        const double* a_minus1, const double* s_tv, const double* v_tv, double* traj,
+                                        int32_t* status, void* stream) {
+    return run_preview_impl(false, "eepacc_run_abmpc_preview", h, B, n_steps, n_lead, s0, v0, a_minus1, s_tv, v_tv, traj, status, stream);
+}
+extern "C" int eepacc_run_blmpc_preview(eepacc_handle* h, int B, int n_steps, int n_lead, const double* s0, const double* v0,
+                                        const double* a_minus1, const double* s_tv, const double* v_tv, double* traj,
+                                        int32_t* status, void* stream) {
+    return run_preview_impl(true, "eepacc_run_blmpc_preview", h, B, n_steps, n_lead, s0, v0, a_minus1, s_tv, v_tv, traj, status, stream);
 }
 
 // ---- the condensed QP of a step as data: eepacc_{ab,fb,bl}_qp_size, _qp_rows, _build_qp.  What the three families do alike is
@@ -581,12 +611,11 @@ extern "C" int eepacc_ab_build_qp(eepacc_handle* h, int B, const double* s, cons
     return EEPACC_OK;
 }
 
-extern "C" int eepacc_ab_build_qp_est(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
-                                      const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
-                                      const double* s_est, const double* v_est, const double* s_tv_est,
-                                      double* H, double* g, double* A, double* lba, double* uba, void* stream) {
-    const std::string who = "eepacc_ab_build_qp_est";
-    if (const int rc = est_handle(h, who)) return rc;
+static int build_qp_est_impl(bool bl, const std::string& who, eepacc_handle* h, int B, const double* s, const double* v,
+                             const double* a_prev, const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                             const double* s_est, const double* v_est, const double* s_tv_est,
+                             double* H, double* g, double* A, double* lba, double* uba, void* stream) {
+    if (const int rc = est_handle(h, who, bl)) return rc;
     if (B < 0 || B > h->max_batch)
         return fail(EEPACC_EINVAL, who + ": B = " + std::to_string(B) + " is outside [0, max_batch = " + std::to_string(h->max_batch) + "]");
     if (B == 0) return EEPACC_OK;
@@ -598,9 +627,25 @@ extern "C" int eepacc_ab_build_qp_est(eepacc_handle* h, int B, const double* s, 
     if (const int rc = est_pair(who, s_est, v_est)) return rc;
     const eepacc::AbSupplied sup{s_est, v_est, s_tv_est};
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(eepacc::launch_ab_build(h->d_cfg, h->cfg.N, eepacc::ab_qp_num_rows(h->cfg), B, s, v, a_prev, t0, s_tv, v_tv,
-                                   a_tv_prev, H, g, A, lba, uba, (hipStream_t)stream, &sup));
+    if (bl)
+        HIPCHK(eepacc::launch_bl_qp_est(h->d_cfg, h->cfg.N, eepacc::bl_qp_num_rows(h->cfg), B, s, v, a_prev, t0, s_tv, v_tv,
+                                        a_tv_prev, H, g, A, lba, uba, (hipStream_t)stream, sup));
+    else
+        HIPCHK(eepacc::launch_ab_build(h->d_cfg, h->cfg.N, eepacc::ab_qp_num_rows(h->cfg), B, s, v, a_prev, t0, s_tv, v_tv,
+                                       a_tv_prev, H, g, A, lba, uba, (hipStream_t)stream, &sup));
     return EEPACC_OK;
+}
+extern "C" int eepacc_ab_build_qp_est(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
+                                      const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                                      const double* s_est, const double* v_est, const double* s_tv_est,
+                                      double* H, double* g, double* A, double* lba, double* uba, void* stream) {
+    return build_qp_est_impl(false, "eepacc_ab_build_qp_est", h, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, s_est, v_est, s_tv_est, H, g, A, lba, uba, stream);
+}
+extern "C" int eepacc_bl_build_qp_est(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
+                                      const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                                      const double* s_est, const double* v_est, const double* s_tv_est,
+                                      double* H, double* g, double* A, double* lba, double* uba, void* stream) {
+    return build_qp_est_impl(true, "eepacc_bl_build_qp_est", h, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, s_est, v_est, s_tv_est, H, g, A, lba, uba, stream);
 }
 
 extern "C" int eepacc_bl_qp_size(const eepacc_handle* h, int* nV, int* nC) { return qp_size_impl(kQpBL, h, nV, nC); }

@@ -38,6 +38,8 @@
 //   est    horizon guesses from the caller (eepacc_ab_step_est, eepacc_run_abmpc_preview): the plain kernels with the three
 //          supplied arrays (step) or the preview tables (closed loop) as further arguments of its kernels alone; no handle
 //          has this variant, its two entry points run a plain handle
+//   blest  the same for the baseline controller (eepacc_bl_step_est, eepacc_run_blmpc_preview): blc with est's further
+//          arguments; no handle has this variant either, its entry points run a bl_mode = 1 handle
 #define EEPACC_AB_VARIANTS(X, ...)                                                     \
     X(Plain, nomb, false, false, false, false, false, false, __VA_ARGS__)              \
     X(MoveBlocking, withmb, true, false, false, false, false, false, __VA_ARGS__)      \
@@ -48,7 +50,8 @@
     X(Classes, cls, false, false, false, false, true, false, __VA_ARGS__)              \
     X(ClassesBL, blcls, false, true, false, false, true, false, __VA_ARGS__)           \
     X(ClassesTV, tvcls, false, true, true, false, true, false, __VA_ARGS__)            \
-    X(Est, est, false, false, false, false, false, true, __VA_ARGS__)
+    X(Est, est, false, false, false, false, false, true, __VA_ARGS__)                  \
+    X(BlEst, blest, false, true, false, false, false, true, __VA_ARGS__)
 
 // an instantiation reads its switches from the list by the name of its namespace
 namespace eepacc { namespace ab_switch {
@@ -93,6 +96,9 @@ EEPACC_AB_VARIANTS(EEPACC_AB_SWITCHES)
 #define EEPACC_IMPL_NS est
 #include "eepacc_ab_impl.inc"
 #undef EEPACC_IMPL_NS
+#define EEPACC_IMPL_NS blest
+#include "eepacc_ab_impl.inc"
+#undef EEPACC_IMPL_NS
 
 // ----------------------------------------------------------------------------------------------
 // host-side launchers used by eepacc_capi.cpp
@@ -124,8 +130,9 @@ size_t ab_smem_bytes(int N) {
 }
 
 // the kernel of the handle's variant, small or large horizon; a kernel with one parameter more than the launch has
-// arguments is a class kernel (eepacc_ab_impl.inc, cfg_of) and gets the class map as its last.  The est kernels have
-// three more: no handle has that variant, and launch_est below gives them theirs.
+// arguments is a class kernel (eepacc_ab_impl.inc, cfg_of) and gets the class map as its last.  The est and blest kernels
+// have three more: no handle has those variants, and launch_est below gives them theirs (est for a plain handle, blest for
+// one of the baseline controller).
 template <class... P, class... A>
 static void launch_ab(void (*kernel)(P...), int grid, int block, size_t smem, hipStream_t stream, const int32_t* class_of, A... args) {
     if constexpr (sizeof...(P) == sizeof...(A) + 1) hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), smem, stream, args..., class_of);
@@ -169,8 +176,11 @@ hipError_t launch_ab_step(const DevCfg* dC, const int32_t* class_of, int N, AbVa
                           unsigned long long* codes, double* out, double* s_pred, double* v_pred,
                           int32_t* status, int32_t* iters, hipStream_t stream, const AbSupplied* sup) {
     if (sup) {
-        if (N > kNSSmall) launch_est(est::step_kernel<kMMaxLarge, kNSLarge, kWpbLarge>(), (B + kWpbLarge - 1) / kWpbLarge, kWpbLarge, N, stream, dC, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, codes, out, s_pred, v_pred, status, iters, sup->s_est, sup->v_est, sup->s_tv_est);
-        else launch_est(est::step_kernel<kMMaxSmall, kNSSmall, 4>(), (B + 3) / 4, 4, N, stream, dC, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, codes, out, s_pred, v_pred, status, iters, sup->s_est, sup->v_est, sup->s_tv_est);
+        const bool bl = variant == AbVariant::Baseline;
+#define EEPACC_EST_STEP(NSP, MM, NSV, WPB) launch_est(NSP::step_kernel<MM, NSV, WPB>(), (B + WPB - 1) / WPB, WPB, N, stream, dC, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, codes, out, s_pred, v_pred, status, iters, sup->s_est, sup->v_est, sup->s_tv_est)
+        if (N > kNSSmall) { if (bl) EEPACC_EST_STEP(blest, kMMaxLarge, kNSLarge, kWpbLarge); else EEPACC_EST_STEP(est, kMMaxLarge, kNSLarge, kWpbLarge); }
+        else { if (bl) EEPACC_EST_STEP(blest, kMMaxSmall, kNSSmall, 4); else EEPACC_EST_STEP(est, kMMaxSmall, kNSSmall, 4); }
+#undef EEPACC_EST_STEP
         return hipGetLastError();
     }
     if (N > kNSSmall) EEPACC_LAUNCH(step_kernel, kMMaxLarge, kNSLarge, kWpbLarge, (B + kWpbLarge - 1) / kWpbLarge, dC, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, codes, out, s_pred, v_pred, status, iters);
@@ -191,8 +201,11 @@ hipError_t launch_run_abmpc(const DevCfg* dC, const int32_t* class_of, int N, Ab
                                num_cus * (large ? 1 : kBlocksSmall), stream, ul);
     if (e != hipSuccess) return e;
     if (pv) {
-        if (large) launch_est(est::run_kernel<kMMaxLarge, kNSLarge, kWpbLarge>(), ul.grid, kWpbLarge, N, stream, dC, B, k_start, n_steps, s0, v0, a_m1, s_tv, v_tv, carry, codes, traj, status, iters_total, work_counter, done, kChunkSteps, err_word, ul.spin_limit, pv->idx, pv->frac, pv->n_lead);
-        else launch_est(est::run_kernel<kMMaxSmall, kNSSmall, 4>(), ul.grid, 4, N, stream, dC, B, k_start, n_steps, s0, v0, a_m1, s_tv, v_tv, carry, codes, traj, status, iters_total, work_counter, done, kChunkSteps, err_word, ul.spin_limit, pv->idx, pv->frac, pv->n_lead);
+        const bool bl = variant == AbVariant::Baseline;
+#define EEPACC_EST_RUN(NSP, MM, NSV, WPB) launch_est(NSP::run_kernel<MM, NSV, WPB>(), ul.grid, WPB, N, stream, dC, B, k_start, n_steps, s0, v0, a_m1, s_tv, v_tv, carry, codes, traj, status, iters_total, work_counter, done, kChunkSteps, err_word, ul.spin_limit, pv->idx, pv->frac, pv->n_lead)
+        if (large) { if (bl) EEPACC_EST_RUN(blest, kMMaxLarge, kNSLarge, kWpbLarge); else EEPACC_EST_RUN(est, kMMaxLarge, kNSLarge, kWpbLarge); }
+        else { if (bl) EEPACC_EST_RUN(blest, kMMaxSmall, kNSSmall, 4); else EEPACC_EST_RUN(est, kMMaxSmall, kNSSmall, 4); }
+#undef EEPACC_EST_RUN
         return hipGetLastError();
     }
     if (large)

@@ -2,7 +2,7 @@
 // in the layout the dense QP operator reads): k_ab_build (eepacc_ab_build.hip), k_fb_qp (eepacc_fb_qp.hip) and k_bl_qp
 // (eepacc_bl_qp.hip).  One workgroup of BT threads per instance; stage quantities go into LDS once; the dynamic LDS holds the
 // sensitivity tables [N+1][N|1] and the row list.  What is here is what the three kernels do alike: the ego estimate (and the
-// guesses a caller supplies in its place, which k_ab_build alone takes so far), the row
+// guesses a caller supplies in its place, which k_ab_build_est and k_bl_qp_est take), the row
 // list, the walks over H, the bounds and A, and for the two double-integrator controllers (AB, BL) the row type, the position
 // sensitivities and the entry of A.  The entry formulas differ per controller and stay in the units, which hand them to the
 // writers as lambdas; everything inlines.

@@ -13,7 +13,7 @@ from typing import Any, Dict, NamedTuple, Optional
 
 import numpy as np
 
-from ._abi import (SettingsHolder, SettingsPOD, Vehicle, make_vehicle, pack_classes, OUT, OUT_N, OUT_FIELDS, KPI_N, FKPI_N, FKPI_WEIGHTS, RKPI_N, RLIM_N, ROUTE_KPIS_ARGTYPES, AB_BUILD_ARGTYPES, AB_EST_ARGTYPES,
+from ._abi import (SettingsHolder, SettingsPOD, Vehicle, make_vehicle, pack_classes, OUT, OUT_N, OUT_FIELDS, KPI_N, FKPI_N, FKPI_WEIGHTS, RKPI_N, RLIM_N, ROUTE_KPIS_ARGTYPES, AB_BUILD_ARGTYPES, AB_EST_ARGTYPES, BL_EST_ARGTYPES,
                    FB_BUILD_ARGTYPES, BL_BUILD_ARGTYPES,
                    c_double_p, as_dptr, as_iptr)
 
@@ -75,7 +75,7 @@ def load_library() -> C.CDLL:
     lib.eepacc_qp_solve_batched_dual.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [dp] * 8 + [dp, dp] + [dp] * 3 + [dp] * 5 + [vp]
     lib.eepacc_qp_kkt_solve_batched.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int] + [dp] * 2 + [dp] * 2 + [dp] * 3 + [dp] * 3 + [dp, vp]
     for name, argtypes in (list(AB_BUILD_ARGTYPES.items()) + list(FB_BUILD_ARGTYPES.items()) + list(BL_BUILD_ARGTYPES.items())
-                           + list(AB_EST_ARGTYPES.items())):
+                           + list(AB_EST_ARGTYPES.items()) + list(BL_EST_ARGTYPES.items())):
         getattr(lib, name).argtypes = argtypes
     lib.eepacc_synchronize.argtypes = [vp, vp]
     lib.eepacc_build_flags.restype = C.c_char_p
@@ -94,6 +94,7 @@ ABI_SYMBOLS = ["eepacc_last_error", "eepacc_version", "eepacc_sizeof_settings", 
                "eepacc_ab_step_est", "eepacc_ab_build_qp_est", "eepacc_run_abmpc_preview",
                "eepacc_fb_qp_size", "eepacc_fb_qp_rows", "eepacc_fb_build_qp",
                "eepacc_bl_qp_size", "eepacc_bl_qp_rows", "eepacc_bl_build_qp",
+               "eepacc_bl_step_est", "eepacc_bl_build_qp_est", "eepacc_run_blmpc_preview",
                "eepacc_synchronize", "eepacc_build_flags"]
 
 
@@ -324,30 +325,54 @@ class Engine:
         """The three supplied arrays [N+1, B] (None: the engine's estimator) as device tensors."""
         return [None if x is None else self._d(x, (self.N + 1) * B) for x in (s_est, v_est, s_tv_est)]
 
+    def _est_check(self, s, s_est, v_est, s_tv_est):
+        """What the bl_ methods refuse before anything reaches the device: half a pair, an array that is not [N+1, B]."""
+        if (s_est is None) != (v_est is None):
+            raise ValueError("s_est and v_est are given together or both None")
+        shape = lambda x: tuple(x.shape) if hasattr(x, "shape") else tuple(np.shape(x))        # numpy, torch (any device), lists
+        B = int(np.prod(shape(s), dtype=np.int64))
+        for name, x in (("s_est", s_est), ("v_est", v_est), ("s_tv_est", s_tv_est)):
+            if x is not None and shape(x) != (self.N + 1, B):
+                raise ValueError("%s has shape %s, expected (N_hor + 1, B) = (%d, %d)" % (name, shape(x), self.N + 1, B))
+
+    def _step_est(self, entry, ins, est, want_pred):
+        B = int(self.torch.as_tensor(ins[0]).numel())
+        est = self._est(B, *est)
+        fn = lambda h, B_, *rest: entry(h, B_, *rest[:7], *[_ptr(x) for x in est], *rest[7:])
+        return self._step(fn, ins, want_pred)
+
+    def _build_qp_est(self, entry, size, ins, est):
+        B = int(self.torch.as_tensor(ins[0]).numel())
+        ins = [self._d(x, B) for x in ins]
+        est = self._est(B, *est)
+        ptrs, qp = self._qp_outputs(B, *size())
+        _check(entry(self.h, B, *[x.data_ptr() for x in ins], *[_ptr(x) for x in est], *ptrs, self._stream()))
+        return qp
+
+    def _run_preview(self, entry, s0, v0, a_minus1, s_tv, v_tv, n_steps, resume, out):
+        t = self.torch
+        lead = [t.as_tensor(x, dtype=t.float64, device=self.device).contiguous() for x in (s_tv, v_tv)]
+        if lead[0].dim() != 2 or lead[0].shape != lead[1].shape:
+            raise ValueError("s_tv and v_tv are [n_lead, B] both")
+        n_lead, B = lead[0].shape
+        n_steps = n_lead if n_steps is None else int(n_steps)
+        fn = lambda h, B_, n, *rest: entry(h, B_, n, n_lead, *rest)
+        return self._run(fn, (s0, v0, a_minus1), lead, n_steps, resume, out, lead_rows=False)
+
     def ab_step_est(self, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, s_est=None, v_est=None, s_tv_est=None,
                     want_pred: bool = True):
         """eepacc_ab_step_est: ab_step with the horizon guesses supplied, the contract of the reference's Simulink block
         ACCMPC(..., s_est, v_est, s_tv_est, ...).  s_est, v_est (together or both None) and s_tv_est are [N+1, B] as
         EstimateVehicleTrajectory returns them (the layout of the predictions ab_step returns); None keeps the engine's
         estimator.  Reads and writes the engine state ab_step does; results as ab_step."""
-        t = self.torch
-        B = int(t.as_tensor(s).numel())
-        est = self._est(B, s_est, v_est, s_tv_est)
-        fn = lambda h, B_, *rest: self.lib.eepacc_ab_step_est(h, B_, *rest[:7], *[_ptr(x) for x in est], *rest[7:])
-        return self._step(fn, (s, v, a_prev, t0, s_tv, v_tv, a_tv_prev), want_pred)
+        return self._step_est(self.lib.eepacc_ab_step_est, (s, v, a_prev, t0, s_tv, v_tv, a_tv_prev), (s_est, v_est, s_tv_est), want_pred)
 
     def ab_build_qp_est(self, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, s_est=None, v_est=None, s_tv_est=None) -> AbQp:
         """eepacc_ab_build_qp_est: the condensed QP of the step ab_step_est solves, CreateQP_AB on the supplied guesses.
         Returns AbQp as ab_build_qp does; ab_qp_size and ab_qp_rows describe it.  qp_sens.ab_lead_gradient differentiates
         its solution with respect to s_tv_est."""
-        t = self.torch
-        B = int(t.as_tensor(s).numel())
-        ins = [self._d(x, B) for x in (s, v, a_prev, t0, s_tv, v_tv, a_tv_prev)]
-        est = self._est(B, s_est, v_est, s_tv_est)
-        ptrs, qp = self._qp_outputs(B, *self.ab_qp_size())
-        _check(self.lib.eepacc_ab_build_qp_est(self.h, B, *[x.data_ptr() for x in ins], *[_ptr(x) for x in est], *ptrs,
-                                               self._stream()))
-        return AbQp(*qp)
+        return AbQp(*self._build_qp_est(self.lib.eepacc_ab_build_qp_est, self.ab_qp_size, (s, v, a_prev, t0, s_tv, v_tv, a_tv_prev),
+                                        (s_est, v_est, s_tv_est)))
 
     def run_abmpc_preview(self, s0, v0, a_minus1, s_tv, v_tv, n_steps=None, resume: bool = False, out=None):
         """eepacc_run_abmpc_preview: run_abmpc whose steps take the lead's horizon guess from the lead trace itself
@@ -355,12 +380,30 @@ class Engine:
         n_lead >= n_steps (default n_lead): the rows of the launch's steps, then the future the last steps look into; past
         the last row the lead is carried on at its last speed.  Returns traj [n_steps, OUT_N, B], status [n_steps, B];
         resume / out as run_abmpc (a resumed launch passes the continued rows)."""
-        t = self.torch
-        lead = [t.as_tensor(x, dtype=t.float64, device=self.device).contiguous() for x in (s_tv, v_tv)]
-        n_lead, B = lead[0].shape
-        n_steps = n_lead if n_steps is None else int(n_steps)
-        fn = lambda h, B_, n, *rest: self.lib.eepacc_run_abmpc_preview(h, B_, n, n_lead, *rest)
-        return self._run(fn, (s0, v0, a_minus1), lead, n_steps, resume, out, lead_rows=False)
+        return self._run_preview(self.lib.eepacc_run_abmpc_preview, s0, v0, a_minus1, s_tv, v_tv, n_steps, resume, out)
+
+    # the baseline controller's three (an engine made from settings.Settings_BL; refused on any other)
+    def bl_step_est(self, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, s_est=None, v_est=None, s_tv_est=None,
+                    want_pred: bool = True):
+        """eepacc_bl_step_est: the baseline controller's step (eepacc_bl_step) with the horizon guesses supplied, the contract
+        of CreateQP_BL(..., s_est, v_est, s_tv_est, ...).  Arguments and results as ab_step_est; None keeps the engine's
+        estimator, and with all three None the step is eepacc_bl_step's bit for bit.  Shares the engine state of ab_step /
+        run_blmpc on this engine."""
+        self._est_check(s, s_est, v_est, s_tv_est)
+        return self._step_est(self.lib.eepacc_bl_step_est, (s, v, a_prev, t0, s_tv, v_tv, a_tv_prev), (s_est, v_est, s_tv_est), want_pred)
+
+    def bl_build_qp_est(self, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, s_est=None, v_est=None, s_tv_est=None) -> BlQp:
+        """eepacc_bl_build_qp_est: the condensed QP of the step bl_step_est solves, CreateQP_BL on the supplied guesses.
+        Returns BlQp as bl_build_qp does; bl_qp_size and bl_qp_rows describe it.  A linear program with the reference's
+        weights: compare objective values, not points."""
+        self._est_check(s, s_est, v_est, s_tv_est)
+        return BlQp(*self._build_qp_est(self.lib.eepacc_bl_build_qp_est, self.bl_qp_size, (s, v, a_prev, t0, s_tv, v_tv, a_tv_prev),
+                                        (s_est, v_est, s_tv_est)))
+
+    def run_blmpc_preview(self, s0, v0, a_minus1, s_tv, v_tv, n_steps=None, resume: bool = False, out=None):
+        """eepacc_run_blmpc_preview: run_blmpc whose steps take the lead's horizon guess from the lead trace itself, by the
+        rule of run_abmpc_preview (scenarios.lead_preview); arguments and results as there."""
+        return self._run_preview(self.lib.eepacc_run_blmpc_preview, s0, v0, a_minus1, s_tv, v_tv, n_steps, resume, out)
 
     # B1 ------------------------------------------------------------------------------------
     def run_abmpc(self, s0, v0, a_minus1, s_tv, v_tv, resume: bool = False, out=None, by_name_bl: bool = False):
@@ -724,7 +767,8 @@ def RunOpt_TVMPC(OPTsettings: Dict[str, Any], V: Optional[Dict[str, float]] = No
 
 
 def generate_lead_and_run(OPTsettings: Dict[str, Any], V: Optional[Dict[str, float]] = None, kind: str = "ab", batch: int = 1,
-                          device: int = 0, s_init=None, v_init=None, a_minus1=None, tv_init=None, engines=None):
+                          device: int = 0, s_init=None, v_init=None, a_minus1=None, tv_init=None, engines=None,
+                          preview: bool = False):
     """What ABO/Main.m:82-89 does for a use case with generateTVMPC and IncludeTV, for a batch: the lead vehicle's trace is
     generated by RunOpt_TVMPC on the device, TVlength is subtracted from its distance (:88) and the result is handed to
     run_abmpc / run_fbmpc / run_blmpc (kind "ab" / "fb" / "bl") as device tensors, with no host copy in between.
@@ -732,10 +776,15 @@ def generate_lead_and_run(OPTsettings: Dict[str, Any], V: Optional[Dict[str, flo
     tv_init = (s0, v0, a_minus1) of the lead vehicles, each [batch] (default: TVinitDist, TVinitVel, a_minus1);
     s_init, v_init, a_minus1: the ego vehicles' (default: the settings').  engines = (tv_engine, ego_engine) reuses handles.
     The two controllers share the sample grid, so TV_Ts must equal Tvec[0]: anything else is refused, not resampled.
+    preview=True (kind "ab" or "bl"): the generated trace is also the controller's guess of the lead's future, through
+    run_abmpc_preview / run_blmpc_preview with n_lead = n_steps, so that ABMPC and its yardstick can be given the same
+    information; FBMPC has no such entry and raises ValueError.
     Returns (traj, status, s_tv, v_tv): the ego closed loop and the [n_steps, batch] lead traces it was fed."""
     from .settings import SetVehicleParameters, Settings_TV, Settings_BL
     if kind not in ("ab", "fb", "bl"):
         raise ValueError("kind must be 'ab', 'fb' or 'bl'")
+    if preview and kind == "fb":
+        raise ValueError("preview=True: FBMPC has no entry with supplied horizon guesses; kind must be 'ab' or 'bl'")
     Ts = float(np.asarray(OPTsettings["Tvec"]).ravel()[0])
     if float(OPTsettings["TV_Ts"]) != Ts:
         raise ValueError("TV_Ts = %g differs from Tvec[0] = %g: the lead trace would have to be resampled (ABO/Main.m:82-89 "
@@ -756,7 +805,10 @@ def generate_lead_and_run(OPTsettings: Dict[str, Any], V: Optional[Dict[str, flo
     lead, _ = tv.run_tvmpc(tv0[0], tv0[1], tv0[2], n_steps)
     s_tv = (lead[:, OUT["s"], :] - float(OPTsettings["TVlength"])).contiguous()      # Main.m:88
     v_tv = lead[:, OUT["v"], :].contiguous()
-    run = {"ab": ego.run_abmpc, "fb": ego.run_fbmpc, "bl": ego.run_blmpc}[kind]
+    if preview:
+        run = {"ab": ego.run_abmpc_preview, "bl": ego.run_blmpc_preview}[kind]
+    else:
+        run = {"ab": ego.run_abmpc, "fb": ego.run_fbmpc, "bl": ego.run_blmpc}[kind]
     traj, status = run(full(s_init, OPTsettings["s_init"]), full(v_init, OPTsettings["v_init"]),
                        full(a_minus1, OPTsettings["a_minus1"]), s_tv, v_tv)
     return traj, status, s_tv, v_tv

@@ -208,7 +208,7 @@ int  eepacc_create_classes(eepacc_handle** out, const eepacc_settings* S, const 
  * handle created by eepacc_create from the settings of its class.
  *
  * Refused with EEPACC_ENOTSUP: FBMPC, the dense QP operator, every _qp_size / _qp_rows / _build_qp, the _est entries and
- * eepacc_run_abmpc_preview.  A bl_mode = 2 handle on an ABMPC / BLMPC entry and a bl_mode = 1 handle on a TVMPC entry answer
+ * the two _preview loops.  A bl_mode = 2 handle on an ABMPC / BLMPC entry and a bl_mode = 1 handle on a TVMPC entry answer
  * EEPACC_EINVAL, as the handles of eepacc_create with those modes do.  A handle of eepacc_create_classes (ABMPC classes)
  * on eepacc_bl_* / eepacc_tv_* stays EEPACC_ENOTSUP. */
 int  eepacc_create_classes_bl(eepacc_handle** out, const eepacc_settings* S, const eepacc_vehicle* V,
@@ -267,10 +267,13 @@ int  eepacc_ab_step(eepacc_handle* h, int B,
  * (1-frac) s_tv[r+idx] + frac s_tv[r+idx+1], and past the last row s_tv[n_lead-1] + v_tv[n_lead-1] (t - t_last).  A lead at
  * +inf (no lead, Main.m:77-80) stays +inf.  scenarios.lead_preview of the Python package states the rule in numpy.
  *
- * EEPACC_ENOTSUP, the message naming the cause: a handle of eepacc_create_classes, bl_mode != 0, any Mb[k] != 0,
+ * EEPACC_ENOTSUP, the message naming the cause: a handle of eepacc_create_classes / _classes_bl, bl_mode != 0, any Mb[k] != 0,
  * ab_fuel_term == 2.  EEPACC_EINVAL: a NULL required buffer, s_est without v_est or the reverse, B out of range,
  * n_lead < n_steps.  B = 0 returns EEPACC_OK.
- * Not built: supplied guesses for FBMPC, for the baseline and target-vehicle controllers, and a preview of the ego estimate.
+ * The baseline controller's counterparts are eepacc_bl_step_est, eepacc_bl_build_qp_est and eepacc_run_blmpc_preview, below; on a
+ * bl_mode = 1 handle the message of these three entries points to them.
+ * Not built: supplied guesses for FBMPC, for class handles, for the target-vehicle controller, for move blocking and the ICE
+ * map, and a preview of the ego estimate.
  * Cost against eepacc_ab_step / eepacc_run_abmpc: tools/gpu_ab_est_bench.py, DESIGN.md section 3.4f. */
 int  eepacc_ab_step_est(eepacc_handle* h, int B,
                         const double* s, const double* v, const double* a_prev, const double* t0,
@@ -562,6 +565,45 @@ int  eepacc_run_blmpc_host(eepacc_handle* h, int B, int n_steps,
                            const double* s0, const double* v0, const double* a_minus1,
                            const double* s_tv, const double* v_tv,
                            double* traj, int32_t* status);
+
+/* The baseline controller with the horizon guesses supplied: the contract of CreateQP_BL(OPTsettings, n_x, n_u, s_0, v_0, s_est,
+ * v_est, s_tv_est, t_0, a_minus1) (ABO/RunOpt_BLMPC.m:56,182), for a handle created with bl_mode = 1.  They are to eepacc_bl_step,
+ * eepacc_bl_build_qp and eepacc_run_blmpc what eepacc_ab_step_est, eepacc_ab_build_qp_est and eepacc_run_abmpc_preview are to
+ * the ABMPC entries: same arguments, argument order, layouts and NULL rules, so that the yardstick of a use case can be given
+ * the lead's future that ABMPC was given.
+ * s_est, v_est, s_tv_est: device arrays [N_hor+1][B].  s_est and v_est are given together or both NULL; NULL: the handle's ego
+ * estimator.  They reach the problem through the route and comfort bounds alone (EstimateRouteAndComfortBounds,
+ * CreateQP_BL.m:46); row 0 is used as given.  s_tv_est may be NULL: the handle's TVestSetting.  It enters only the upper bound
+ * of the two safe-distance rows of every stage (CreateQP_BL.m:291,295) and of the two terminal rows, which read s_tv_est(N) of
+ * the reference, stage N_hor - 1 here (:309,313): row N_hor is not read.  +inf: no lead at that stage.  With all three NULL the
+ * entries compute what eepacc_bl_step / eepacc_bl_build_qp compute, bit for bit.
+ * eepacc_bl_step_est reads and writes exactly the handle state eepacc_bl_step does (warm start, the proximal iteration's
+ * working set, carried predictions, iteration counts): the two can alternate on one handle.  eepacc_bl_build_qp_est reads no
+ * solver state and writes none; eepacc_bl_qp_size and eepacc_bl_qp_rows describe its output.  The problem is a linear program
+ * with the reference's weights: compare objective values (EEPACC_OUT_COST), not points.
+ * eepacc_run_blmpc_preview: eepacc_run_blmpc with the lead's horizon guess read from the lead trace itself, by the preview rule
+ * of eepacc_run_abmpc_preview unchanged (s_tv, v_tv [n_lead][B], n_lead >= n_steps, resumed launches pass the continued rows,
+ * past the last row the lead continues at its last speed, +inf stays +inf; scenarios.lead_preview states it in numpy).  The ego
+ * estimator stays the handle's.
+ * EEPACC_ENOTSUP, the message naming the cause: a handle of eepacc_create_classes / eepacc_create_classes_bl; bl_mode = 0 (the
+ * message points to the eepacc_ab_ entries); bl_mode = 2 (the target-vehicle controller has no lead and hands the bounds a
+ * zero speed estimate: not built).  EEPACC_EINVAL: a NULL required buffer, s_est without v_est or the reverse, B out of range,
+ * n_lead < n_steps.  B = 0 returns EEPACC_OK.
+ * Cost against eepacc_bl_step / eepacc_run_blmpc: tools/gpu_bl_est_bench.py, DESIGN.md section 3.7b. */
+int  eepacc_bl_step_est(eepacc_handle* h, int B,
+                        const double* s, const double* v, const double* a_prev, const double* t0,
+                        const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                        const double* s_est, const double* v_est, const double* s_tv_est,
+                        double* out, double* s_pred, double* v_pred, int32_t* status, void* stream);
+int  eepacc_bl_build_qp_est(eepacc_handle* h, int B,
+                            const double* s, const double* v, const double* a_prev, const double* t0,
+                            const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                            const double* s_est, const double* v_est, const double* s_tv_est,
+                            double* H, double* g, double* A, double* lba, double* uba, void* stream);
+int  eepacc_run_blmpc_preview(eepacc_handle* h, int B, int n_steps, int n_lead,
+                              const double* s0, const double* v0, const double* a_minus1,
+                              const double* s_tv, const double* v_tv,
+                              double* traj, int32_t* status, void* stream);
 
 /* Target-vehicle MPC by name: [s_opt, v_opt, numSolverErrors] = RunOpt_TVMPC(OPTsettings) (ABO/RunOpt_TVMPC.m:1,
  * ABO/Main.m:85) and the body of its loop (:156-277).  They require a handle created with bl_mode = 2 (EEPACC_EINVAL
