@@ -66,6 +66,12 @@ AB_EST_ARGTYPES = {
 # the baseline controller's counterparts (a handle with bl_mode = 1): arguments and order are those of the AB entries
 BL_EST_ARGTYPES = {name.replace("eepacc_ab_", "eepacc_bl_").replace("abmpc", "blmpc"): list(argtypes)
                    for name, argtypes in AB_EST_ARGTYPES.items()}
+# the step and the closed loop of the two on a handle with settings classes (eepacc_create_classes, eepacc_create_classes_bl
+# with bl_mode = 1): arguments and order are those of eepacc_ab_step_est and eepacc_run_abmpc_preview
+CLASSES_EST_ARGTYPES = {
+    "eepacc_classes_step_est": list(AB_EST_ARGTYPES["eepacc_ab_step_est"]),
+    "eepacc_run_classes_preview": list(AB_EST_ARGTYPES["eepacc_run_abmpc_preview"]),
+}
 
 # enum EEPACC_FB_ROW_*: the row types of eepacc_fb_qp_rows, ascending in the order of the rows within a stage
 FB_ROW_TYPES = ["s", "v", "fm", "fb", "xi_v", "xi_h", "xi_s", "xi_f", "blocked_fm", "blocked_fb", "tm_min", "tm_max",

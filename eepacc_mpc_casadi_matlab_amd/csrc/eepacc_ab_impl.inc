@@ -4,8 +4,9 @@
 // soft rows), EEPACC_IMPL_TV (with _BL: the target-vehicle MPC, CreateQP_TV.m: the baseline QP without its
 // vehicle-following rows and without lead inputs), EEPACC_IMPL_ICE (the ICE-map fuel term, whose Hessian is built and
 // inverted every step), EEPACC_IMPL_CLS (settings classes: every instance has the DevCfg of its class) and EEPACC_IMPL_EST
-// (horizon guesses from the caller instead of the estimators: eepacc_ab_step_est, eepacc_run_abmpc_preview), so that the
-// default path carries no register or instruction cost for the variants.
+// (horizon guesses from the caller instead of the estimators: eepacc_ab_step_est, eepacc_run_abmpc_preview; with
+// EEPACC_IMPL_CLS: eepacc_classes_step_est, eepacc_run_classes_preview), so that the default path carries no register or
+// instruction cost for the variants.
 // The tables of the active-set method (the inverse He of the effective Hessian, the inverse Schur block P of the working
 // set) are maintained by eepacc_schur.h, and the steps of a dual pass that do not depend on the row catalogue are in
 // eepacc_dual_step.h; the FBMPC kernels share both, and both are included once, outside these namespaces.
@@ -21,7 +22,7 @@ static_assert(!kTargetVeh || kBaseline, "the target-vehicle MPC is a variant of 
 constexpr bool kClasses = EEPACC_IMPL_CLS;  // a handle of eepacc_create_classes / _classes_bl: the kernels' Cp is its array DevCfg[n_classes]
 static_assert(!kClasses || !(kMoveBlocking || kIce), "settings classes are built for the plain ABMPC kernels and the two baseline variants only");
 constexpr bool kEst = EEPACC_IMPL_EST;      // the kernels take horizon guesses as further arguments (DESIGN.md section 3.4f)
-static_assert(!kEst || !(kMoveBlocking || kTargetVeh || kIce || kClasses), "supplied horizon guesses are built for the plain ABMPC kernels and the baseline controller (blest) only");
+static_assert(!kEst || !(kMoveBlocking || kTargetVeh || kIce), "supplied horizon guesses are built for the plain ABMPC kernels and the baseline controller, with one DevCfg (est, blest) or with settings classes (clsest, blclsest), only");
 
 
 #undef PTIC
@@ -1610,12 +1611,17 @@ static_assert(kClasses ==
               false,
 #endif
               "EEPACC_IMPL_CLASS_MAP is defined for the instantiation whose list entry sets EEPACC_IMPL_CLS, and for no other");
-template <class... ClassOf>
-__device__ __forceinline__ const DevCfg& cfg_of(const DevCfg& C0, int b, ClassOf... class_of) {
-    static_assert(kEst || sizeof...(ClassOf) == (kClasses ? 1 : 0), "the class map is an argument of the class kernels, and of them alone");
+// clsest, blclsest: the kernels' pack holds both, the class map first and the est arguments behind it.  cfg_of (and with it
+// EEPACC_AB_UNIT_CFG) takes the whole pack and reads its head; est_supplied / est_preview below take the whole pack too and
+// read what follows the map.
+template <class Head, class... Tail>
+__device__ __forceinline__ Head pack_head(Head head, Tail...) { return head; }
+template <class... Extra>
+__device__ __forceinline__ const DevCfg& cfg_of(const DevCfg& C0, int b, Extra... extra) {
+    static_assert(kEst || sizeof...(Extra) == (kClasses ? 1 : 0), "the class map is an argument of the class kernels, and of them alone");
     if constexpr (kClasses) {
-        const int32_t* map[] = {class_of...};
-        return (&C0)[__builtin_amdgcn_readfirstlane(map[0][b])];
+        const int32_t* map = pack_head(extra...);
+        return (&C0)[__builtin_amdgcn_readfirstlane(map[b])];
     } else return C0;
 }
 
@@ -1629,6 +1635,11 @@ __device__ __forceinline__ EstIn est_supplied(int lane, int N, int B, int b, con
     if (e.ego) { e.s_est = s_est[ke * B + b]; e.v_est = v_est[ke * B + b]; }
     if (e.lead) e.stv_est = s_tv_est[kl * B + b];
     return e;
+}
+// (clsest, blclsest: the pack's head is the class map, which cfg_of has read)
+__device__ __forceinline__ EstIn est_supplied(int lane, int N, int B, int b, const int32_t* /*class_of*/, const double* __restrict__ s_est,
+                                              const double* __restrict__ v_est, const double* __restrict__ s_tv_est) {
+    return est_supplied(lane, N, B, b, s_est, v_est, s_tv_est);
 }
 // The lead's guess of the step at row kk of the launch's traces [n_lead][B], read from the traces themselves
 // (eepacc_run_abmpc_preview; scenarios.lead_preview is the specification).  Stage k looks tau_k ahead, at row
@@ -1651,9 +1662,17 @@ __device__ __forceinline__ EstIn est_preview(const DevCfg& C, int lane, int B, i
     }
     return e;
 }
+// (clsest, blclsest: the class map in front.  C is the DevCfg of the unit's instance, EEPACC_AB_UNIT_CFG's binding: N, tau
+// and Tvec[0] are read from it, while idx and frac are the handle's tables, made of class 0's Tvec.  The classes of a
+// handle share N and Tvec, so the two agree.)
+__device__ __forceinline__ EstIn est_preview(const DevCfg& C, int lane, int B, int b, int kk, const double* __restrict__ s_tv,
+                                             const double* __restrict__ v_tv, const int32_t* /*class_of*/, const int32_t* __restrict__ idx,
+                                             const double* __restrict__ frac, int n_lead) {
+    return est_preview(C, lane, B, b, kk, s_tv, v_tv, idx, frac, n_lead);
+}
 
 // B2: one step for B instances.  state: per instance 64 x uint64 codes (instance-major).  extra: the class map (cls), the
-// three supplied arrays (est), nothing elsewhere.
+// three supplied arrays (est), the map and then the arrays (clsest), nothing elsewhere.
 template <int MMAX, int NS, int WPB, class... Extra>
 __global__ void __launch_bounds__(64 * WPB, ((NS <= 32 && WPB >= 4) ? 2 : 1))
 k_ab_step(const DevCfg* __restrict__ Cp, int B,
@@ -1690,7 +1709,8 @@ k_ab_step(const DevCfg* __restrict__ Cp, int B,
 }
 
 // B1: closed loop over n_steps for B instances (ABO/RunOpt_ABMPC.m:154-340) in work units (run_units, eepacc_units.h).
-// Ts and the LDS layout are fixed for the launch (Cp[0]); the settings are bound per work unit.
+// Ts and the LDS layout are fixed for the launch (Cp[0]); the settings are bound per work unit.  With classes, every C
+// inside the unit's body is that binding (it shadows the kernel's class-0 C), est_preview's argument included.
 // k_start > 0 resumes from the carried per-instance state (carry [6][B], see Carry; codes: shifted working set).  The
 // small-horizon kernel is compiled for 2 waves per SIMD (1: 512 registers, no scratch; measured slower).
 template <int MMAX, int NS, int WPB, class... Extra>
@@ -1754,12 +1774,14 @@ k_run_abmpc(const DevCfg* __restrict__ Cp, int B, int k_start, int n_steps,
 
 // the kernels of this instantiation as the host launches them: with the class map where the variant has one
 template <int MMAX, int NS, int WPB> constexpr auto step_kernel() {
-    if constexpr (kEst) return &k_ab_step<MMAX, NS, WPB, const double*, const double*, const double*>;      // s_est, v_est, s_tv_est
+    if constexpr (kEst && kClasses) return &k_ab_step<MMAX, NS, WPB, const int32_t*, const double*, const double*, const double*>;   // class_of, then est's
+    else if constexpr (kEst) return &k_ab_step<MMAX, NS, WPB, const double*, const double*, const double*>;      // s_est, v_est, s_tv_est
     else if constexpr (kClasses) return &k_ab_step<MMAX, NS, WPB, const int32_t*>;
     else return &k_ab_step<MMAX, NS, WPB>;
 }
 template <int MMAX, int NS, int WPB> constexpr auto run_kernel() {
-    if constexpr (kEst) return &k_run_abmpc<MMAX, NS, WPB, const int32_t*, const double*, int>;             // idx, frac, n_lead
+    if constexpr (kEst && kClasses) return &k_run_abmpc<MMAX, NS, WPB, const int32_t*, const int32_t*, const double*, int>;   // class_of, then est's
+    else if constexpr (kEst) return &k_run_abmpc<MMAX, NS, WPB, const int32_t*, const double*, int>;             // idx, frac, n_lead
     else if constexpr (kClasses) return &k_run_abmpc<MMAX, NS, WPB, const int32_t*>;
     else return &k_run_abmpc<MMAX, NS, WPB>;
 }

@@ -418,7 +418,7 @@ extern "C" int eepacc_run_tvmpc(eepacc_handle* h, int B, int n_steps, const doub
 // ---- horizon guesses from the caller: eepacc_ab_step_est, eepacc_ab_build_qp_est, eepacc_run_abmpc_preview run a plain ABMPC
 // handle (AbVariant::Plain) through the est kernels, eepacc_bl_step_est, eepacc_bl_build_qp_est, eepacc_run_blmpc_preview a
 // handle of the baseline controller (bl_mode = 1, AbVariant::Baseline) through the blest kernels: on the handle's own state.
-// bl: the entry belongs to the baseline controller.
+// bl: the entry belongs to the baseline controller.  With settings classes: est_classes_handle below.
 static int est_handle(const eepacc_handle* h, const std::string& who, bool bl = false) {
     if (!h) return fail(EEPACC_EINVAL, who + ": NULL handle");
     if (h->n_classes) return fail(EEPACC_ENOTSUP, who + ": a handle of eepacc_create_classes / eepacc_create_classes_bl has no variant with supplied horizon guesses");
@@ -437,17 +437,37 @@ static int est_handle(const eepacc_handle* h, const std::string& who, bool bl = 
     if (h->cfg.ab_fuel_term == 2) return fail(EEPACC_ENOTSUP, who + ": ab_fuel_term == 2: the ICE-map fuel term has no variant with supplied horizon guesses");
     return EEPACC_OK;
 }
+// eepacc_classes_step_est, eepacc_run_classes_preview: the same for a handle with settings classes, which decides the
+// controller itself (eepacc_create_classes: the clsest kernels, eepacc_create_classes_bl with bl_mode = 1: blclsest).  The
+// six entries above keep refusing class handles; these two refuse every other handle.
+static int est_classes_handle(const eepacc_handle* h, const std::string& who) {
+    if (!h) return fail(EEPACC_EINVAL, who + ": NULL handle");
+    if (!h->n_classes) {
+        const char* plain = h->cfg.bl_mode == 1 ? "eepacc_bl_step_est / eepacc_run_blmpc_preview run a handle of the baseline controller"
+                          : h->cfg.bl_mode == 2 ? "the target-vehicle controller has no entry with supplied horizon guesses"
+                                                : "eepacc_ab_step_est / eepacc_run_abmpc_preview run a plain ABMPC handle";
+        return fail(EEPACC_ENOTSUP, who + ": this handle has no settings classes (it was created by eepacc_create with bl_mode = " +
+                                        std::to_string(h->cfg.bl_mode) + "); " + plain);
+    }
+    if (h->cfg.bl_mode == 2)
+        return fail(EEPACC_ENOTSUP, who + ": the classes of this handle were created with bl_mode = 2 (RunOpt_TVMPC); the target-vehicle controller has no lead and hands its bounds a zero speed estimate, so supplied horizon guesses are not built for it");
+    return EEPACC_OK;       // (class handles have neither move blocking nor the ICE-map fuel term: create_classes_impl)
+}
+enum class EstEntry { Ab, Bl, Classes };
+static int est_entry_handle(EstEntry entry, const eepacc_handle* h, const std::string& who) {
+    return entry == EstEntry::Classes ? est_classes_handle(h, who) : est_handle(h, who, entry == EstEntry::Bl);
+}
 static int est_pair(const std::string& who, const double* s_est, const double* v_est) {
     if (s_est && !v_est) return fail(EEPACC_EINVAL, who + ": s_est is given without v_est; the two are given together or both NULL");
     if (v_est && !s_est) return fail(EEPACC_EINVAL, who + ": v_est is given without s_est; the two are given together or both NULL");
     return EEPACC_OK;
 }
 
-static int step_est_impl(bool bl, const std::string& who, eepacc_handle* h, int B, const double* s, const double* v,
+static int step_est_impl(EstEntry entry, const std::string& who, eepacc_handle* h, int B, const double* s, const double* v,
                          const double* a_prev, const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
                          const double* s_est, const double* v_est, const double* s_tv_est,
                          double* out, double* s_pred, double* v_pred, int32_t* status, void* stream) {
-    if (const int rc = est_handle(h, who, bl)) return rc;
+    if (const int rc = est_entry_handle(entry, h, who)) return rc;
     if (B < 0 || B > h->max_batch)
         return fail(EEPACC_EINVAL, who + ": B = " + std::to_string(B) + " is outside [0, max_batch = " + std::to_string(h->max_batch) + "]");
     if (B == 0) return EEPACC_OK;
@@ -459,19 +479,25 @@ extern "C" int eepacc_ab_step_est(eepacc_handle* h, int B, const double* s, cons
                                   const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
                                   const double* s_est, const double* v_est, const double* s_tv_est,
                                   double* out, double* s_pred, double* v_pred, int32_t* status, void* stream) {
-    return step_est_impl(false, "eepacc_ab_step_est", h, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, s_est, v_est, s_tv_est, out, s_pred, v_pred, status, stream);
+    return step_est_impl(EstEntry::Ab, "eepacc_ab_step_est", h, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, s_est, v_est, s_tv_est, out, s_pred, v_pred, status, stream);
 }
 extern "C" int eepacc_bl_step_est(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
                                   const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
                                   const double* s_est, const double* v_est, const double* s_tv_est,
                                   double* out, double* s_pred, double* v_pred, int32_t* status, void* stream) {
-    return step_est_impl(true, "eepacc_bl_step_est", h, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, s_est, v_est, s_tv_est, out, s_pred, v_pred, status, stream);
+    return step_est_impl(EstEntry::Bl, "eepacc_bl_step_est", h, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, s_est, v_est, s_tv_est, out, s_pred, v_pred, status, stream);
+}
+extern "C" int eepacc_classes_step_est(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
+                                       const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                                       const double* s_est, const double* v_est, const double* s_tv_est,
+                                       double* out, double* s_pred, double* v_pred, int32_t* status, void* stream) {
+    return step_est_impl(EstEntry::Classes, "eepacc_classes_step_est", h, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, s_est, v_est, s_tv_est, out, s_pred, v_pred, status, stream);
 }
 
-static int run_preview_impl(bool bl, const std::string& who, eepacc_handle* h, int B, int n_steps, int n_lead, const double* s0,
+static int run_preview_impl(EstEntry entry, const std::string& who, eepacc_handle* h, int B, int n_steps, int n_lead, const double* s0,
                             const double* v0, const double* a_minus1, const double* s_tv, const double* v_tv, double* traj,
                             int32_t* status, void* stream) {
-    if (const int rc = est_handle(h, who, bl)) return rc;
+    if (const int rc = est_entry_handle(entry, h, who)) return rc;
     if (B < 0 || B > h->max_batch || n_steps < 0)
         return fail(EEPACC_EINVAL, who + ": B = " + std::to_string(B) + " must be in [0, max_batch = " + std::to_string(h->max_batch) + "] and n_steps = " + std::to_string(n_steps) + " not negative");
     if (n_lead < n_steps)
@@ -481,7 +507,7 @@ static int run_preview_impl(bool bl, const std::string& who, eepacc_handle* h, i
         const int N = h->cfg.N;
         std::vector<int32_t> idx((size_t)N);
         std::vector<double> frac((size_t)N);
-        eepacc::preview_tables(h->cfg.Tvec, N, idx.data(), frac.data());
+        eepacc::preview_tables(h->cfg.Tvec, N, idx.data(), frac.data());        // (class handle: class 0's Tvec, which every class shares)
         HIPCHK(hipSetDevice(h->device));
         HIPCHK(h->d_pv_frac.alloc((size_t)N));
         HIPCHK(hipMemcpy(h->d_pv_frac, frac.data(), (size_t)N * sizeof(double), hipMemcpyHostToDevice));
@@ -494,12 +520,17 @@ static int run_preview_impl(bool bl, const std::string& who, eepacc_handle* h, i
 extern "C" int eepacc_run_abmpc_preview(eepacc_handle* h, int B, int n_steps, int n_lead, const double* s0, const double* v0,
                                         const double* a_minus1, const double* s_tv, const double* v_tv, double* traj,
                                         int32_t* status, void* stream) {
-    return run_preview_impl(false, "eepacc_run_abmpc_preview", h, B, n_steps, n_lead, s0, v0, a_minus1, s_tv, v_tv, traj, status, stream);
+    return run_preview_impl(EstEntry::Ab, "eepacc_run_abmpc_preview", h, B, n_steps, n_lead, s0, v0, a_minus1, s_tv, v_tv, traj, status, stream);
 }
 extern "C" int eepacc_run_blmpc_preview(eepacc_handle* h, int B, int n_steps, int n_lead, const double* s0, const double* v0,
                                         const double* a_minus1, const double* s_tv, const double* v_tv, double* traj,
                                         int32_t* status, void* stream) {
-    return run_preview_impl(true, "eepacc_run_blmpc_preview", h, B, n_steps, n_lead, s0, v0, a_minus1, s_tv, v_tv, traj, status, stream);
+    return run_preview_impl(EstEntry::Bl, "eepacc_run_blmpc_preview", h, B, n_steps, n_lead, s0, v0, a_minus1, s_tv, v_tv, traj, status, stream);
+}
+extern "C" int eepacc_run_classes_preview(eepacc_handle* h, int B, int n_steps, int n_lead, const double* s0, const double* v0,
+                                          const double* a_minus1, const double* s_tv, const double* v_tv, double* traj,
+                                          int32_t* status, void* stream) {
+    return run_preview_impl(EstEntry::Classes, "eepacc_run_classes_preview", h, B, n_steps, n_lead, s0, v0, a_minus1, s_tv, v_tv, traj, status, stream);
 }
 
 // ---- the condensed QP of a step as data: eepacc_{ab,fb,bl}_qp_size, _qp_rows, _build_qp.  What the three families do alike is

@@ -40,6 +40,10 @@
 //          has this variant, its two entry points run a plain handle
 //   blest  the same for the baseline controller (eepacc_bl_step_est, eepacc_run_blmpc_preview): blc with est's further
 //          arguments; no handle has this variant either, its entry points run a bl_mode = 1 handle
+//   clsest, blclsest  cls and blcls with est's further arguments behind the class map (eepacc_classes_step_est,
+//          eepacc_run_classes_preview): no handle has these variants, the two entry points run a handle of
+//          eepacc_create_classes through clsest and one of eepacc_create_classes_bl with bl_mode = 1 through blclsest
+//          
 #define EEPACC_AB_VARIANTS(X, ...)                                                     \
     X(Plain, nomb, false, false, false, false, false, false, __VA_ARGS__)              \
     X(MoveBlocking, withmb, true, false, false, false, false, false, __VA_ARGS__)      \
@@ -51,7 +55,9 @@
     X(ClassesBL, blcls, false, true, false, false, true, false, __VA_ARGS__)           \
     X(ClassesTV, tvcls, false, true, true, false, true, false, __VA_ARGS__)            \
     X(Est, est, false, false, false, false, false, true, __VA_ARGS__)                  \
-    X(BlEst, blest, false, true, false, false, false, true, __VA_ARGS__)
+    X(BlEst, blest, false, true, false, false, false, true, __VA_ARGS__)               \
+    X(ClassesEst, clsest, false, false, false, false, true, true, __VA_ARGS__)         \
+    X(ClassesBlEst, blclsest, false, true, false, false, true, true, __VA_ARGS__)
 
 // an instantiation reads its switches from the list by the name of its namespace
 namespace eepacc { namespace ab_switch {
@@ -90,6 +96,12 @@ EEPACC_AB_VARIANTS(EEPACC_AB_SWITCHES)
 #include "eepacc_ab_impl.inc"
 #undef EEPACC_IMPL_NS
 #define EEPACC_IMPL_NS tvcls
+#include "eepacc_ab_impl.inc"
+#undef EEPACC_IMPL_NS
+#define EEPACC_IMPL_NS clsest
+#include "eepacc_ab_impl.inc"
+#undef EEPACC_IMPL_NS
+#define EEPACC_IMPL_NS blclsest
 #include "eepacc_ab_impl.inc"
 #undef EEPACC_IMPL_CLASS_MAP
 #undef EEPACC_IMPL_NS
@@ -131,8 +143,9 @@ size_t ab_smem_bytes(int N) {
 
 // the kernel of the handle's variant, small or large horizon; a kernel with one parameter more than the launch has
 // arguments is a class kernel (eepacc_ab_impl.inc, cfg_of) and gets the class map as its last.  The est and blest kernels
-// have three more: no handle has those variants, and launch_est below gives them theirs (est for a plain handle, blest for
-// one of the baseline controller).
+// have three more, the clsest and blclsest kernels four: no handle has those variants, and launch_est below gives them
+// theirs (est for a plain handle, blest for one of the baseline controller, clsest and blclsest for the class handles of
+// the two, with the class map in front of est's arguments).
 template <class... P, class... A>
 static void launch_ab(void (*kernel)(P...), int grid, int block, size_t smem, hipStream_t stream, const int32_t* class_of, A... args) {
     if constexpr (sizeof...(P) == sizeof...(A) + 1) hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), smem, stream, args..., class_of);
@@ -176,10 +189,18 @@ hipError_t launch_ab_step(const DevCfg* dC, const int32_t* class_of, int N, AbVa
                           unsigned long long* codes, double* out, double* s_pred, double* v_pred,
                           int32_t* status, int32_t* iters, hipStream_t stream, const AbSupplied* sup) {
     if (sup) {
-        const bool bl = variant == AbVariant::Baseline;
-#define EEPACC_EST_STEP(NSP, MM, NSV, WPB) launch_est(NSP::step_kernel<MM, NSV, WPB>(), (B + WPB - 1) / WPB, WPB, N, stream, dC, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, codes, out, s_pred, v_pred, status, iters, sup->s_est, sup->v_est, sup->s_tv_est)
-        if (N > kNSSmall) { if (bl) EEPACC_EST_STEP(blest, kMMaxLarge, kNSLarge, kWpbLarge); else EEPACC_EST_STEP(est, kMMaxLarge, kNSLarge, kWpbLarge); }
-        else { if (bl) EEPACC_EST_STEP(blest, kMMaxSmall, kNSSmall, 4); else EEPACC_EST_STEP(est, kMMaxSmall, kNSSmall, 4); }
+        const bool bl = variant == AbVariant::Baseline || variant == AbVariant::ClassesBL;
+#define EEPACC_EST_STEP(NSP, MM, NSV, WPB, ...) launch_est(NSP::step_kernel<MM, NSV, WPB>(), (B + WPB - 1) / WPB, WPB, N, stream, dC, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, codes, out, s_pred, v_pred, status, iters, __VA_ARGS__)
+#define EEPACC_EST_STEP_SIZE(MM, NSV, WPB)                                                                                  \
+        do {                                                                                                                 \
+            if (class_of) { if (bl) EEPACC_EST_STEP(blclsest, MM, NSV, WPB, class_of, sup->s_est, sup->v_est, sup->s_tv_est); \
+                            else EEPACC_EST_STEP(clsest, MM, NSV, WPB, class_of, sup->s_est, sup->v_est, sup->s_tv_est); }    \
+            else if (bl) EEPACC_EST_STEP(blest, MM, NSV, WPB, sup->s_est, sup->v_est, sup->s_tv_est);                        \
+            else EEPACC_EST_STEP(est, MM, NSV, WPB, sup->s_est, sup->v_est, sup->s_tv_est);                                  \
+        } while (0)
+        if (N > kNSSmall) EEPACC_EST_STEP_SIZE(kMMaxLarge, kNSLarge, kWpbLarge);
+        else EEPACC_EST_STEP_SIZE(kMMaxSmall, kNSSmall, 4);
+#undef EEPACC_EST_STEP_SIZE
 #undef EEPACC_EST_STEP
         return hipGetLastError();
     }
@@ -201,10 +222,18 @@ hipError_t launch_run_abmpc(const DevCfg* dC, const int32_t* class_of, int N, Ab
                                num_cus * (large ? 1 : kBlocksSmall), stream, ul);
     if (e != hipSuccess) return e;
     if (pv) {
-        const bool bl = variant == AbVariant::Baseline;
-#define EEPACC_EST_RUN(NSP, MM, NSV, WPB) launch_est(NSP::run_kernel<MM, NSV, WPB>(), ul.grid, WPB, N, stream, dC, B, k_start, n_steps, s0, v0, a_m1, s_tv, v_tv, carry, codes, traj, status, iters_total, work_counter, done, kChunkSteps, err_word, ul.spin_limit, pv->idx, pv->frac, pv->n_lead)
-        if (large) { if (bl) EEPACC_EST_RUN(blest, kMMaxLarge, kNSLarge, kWpbLarge); else EEPACC_EST_RUN(est, kMMaxLarge, kNSLarge, kWpbLarge); }
-        else { if (bl) EEPACC_EST_RUN(blest, kMMaxSmall, kNSSmall, 4); else EEPACC_EST_RUN(est, kMMaxSmall, kNSSmall, 4); }
+        const bool bl = variant == AbVariant::Baseline || variant == AbVariant::ClassesBL;
+#define EEPACC_EST_RUN(NSP, MM, NSV, WPB, ...) launch_est(NSP::run_kernel<MM, NSV, WPB>(), ul.grid, WPB, N, stream, dC, B, k_start, n_steps, s0, v0, a_m1, s_tv, v_tv, carry, codes, traj, status, iters_total, work_counter, done, kChunkSteps, err_word, ul.spin_limit, __VA_ARGS__)
+#define EEPACC_EST_RUN_SIZE(MM, NSV, WPB)                                                                       \
+        do {                                                                                                     \
+            if (class_of) { if (bl) EEPACC_EST_RUN(blclsest, MM, NSV, WPB, class_of, pv->idx, pv->frac, pv->n_lead); \
+                            else EEPACC_EST_RUN(clsest, MM, NSV, WPB, class_of, pv->idx, pv->frac, pv->n_lead); }    \
+            else if (bl) EEPACC_EST_RUN(blest, MM, NSV, WPB, pv->idx, pv->frac, pv->n_lead);                     \
+            else EEPACC_EST_RUN(est, MM, NSV, WPB, pv->idx, pv->frac, pv->n_lead);                               \
+        } while (0)
+        if (large) EEPACC_EST_RUN_SIZE(kMMaxLarge, kNSLarge, kWpbLarge);
+        else EEPACC_EST_RUN_SIZE(kMMaxSmall, kNSSmall, 4);
+#undef EEPACC_EST_RUN_SIZE
 #undef EEPACC_EST_RUN
         return hipGetLastError();
     }

@@ -13,7 +13,7 @@ from typing import Any, Dict, NamedTuple, Optional
 
 import numpy as np
 
-from ._abi import (SettingsHolder, SettingsPOD, Vehicle, make_vehicle, pack_classes, OUT, OUT_N, OUT_FIELDS, KPI_N, FKPI_N, FKPI_WEIGHTS, RKPI_N, RLIM_N, ROUTE_KPIS_ARGTYPES, AB_BUILD_ARGTYPES, AB_EST_ARGTYPES, BL_EST_ARGTYPES,
+from ._abi import (SettingsHolder, SettingsPOD, Vehicle, make_vehicle, pack_classes, OUT, OUT_N, OUT_FIELDS, KPI_N, FKPI_N, FKPI_WEIGHTS, RKPI_N, RLIM_N, ROUTE_KPIS_ARGTYPES, AB_BUILD_ARGTYPES, AB_EST_ARGTYPES, BL_EST_ARGTYPES, CLASSES_EST_ARGTYPES,
                    FB_BUILD_ARGTYPES, BL_BUILD_ARGTYPES,
                    c_double_p, as_dptr, as_iptr)
 
@@ -75,7 +75,7 @@ def load_library() -> C.CDLL:
     lib.eepacc_qp_solve_batched_dual.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [dp] * 8 + [dp, dp] + [dp] * 3 + [dp] * 5 + [vp]
     lib.eepacc_qp_kkt_solve_batched.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int] + [dp] * 2 + [dp] * 2 + [dp] * 3 + [dp] * 3 + [dp, vp]
     for name, argtypes in (list(AB_BUILD_ARGTYPES.items()) + list(FB_BUILD_ARGTYPES.items()) + list(BL_BUILD_ARGTYPES.items())
-                           + list(AB_EST_ARGTYPES.items()) + list(BL_EST_ARGTYPES.items())):
+                           + list(AB_EST_ARGTYPES.items()) + list(BL_EST_ARGTYPES.items()) + list(CLASSES_EST_ARGTYPES.items())):
         getattr(lib, name).argtypes = argtypes
     lib.eepacc_synchronize.argtypes = [vp, vp]
     lib.eepacc_build_flags.restype = C.c_char_p
@@ -95,6 +95,7 @@ ABI_SYMBOLS = ["eepacc_last_error", "eepacc_version", "eepacc_sizeof_settings", 
                "eepacc_fb_qp_size", "eepacc_fb_qp_rows", "eepacc_fb_build_qp",
                "eepacc_bl_qp_size", "eepacc_bl_qp_rows", "eepacc_bl_build_qp",
                "eepacc_bl_step_est", "eepacc_bl_build_qp_est", "eepacc_run_blmpc_preview",
+               "eepacc_classes_step_est", "eepacc_run_classes_preview",
                "eepacc_synchronize", "eepacc_build_flags"]
 
 
@@ -404,6 +405,25 @@ class Engine:
         """eepacc_run_blmpc_preview: run_blmpc whose steps take the lead's horizon guess from the lead trace itself, by the
         rule of run_abmpc_preview (scenarios.lead_preview); arguments and results as there."""
         return self._run_preview(self.lib.eepacc_run_blmpc_preview, s0, v0, a_minus1, s_tv, v_tv, n_steps, resume, out)
+
+    # the same on an engine of from_classes: the engine's classes decide the controller (ABMPC, or Settings_BL in every class)
+    def classes_step_est(self, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, s_est=None, v_est=None, s_tv_est=None,
+                         want_pred: bool = True):
+        """eepacc_classes_step_est: ab_step_est / bl_step_est for an engine with settings classes, every instance with the
+        settings of its class in set_classes' map.  Arguments and results as ab_step_est; None keeps the estimator of the
+        instance's class, and with all three None the step is the engine's ab_step bit for bit.  Shares the engine state of
+        ab_step / run_abmpc / run_blmpc on this engine.  Refused on an engine without classes and on target-vehicle classes."""
+        self._est_check(s, s_est, v_est, s_tv_est)
+        return self._step_est(self.lib.eepacc_classes_step_est, (s, v, a_prev, t0, s_tv, v_tv, a_tv_prev), (s_est, v_est, s_tv_est), want_pred)
+
+    def run_classes_preview(self, s0, v0, a_minus1, s_tv, v_tv, n_steps=None, resume: bool = False, out=None):
+        """eepacc_run_classes_preview: run_abmpc_preview / run_blmpc_preview for an engine with settings classes, one launch
+        for the mixed batch; the rule is run_abmpc_preview's (scenarios.lead_preview), arguments and results as there.  A
+        resumed launch may follow run_abmpc / run_blmpc on the same engine and passes the continued rows."""
+        shape = lambda x: tuple(x.shape) if hasattr(x, "shape") else tuple(np.shape(x))
+        if len(shape(s_tv)) != 2 or shape(s_tv) != shape(v_tv):
+            raise ValueError("s_tv and v_tv are [n_lead, B] both, got %s and %s" % (shape(s_tv), shape(v_tv)))
+        return self._run_preview(self.lib.eepacc_run_classes_preview, s0, v0, a_minus1, s_tv, v_tv, n_steps, resume, out)
 
     # B1 ------------------------------------------------------------------------------------
     def run_abmpc(self, s0, v0, a_minus1, s_tv, v_tv, resume: bool = False, out=None, by_name_bl: bool = False):
@@ -814,7 +834,7 @@ def generate_lead_and_run(OPTsettings: Dict[str, Any], V: Optional[Dict[str, flo
     return traj, status, s_tv, v_tv
 
 
-def generate_lead_and_run_mix(mix: Dict[str, Any], kind: str = "ab", engines=None, device: int = 0):
+def generate_lead_and_run_mix(mix: Dict[str, Any], kind: str = "ab", engines=None, device: int = 0, preview: bool = False):
     """ABO/Main.m:82-89 for a whole use-case mix (scenarios.make_use_case_mix): a target-vehicle class engine generates every
     instance's lead along the route of its own class in one launch, TVlength[class_of] is subtracted on the device (:88) and
     the traces are handed to the ABMPC (kind "ab") or BLMPC (kind "bl") class engine as device tensors, with no host copy in
@@ -824,6 +844,9 @@ def generate_lead_and_run_mix(mix: Dict[str, Any], kind: str = "ab", engines=Non
     kind "bl" takes a mix made with controller="bl", or applies settings.Settings_BL to the classes of an ABMPC mix.
     engines = (tv_engine, ego_engine) reuses class handles (their class maps are set here).  The controllers share the sample
     grid, so a class whose TV_Ts differs from the Tvec[0] of its ABMPC settings is refused, not resampled.
+    preview=True: the traces assembled here (the generated lead, or the mix's own rows where the instance keeps them) are also
+    every controller's guess of its lead's future, through run_classes_preview of the ego class engine with n_lead = n_steps,
+    for both kinds; an instance without a lead (+inf) has none at any stage.
     Returns (traj, status, s_tv, v_tv): the ego closed loop and the [n_steps, B] lead traces it was fed."""
     from .settings import Settings_BL
     if kind not in ("ab", "bl"):
@@ -861,7 +884,7 @@ def generate_lead_and_run_mix(mix: Dict[str, Any], kind: str = "ab", engines=Non
     gen = t.as_tensor(generated[class_of], device=tv.device)[None, :]
     s_tv = t.where(gen, lead[:, OUT["s"], :] - per("TVlength")[None, :], t.as_tensor(mix["s_tv"], **f64)).contiguous()      # Main.m:88
     v_tv = t.where(gen, lead[:, OUT["v"], :], t.as_tensor(mix["v_tv"], **f64)).contiguous()
-    run = ego.run_blmpc if kind == "bl" else ego.run_abmpc
+    run = ego.run_classes_preview if preview else ego.run_blmpc if kind == "bl" else ego.run_abmpc
     traj, status = run(mix["s0"], mix["v0"], mix["a_minus1"], s_tv, v_tv)
     return traj, status, s_tv, v_tv
 

@@ -272,8 +272,9 @@ int  eepacc_ab_step(eepacc_handle* h, int B,
  * n_lead < n_steps.  B = 0 returns EEPACC_OK.
  * The baseline controller's counterparts are eepacc_bl_step_est, eepacc_bl_build_qp_est and eepacc_run_blmpc_preview, below; on a
  * bl_mode = 1 handle the message of these three entries points to them.
- * Not built: supplied guesses for FBMPC, for class handles, for the target-vehicle controller, for move blocking and the ICE
- * map, and a preview of the ego estimate.
+ * Class handles have entries of their own, eepacc_classes_step_est and eepacc_run_classes_preview, below.
+ * Not built: supplied guesses for FBMPC, for the target-vehicle controller, for move blocking and the ICE map, and a preview
+ * of the ego estimate.
  * Cost against eepacc_ab_step / eepacc_run_abmpc: tools/gpu_ab_est_bench.py, DESIGN.md section 3.4f. */
 int  eepacc_ab_step_est(eepacc_handle* h, int B,
                         const double* s, const double* v, const double* a_prev, const double* t0,
@@ -604,6 +605,32 @@ int  eepacc_run_blmpc_preview(eepacc_handle* h, int B, int n_steps, int n_lead,
                               const double* s0, const double* v0, const double* a_minus1,
                               const double* s_tv, const double* v_tv,
                               double* traj, int32_t* status, void* stream);
+
+/* Supplied horizon guesses on a handle with settings classes: eepacc_ab_step_est / eepacc_bl_step_est and
+ * eepacc_run_abmpc_preview / eepacc_run_blmpc_preview for the mixed launch, with their arguments, layouts, NULL rules and
+ * preview rule unchanged.  The handle decides the controller: one of eepacc_create_classes runs ABMPC (kernels clsest), one of
+ * eepacc_create_classes_bl with bl_mode = 1 the baseline controller (kernels blclsest); every instance is solved with the
+ * settings of its class in eepacc_set_classes' map, as in eepacc_ab_step / eepacc_run_abmpc on the same handle.  They read and
+ * write exactly the handle state those entries do (warm start, carried predictions, closed-loop carry, iteration counts), so
+ * they alternate freely with eepacc_ab_step, eepacc_run_abmpc and eepacc_run_blmpc on one handle; a resumed
+ * eepacc_run_classes_preview passes the continued rows of the traces.  With s_est, v_est and s_tv_est all NULL
+ * eepacc_classes_step_est computes what eepacc_ab_step computes on the handle, bit for bit.  The preview tables are made once
+ * per handle from class 0's Tvec, which every class shares.
+ * EEPACC_ENOTSUP, the message naming the entry and the cause: a handle without classes (the message points to the plain
+ * entries of its mode); a class handle with bl_mode = 2 (no lead).  EEPACC_EINVAL: a call before eepacc_set_classes or with
+ * another B than the map's, s_est without v_est or the reverse, n_lead < n_steps, B outside [0, max_batch], a NULL required
+ * buffer.  B = 0 returns EEPACC_OK.  The six entries above keep refusing class handles, and the QP builders stay refused on
+ * them.
+ * Cost against twelve launches on plain handles: tools/gpu_classes_est_bench.py, DESIGN.md section 3.4h. */
+int  eepacc_classes_step_est(eepacc_handle* h, int B,
+                             const double* s, const double* v, const double* a_prev, const double* t0,
+                             const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                             const double* s_est, const double* v_est, const double* s_tv_est,
+                             double* out, double* s_pred, double* v_pred, int32_t* status, void* stream);
+int  eepacc_run_classes_preview(eepacc_handle* h, int B, int n_steps, int n_lead,
+                                const double* s0, const double* v0, const double* a_minus1,
+                                const double* s_tv, const double* v_tv,
+                                double* traj, int32_t* status, void* stream);
 
 /* Target-vehicle MPC by name: [s_opt, v_opt, numSolverErrors] = RunOpt_TVMPC(OPTsettings) (ABO/RunOpt_TVMPC.m:1,
  * ABO/Main.m:85) and the body of its loop (:156-277).  They require a handle created with bl_mode = 2 (EEPACC_EINVAL
