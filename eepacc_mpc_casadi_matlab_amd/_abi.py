@@ -73,6 +73,14 @@ CLASSES_EST_ARGTYPES = {
     "eepacc_run_classes_preview": list(AB_EST_ARGTYPES["eepacc_run_abmpc_preview"]),
 }
 
+# the condensed QP of a step as data on a handle with settings classes: size and rows as the ab_ / bl_ entries (the rows of one
+# class, cls, padded with -1 to the handle's nC), the build with the arguments of eepacc_ab_build_qp_est
+CLASSES_BUILD_ARGTYPES = {
+    "eepacc_classes_qp_size": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "eepacc_classes_qp_rows": [C.c_void_p, C.c_int, c_int32_p, c_int32_p],
+    "eepacc_classes_build_qp": list(AB_EST_ARGTYPES["eepacc_ab_build_qp_est"]),
+}
+
 # enum EEPACC_FB_ROW_*: the row types of eepacc_fb_qp_rows, ascending in the order of the rows within a stage
 FB_ROW_TYPES = ["s", "v", "fm", "fb", "xi_v", "xi_h", "xi_s", "xi_f", "blocked_fm", "blocked_fb", "tm_min", "tm_max",
                 "axle_min", "axle_max", "fric_max", "fric_min", "a_max", "a_min", "j_max", "j_min",

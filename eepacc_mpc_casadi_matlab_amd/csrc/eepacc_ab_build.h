@@ -35,4 +35,12 @@ hipError_t launch_ab_build_est(const DevCfg* cfg, int N, int nC, int B, const do
                                double* H, double* g, double* A, double* lba, double* uba, hipStream_t stream,
                                const AbSupplied& sup);
 
+// the same on a handle with settings classes (eepacc_ab_build_cls.hip, eepacc_classes_build_qp): cfg is the class array,
+// class_of the device map [B], nC the row count of the largest class (classes_qp_num_rows, eepacc_cfg.h): the leading row
+// dimension of A, lba, uba, padding rows behind an instance's own.  The members of sup may be null.
+hipError_t launch_ab_build_cls(const DevCfg* cfg, const int32_t* class_of, int N, int nC, int B, const double* s, const double* v,
+                               const double* a_prev, const double* t0, const double* s_tv, const double* v_tv,
+                               const double* a_tv_prev, double* H, double* g, double* A, double* lba, double* uba,
+                               hipStream_t stream, const AbSupplied& sup);
+
 }  // namespace eepacc

@@ -1,9 +1,13 @@
 // eepacc_ab_build_kernel.inc -- the kernel that writes the condensed QP of an ABMPC step, with what it alone uses.  Included
 // into an anonymous namespace by eepacc_ab_build.hip (k_ab_build: the estimators' horizon guesses) and by
-// eepacc_ab_build_est.hip (k_ab_build_est: the guesses of the caller), with three macros:
+// eepacc_ab_build_est.hip (k_ab_build_est: the guesses of the caller), with three macros, and by eepacc_ab_build_cls.hip
+// (k_ab_build_cls: a handle with settings classes) with a fourth:
 //   EEPACC_AB_BUILD_KERNEL       the kernel's name
 //   EEPACC_AB_BUILD_MORE_PARAMS  its parameters after uba (with the leading comma), empty in k_ab_build
 //   EEPACC_AB_BUILD_SUPPLIED     the statement that puts the caller's guesses of stage k in place of the estimates, empty there
+//   EEPACC_AB_BUILD_CLASSES      defined: cfg is the class array and class_of (among the further parameters) the class of every
+//                                instance; the workgroup takes the settings of its instance's class, nC is the row count of the
+//                                largest class and the rows behind the class's own are padding (eepacc_qp_build.h)
 // One kernel per translation unit: a second caller of the helpers below in the same unit changes what the compiler inlines
 // into the first, and k_ab_build is to keep its code (profiles/est_codegen.txt).
 struct Stages {                      // per-stage quantities of the step, static LDS
@@ -62,7 +66,15 @@ __global__ void __launch_bounds__(BT) EEPACC_AB_BUILD_KERNEL(const DevCfg* __res
                                                  double* __restrict__ lba, double* __restrict__ uba EEPACC_AB_BUILD_MORE_PARAMS) {
     extern __shared__ __align__(16) unsigned char smem[];
     __shared__ Stages S;
+#ifdef EEPACC_AB_BUILD_CLASSES
+    // the index is uniform over the workgroup, so the settings stay scalar loads; N and Tvec, and with them the LDS geometry,
+    // are every class's alike, the row count and ab_route_rows the class's own (class handles have no move blocking)
+    const DevCfg& C = cfg[class_of[blockIdx.x]];
+    const int n_own = (C.ab_route_rows ? 18 : 14) * C.N + 2;
+#else
     const DevCfg& C = *cfg;
+    const int n_own = nC;
+#endif
     const int N = C.N, nV = 5 * N, tid = threadIdx.x;
     const size_t b = blockIdx.x;
     const int ld = N | 1;
@@ -107,6 +119,9 @@ __global__ void __launch_bounds__(BT) EEPACC_AB_BUILD_KERNEL(const DevCfg* __res
     __syncthreads();
 
     // ---- position sensitivities and free response; suffix sums and the a-a diagonal; the row catalogue
+#ifdef EEPACC_AB_BUILD_CLASSES
+    fill_pad_rows(rows, n_own, nC, tid);
+#endif
     if (tid <= N) {
         const int k = tid;
         S.ds[k] = di_position_row(S.T, Ss, ld, k, s_0, v_0);
@@ -120,7 +135,7 @@ __global__ void __launch_bounds__(BT) EEPACC_AB_BUILD_KERNEL(const DevCfg* __res
             fill_stage_rows(rows, r, k, EEPACC_AB_ROW_N,
                             [&](int type, int kk) { return ab_row_present(type, C.ab_route_rows, C.mb_mask[kk]); });
         } else {
-            fill_terminal_rows(rows, nC, N, EEPACC_AB_ROW_SAFE1, EEPACC_AB_ROW_SAFE2);
+            fill_terminal_rows(rows, n_own, N, EEPACC_AB_ROW_SAFE1, EEPACC_AB_ROW_SAFE2);
         }
     } else if (tid == 64) {
         double acc = 0.0;
@@ -157,9 +172,15 @@ __global__ void __launch_bounds__(BT) EEPACC_AB_BUILD_KERNEL(const DevCfg* __res
         g[b * (size_t)nV + col] = gv;
     }
     // ---- lba, uba, A
+#ifdef EEPACC_AB_BUILD_CLASSES
+    const auto decode = [&](int e) { return row_is_pad(e) ? di_row_blank(0, -1) : ab_row(C, S, row_stage(e), row_type(e), a_minus1); };
+    write_bounds(lba + b * (size_t)nC, uba + b * (size_t)nC, rows, nC, tid,
+                 [&](int e) { return row_is_pad(e) ? RowBounds{-INFINITY, INFINITY, 0.0} : di_bounds(decode(e), S.ds, v_0); });
+#else
     const auto decode = [&](int e) { return ab_row(C, S, row_stage(e), row_type(e), a_minus1); };
     write_bounds(lba + b * (size_t)nC, uba + b * (size_t)nC, rows, nC, tid,
                  [&](int e) { return di_bounds(decode(e), S.ds, v_0); });
+#endif
     write_A<1, 4>(A + b * (size_t)nV * nC, rows, N, nC, tid, decode,
                   [&](const Row& R, int k, int i, double* x) { x[0] = di_A_entry(R, Ss, ld, S.T, k, i); });
 }

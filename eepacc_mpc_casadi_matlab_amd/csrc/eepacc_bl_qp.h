@@ -31,4 +31,11 @@ hipError_t launch_bl_qp_est(const DevCfg* cfg, int N, int nC, int B, const doubl
                             double* H, double* g, double* A, double* lba, double* uba, hipStream_t stream,
                             const AbSupplied& sup);
 
+// the same on a handle with settings classes (eepacc_bl_qp_cls.hip, eepacc_classes_build_qp): cfg is the class array, class_of
+// the device map [B]; the classes share bl_mode and so nC.  The members of sup may be null, and are with bl_mode = 2.
+hipError_t launch_bl_qp_cls(const DevCfg* cfg, const int32_t* class_of, int N, int nC, int B, const double* s, const double* v,
+                            const double* a_prev, const double* t0, const double* s_tv, const double* v_tv,
+                            const double* a_tv_prev, double* H, double* g, double* A, double* lba, double* uba,
+                            hipStream_t stream, const AbSupplied& sup);
+
 }  // namespace eepacc

@@ -1,9 +1,13 @@
 // eepacc_bl_qp_kernel.inc -- the kernel that writes the condensed QP of a BLMPC or TVMPC step, with what it alone uses.
 // Included into an anonymous namespace by eepacc_bl_qp.hip (k_bl_qp: the estimators' horizon guesses) and by
-// eepacc_bl_qp_est.hip (k_bl_qp_est: the guesses of the caller, bl_mode = 1 only), with three macros:
+// eepacc_bl_qp_est.hip (k_bl_qp_est: the guesses of the caller, bl_mode = 1 only), with three macros, and by
+// eepacc_bl_qp_cls.hip (k_bl_qp_cls: a handle with settings classes) with a fourth:
 //   EEPACC_BL_QP_KERNEL       the kernel's name
 //   EEPACC_BL_QP_MORE_PARAMS  its parameters after uba (with the leading comma), empty in k_bl_qp
 //   EEPACC_BL_QP_SUPPLIED     the statement that puts the caller's guesses of stage k in place of the estimates, empty there
+//   EEPACC_BL_QP_CLASSES      defined: cfg is the class array and class_of (among the further parameters) the class of every
+//                             instance; the workgroup takes the settings of its instance's class.  The classes of a handle share
+//                             bl_mode and N and so the row count: there are no padding rows
 // One kernel per translation unit, as eepacc_ab_build_kernel.inc: k_bl_qp is to keep its code (profiles/blest_codegen.txt).
 struct Stages {                      // per-stage quantities of the step, static LDS
     double T[kS], stv[kS], ds[kS];
@@ -48,7 +52,11 @@ __global__ void __launch_bounds__(BT) EEPACC_BL_QP_KERNEL(const DevCfg* __restri
                                               double* __restrict__ lba, double* __restrict__ uba EEPACC_BL_QP_MORE_PARAMS) {
     extern __shared__ __align__(16) unsigned char smem[];
     __shared__ Stages S;
+#ifdef EEPACC_BL_QP_CLASSES
+    const DevCfg& C = cfg[class_of[blockIdx.x]];            // uniform over the workgroup: the settings stay scalar loads
+#else
     const DevCfg& C = *cfg;
+#endif
     const int N = C.N, nV = 2 * N, tid = threadIdx.x;
     const bool tv = C.bl_mode == 2;
     const size_t b = blockIdx.x;

@@ -92,6 +92,7 @@ struct eepacc_handle {
     int n_classes = 0;
     DevMem<int32_t> d_class_of;              // [max_batch] class of every instance
     int classes_B = 0;                       // B of the last eepacc_set_classes (0: none yet)
+    std::vector<eepacc::QpRowsCfg> qp_rows;  // [n_classes] what the row catalogue of eepacc_classes_build_qp reads of every class
     // key figures (eepacc_kpis): what they read of every class, and the cut-off distances of the call in flight
     DevMem<KpiCfg> d_kpi;                    // [max(n_classes, 1)]
     DevMem<double> d_kpi_cut;                // [max(n_classes, 1)]
@@ -166,6 +167,7 @@ static int create_on_device(eepacc_handle** out, std::vector<DevCfg>& Cs, const 
     HIPCHK(hipMemcpy(h->d_route, Rs.data(), Rs.size() * sizeof(RouteCfg), hipMemcpyHostToDevice));
     if (classes) {
         h->n_classes = (int)Cs.size();
+        for (const DevCfg& Ck : Cs) h->qp_rows.push_back(eepacc::qp_rows_cfg(Ck));
         HIPCHK(h->d_class_of.alloc_zero(nB));
     }
     HIPCHK(h->d_codes.alloc_zero(nB * 64));
@@ -692,6 +694,69 @@ extern "C" int eepacc_bl_build_qp(eepacc_handle* h, int B, const double* s, cons
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(eepacc::launch_bl_qp(h->d_cfg, h->cfg.N, eepacc::bl_qp_num_rows(h->cfg), B, s, v, a_prev, t0, tv ? nullptr : s_tv,
                                 tv ? nullptr : v_tv, tv ? nullptr : a_tv_prev, H, g, A, lba, uba, (hipStream_t)stream));
+    return EEPACC_OK;
+}
+
+// ---- the same on a handle with settings classes: eepacc_classes_qp_size, _qp_rows, _build_qp serve class handles only, of
+// either creation entry; the nine entries above keep refusing them.  The catalogue (per-class rows, padding up to the largest
+// class) is eepacc_cfg.cpp's.
+static int classes_qp_handle(const eepacc_handle* h, const std::string& who) {
+    if (!h) return fail(EEPACC_EINVAL, who + ": NULL handle");
+    if (!h->n_classes) {
+        const char* plain = h->cfg.bl_mode ? "eepacc_bl_qp_size, eepacc_bl_qp_rows and eepacc_bl_build_qp / eepacc_bl_build_qp_est build the problem of such a handle"
+                                           : "eepacc_ab_qp_size, eepacc_ab_qp_rows and eepacc_ab_build_qp / eepacc_ab_build_qp_est build the problem of such a handle";
+        return fail(EEPACC_ENOTSUP, who + ": this handle has no settings classes (it was created by eepacc_create with bl_mode = " +
+                                        std::to_string(h->cfg.bl_mode) + "); " + plain);
+    }
+    return EEPACC_OK;
+}
+
+extern "C" int eepacc_classes_qp_size(const eepacc_handle* h, int* nV, int* nC) {
+    const std::string who = "eepacc_classes_qp_size";
+    if (const int rc = classes_qp_handle(h, who)) return rc;
+    if (!nV) return fail(EEPACC_EINVAL, who + ": nV is NULL");
+    if (!nC) return fail(EEPACC_EINVAL, who + ": nC is NULL");
+    *nV = (h->cfg.bl_mode ? kQpBL.nV_stage : kQpAB.nV_stage) * h->cfg.N;
+    *nC = eepacc::classes_qp_max_rows(h->qp_rows.data(), h->n_classes);
+    return EEPACC_OK;
+}
+
+extern "C" int eepacc_classes_qp_rows(const eepacc_handle* h, int cls, int32_t* stage, int32_t* type) {
+    const std::string who = "eepacc_classes_qp_rows";
+    if (const int rc = classes_qp_handle(h, who)) return rc;
+    if (!stage) return fail(EEPACC_EINVAL, who + ": stage is NULL");
+    if (!type) return fail(EEPACC_EINVAL, who + ": type is NULL");
+    return eepacc::classes_qp_rows(h->qp_rows.data(), h->n_classes, cls, stage, type);
+}
+
+extern "C" int eepacc_classes_build_qp(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
+                                       const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                                       const double* s_est, const double* v_est, const double* s_tv_est,
+                                       double* H, double* g, double* A, double* lba, double* uba, void* stream) {
+    const std::string who = "eepacc_classes_build_qp";
+    if (const int rc = classes_qp_handle(h, who)) return rc;
+    const bool tv = h->cfg.bl_mode == 2;                   // no lead vehicle: the three lead arrays are not read
+    if (tv && (s_est || v_est || s_tv_est))
+        return fail(EEPACC_ENOTSUP, who + ": the classes of this handle were created with bl_mode = 2 (RunOpt_TVMPC); the target-vehicle controller has no lead and hands its bounds a zero speed estimate, so supplied horizon guesses are not built for it");
+    if (B < 0 || B > h->max_batch)
+        return fail(EEPACC_EINVAL, who + ": B = " + std::to_string(B) + " is outside [0, max_batch = " + std::to_string(h->max_batch) + "]");
+    if (B == 0) return EEPACC_OK;
+    const struct { const void* p; const char* name; bool needed; } bufs[] = {
+        {s, "s", true}, {v, "v", true}, {a_prev, "a_prev", true}, {t0, "t0", true}, {s_tv, "s_tv", !tv}, {v_tv, "v_tv", !tv},
+        {a_tv_prev, "a_tv_prev", !tv}, {H, "H", true}, {g, "g", true}, {A, "A", true}, {lba, "lba", true}, {uba, "uba", true}};
+    for (const auto& bf : bufs)
+        if (bf.needed && !bf.p) return fail(EEPACC_EINVAL, who + ": " + bf.name + " is NULL");
+    if (const int rc = est_pair(who, s_est, v_est)) return rc;
+    if (const int rc = classes_ready(h, who.c_str(), B)) return rc;
+    const eepacc::AbSupplied sup{s_est, v_est, s_tv_est};
+    const int nC = eepacc::classes_qp_max_rows(h->qp_rows.data(), h->n_classes);
+    HIPCHK(hipSetDevice(h->device));
+    if (h->cfg.bl_mode)
+        HIPCHK(eepacc::launch_bl_qp_cls(h->d_cfg, h->d_class_of, h->cfg.N, nC, B, s, v, a_prev, t0, tv ? nullptr : s_tv,
+                                        tv ? nullptr : v_tv, tv ? nullptr : a_tv_prev, H, g, A, lba, uba, (hipStream_t)stream, sup));
+    else
+        HIPCHK(eepacc::launch_ab_build_cls(h->d_cfg, h->d_class_of, h->cfg.N, nC, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev,
+                                           H, g, A, lba, uba, (hipStream_t)stream, sup));
     return EEPACC_OK;
 }
 

@@ -4,6 +4,7 @@
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include "eepacc_cfg.h"
 
 namespace eepacc {
@@ -268,6 +269,47 @@ RouteCfg build_route_cfg(const eepacc_settings* S, const eepacc_vehicle*) {
     R.TLstopVel = S->TLstopVel; R.TLStopRegionSize = S->TLStopRegionSize;
     R.bl_aLo = S->BL_a_LimLowVel; R.bl_aHi = S->BL_a_LimHighVel; R.bl_jLo = S->BL_j_LimLowVel; R.bl_jHi = S->BL_j_LimHighVel;
     return R;
+}
+
+// ---- the row catalogue of eepacc_classes_build_qp.  A class has the rows of the plain builder of its controller
+// (eepacc_ab_qp_rows, eepacc_bl_qp_rows): per stage the present types in ascending order, then the two terminal rows where the
+// controller has a lead.  Class handles have no move blocking, so EEPACC_AB_ROW_BLOCKED is never present.
+QpRowsCfg qp_rows_cfg(const DevCfg& C) { return QpRowsCfg{C.N, C.bl_mode, C.ab_route_rows}; }
+
+static bool class_row_present(const QpRowsCfg& c, int type) {
+    if (c.bl_mode) return c.bl_mode != 2 || type < EEPACC_BL_ROW_SAFE1;
+    if (type == EEPACC_AB_ROW_BLOCKED) return false;
+    if (type >= EEPACC_AB_ROW_V_LIM && type <= EEPACC_AB_ROW_V_TL) return c.ab_route_rows != 0;
+    return true;
+}
+
+int classes_qp_num_rows(const QpRowsCfg& c) {
+    if (c.bl_mode) return c.bl_mode == 2 ? 11 * c.N : 13 * c.N + 2;
+    return (c.ab_route_rows ? 18 : 14) * c.N + 2;
+}
+
+int classes_qp_max_rows(const QpRowsCfg* c, int n_classes) {
+    int nC = 0;
+    for (int k = 0; k < n_classes; ++k) nC = std::max(nC, classes_qp_num_rows(c[k]));
+    return nC;
+}
+
+int classes_qp_rows(const QpRowsCfg* c, int n_classes, int cls, int32_t* stage, int32_t* type) {
+    if (cls < 0 || cls >= n_classes)
+        return fail(EEPACC_EINVAL, "eepacc_classes_qp_rows: cls = " + std::to_string(cls) + " is outside [0, " + std::to_string(n_classes) + ")");
+    const QpRowsCfg& q = c[cls];
+    const int nC = classes_qp_max_rows(c, n_classes);
+    const int n_types = q.bl_mode ? (int)EEPACC_BL_ROW_N : (int)EEPACC_AB_ROW_N;
+    int r = 0;
+    for (int k = 0; k < q.N; ++k)
+        for (int t = 0; t < n_types; ++t)
+            if (class_row_present(q, t)) { stage[r] = k; type[r] = t; ++r; }
+    if (q.bl_mode != 2) {
+        stage[r] = q.N; type[r] = q.bl_mode ? (int)EEPACC_BL_ROW_SAFE1 : (int)EEPACC_AB_ROW_SAFE1; ++r;
+        stage[r] = q.N; type[r] = q.bl_mode ? (int)EEPACC_BL_ROW_SAFE2 : (int)EEPACC_AB_ROW_SAFE2; ++r;
+    }
+    for (; r < nC; ++r) stage[r] = type[r] = -1;
+    return EEPACC_OK;
 }
 
 }  // namespace eepacc

@@ -34,5 +34,17 @@ KpiCfg build_kpi_cfg(const eepacc_settings* S, const eepacc_vehicle* V);
 FollowCfg build_follow_cfg(const eepacc_settings* S, const eepacc_vehicle* V);
 RouteCfg build_route_cfg(const eepacc_settings* S, const eepacc_vehicle* V);
 
+// The row catalogue of eepacc_classes_build_qp, for a handle's launcher and eepacc_classes_qp_rows alike.  What it depends on of
+// a class that create_classes has accepted (no move blocking; N and bl_mode agree over the classes of a handle):
+struct QpRowsCfg { int32_t N, bl_mode, ab_route_rows; };
+QpRowsCfg qp_rows_cfg(const DevCfg& C);
+// Rows of a class's own problem: 14 N + 2 or 18 N + 2 (ABMPC without / with ab_route_rows), 13 N + 2 (bl_mode 1), 11 N (2)
+int classes_qp_num_rows(const QpRowsCfg& c);
+// nC of the handle: the largest of its classes, the leading row dimension of every instance's A, lba, uba
+int classes_qp_max_rows(const QpRowsCfg* c, int n_classes);
+// stage, type [nC of the handle]: the rows of class cls as eepacc_ab_qp_rows / eepacc_bl_qp_rows order them, then -1 in both
+// for the padding rows up to nC.  EEPACC_EINVAL (through set_error): cls outside [0, n_classes).
+int classes_qp_rows(const QpRowsCfg* c, int n_classes, int cls, int32_t* stage, int32_t* type);
+
 }  // namespace eepacc
 #endif

@@ -48,6 +48,16 @@ __device__ inline void fill_terminal_rows(unsigned short* rows, int nC, int N, i
     rows[nC - 1] = row_code(N, safe2);
 }
 
+// Padding (k_ab_build_cls): where the instances of a launch differ in their row count, the arrays have the leading row
+// dimension nC of the largest and an instance with n_own rows carries nC - n_own padding rows behind its own.  They are
+// entries of the row list like any other, of a type no controller has, so the walks over the bounds and A write them on their
+// way: a blank row (every coefficient 0.0, no slack) with the bounds below, which no finite x violates.
+constexpr int kRowPad = 0xff;
+__device__ inline bool row_is_pad(int e) { return row_type(e) == kRowPad; }
+__device__ inline void fill_pad_rows(unsigned short* rows, int n_own, int nC, int tid) {
+    for (int r = n_own + tid; r < nC; r += BT) rows[r] = row_code(0, kRowPad);
+}
+
 // Ego estimate of stage k.  pred(idx, ps, pv) supplies the previous step's predictions of stage idx for paramEstSetting 2.
 template <class Pred>
 __device__ inline void ego_estimate(const DevCfg& C, double s_0, double v_0, double a_minus1, int k, Pred pred,

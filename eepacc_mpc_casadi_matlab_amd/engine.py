@@ -13,7 +13,7 @@ from typing import Any, Dict, NamedTuple, Optional
 
 import numpy as np
 
-from ._abi import (SettingsHolder, SettingsPOD, Vehicle, make_vehicle, pack_classes, OUT, OUT_N, OUT_FIELDS, KPI_N, FKPI_N, FKPI_WEIGHTS, RKPI_N, RLIM_N, ROUTE_KPIS_ARGTYPES, AB_BUILD_ARGTYPES, AB_EST_ARGTYPES, BL_EST_ARGTYPES, CLASSES_EST_ARGTYPES,
+from ._abi import (SettingsHolder, SettingsPOD, Vehicle, make_vehicle, pack_classes, OUT, OUT_N, OUT_FIELDS, KPI_N, FKPI_N, FKPI_WEIGHTS, RKPI_N, RLIM_N, ROUTE_KPIS_ARGTYPES, AB_BUILD_ARGTYPES, AB_EST_ARGTYPES, BL_EST_ARGTYPES, CLASSES_EST_ARGTYPES, CLASSES_BUILD_ARGTYPES,
                    FB_BUILD_ARGTYPES, BL_BUILD_ARGTYPES,
                    c_double_p, as_dptr, as_iptr)
 
@@ -75,7 +75,7 @@ def load_library() -> C.CDLL:
     lib.eepacc_qp_solve_batched_dual.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [dp] * 8 + [dp, dp] + [dp] * 3 + [dp] * 5 + [vp]
     lib.eepacc_qp_kkt_solve_batched.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int] + [dp] * 2 + [dp] * 2 + [dp] * 3 + [dp] * 3 + [dp, vp]
     for name, argtypes in (list(AB_BUILD_ARGTYPES.items()) + list(FB_BUILD_ARGTYPES.items()) + list(BL_BUILD_ARGTYPES.items())
-                           + list(AB_EST_ARGTYPES.items()) + list(BL_EST_ARGTYPES.items()) + list(CLASSES_EST_ARGTYPES.items())):
+                           + list(AB_EST_ARGTYPES.items()) + list(BL_EST_ARGTYPES.items()) + list(CLASSES_EST_ARGTYPES.items()) + list(CLASSES_BUILD_ARGTYPES.items())):
         getattr(lib, name).argtypes = argtypes
     lib.eepacc_synchronize.argtypes = [vp, vp]
     lib.eepacc_build_flags.restype = C.c_char_p
@@ -96,6 +96,7 @@ ABI_SYMBOLS = ["eepacc_last_error", "eepacc_version", "eepacc_sizeof_settings", 
                "eepacc_bl_qp_size", "eepacc_bl_qp_rows", "eepacc_bl_build_qp",
                "eepacc_bl_step_est", "eepacc_bl_build_qp_est", "eepacc_run_blmpc_preview",
                "eepacc_classes_step_est", "eepacc_run_classes_preview",
+               "eepacc_classes_qp_size", "eepacc_classes_qp_rows", "eepacc_classes_build_qp",
                "eepacc_synchronize", "eepacc_build_flags"]
 
 
@@ -177,6 +178,7 @@ class Engine:
         h = C.c_void_p()
         _check(self.lib.eepacc_create(C.byref(h), C.byref(self.holder.pod), C.byref(self.veh), device, max_batch))
         self.h = h
+        self.class_of = None                 # an engine of from_classes: the map of the last set_classes
 
     @classmethod
     def from_classes(cls, OPT_list, V_list, device: int = 0, max_batch: int = 4096) -> "Engine":
@@ -207,6 +209,7 @@ class Engine:
         create = self.lib.eepacc_create_classes_bl if modes[0] in (1, 2) else self.lib.eepacc_create_classes
         _check(create(C.byref(h), S, self.veh, len(OPT_list), device, max_batch))
         self.h = h
+        self.class_of = None
         return self
 
     def set_classes(self, class_of):
@@ -214,6 +217,7 @@ class Engine:
         len(class_of)).  Resets the carried loop state like reset()."""
         m = np.ascontiguousarray(np.asarray(class_of).reshape(-1), dtype=np.int32)
         _check(self.lib.eepacc_set_classes(self.h, int(m.size), as_iptr(m)))
+        self.class_of = m.copy()
 
     @property
     def num_classes(self) -> int:
@@ -424,6 +428,37 @@ class Engine:
         if len(shape(s_tv)) != 2 or shape(s_tv) != shape(v_tv):
             raise ValueError("s_tv and v_tv are [n_lead, B] both, got %s and %s" % (shape(s_tv), shape(v_tv)))
         return self._run_preview(self.lib.eepacc_run_classes_preview, s0, v0, a_minus1, s_tv, v_tv, n_steps, resume, out)
+
+    # the condensed QP of a step as data on an engine of from_classes: one launch for the mixed batch ----------------------
+    def classes_qp_size(self):
+        """eepacc_classes_qp_size: (nV, nC) of the problems classes_build_qp writes; nC is the row count of the largest class,
+        the leading row dimension of every instance."""
+        return self._qp_size(self.lib.eepacc_classes_qp_size)
+
+    def classes_qp_rows(self, cls: int):
+        """eepacc_classes_qp_rows: (stage, type) of class cls, two int32 arrays [nC] as ab_qp_rows / bl_qp_rows give them for
+        an engine of that class's settings; behind the class's own rows both hold -1 (padding rows)."""
+        _, nC = self.classes_qp_size()
+        stage = np.empty(nC, dtype=np.int32); typ = np.empty(nC, dtype=np.int32)
+        _check(self.lib.eepacc_classes_qp_rows(self.h, int(cls), as_iptr(stage), as_iptr(typ)))
+        return stage, typ
+
+    def classes_build_qp(self, s, v, a_prev, t0, s_tv=None, v_tv=None, a_tv_prev=None, s_est=None, v_est=None, s_tv_est=None):
+        """eepacc_classes_build_qp: ab_build_qp_est / bl_build_qp_est for an engine with settings classes, the problem of
+        every instance with the settings of its class in set_classes' map.  Arguments as ab_build_qp_est; None keeps the
+        estimators of the instance's class; target-vehicle classes take None for the lead arrays and no supplied guesses.
+        Returns AbQp (ABMPC classes) or BlQp with nC of classes_qp_size: over its class's own rows an instance holds what
+        the plain engine of its class builds, bit for bit, its padding rows (classes_qp_rows: -1) A = 0, lba = -inf,
+        uba = +inf.  Reads the engine's state and writes none of it."""
+        self._est_check(s, s_est, v_est, s_tv_est)
+        t = self.torch
+        B = int(t.as_tensor(s).numel())
+        ins = [None if x is None else self._d(x, B) for x in (s, v, a_prev, t0, s_tv, v_tv, a_tv_prev)]
+        est = self._est(B, s_est, v_est, s_tv_est)
+        nV, nC = self.classes_qp_size()
+        ptrs, qp = self._qp_outputs(B, nV, nC)
+        _check(self.lib.eepacc_classes_build_qp(self.h, B, *[_ptr(x) for x in ins + est], *ptrs, self._stream()))
+        return (AbQp if nV == 5 * self.N else BlQp)(*qp)
 
     # B1 ------------------------------------------------------------------------------------
     def run_abmpc(self, s0, v0, a_minus1, s_tv, v_tv, resume: bool = False, out=None, by_name_bl: bool = False):

@@ -221,14 +221,30 @@ def lead_gradient_from_uba(g_uba, stage, typ, N):
     return g_uba @ g_uba.new_tensor(sel)
 
 
-def ab_lead_gradient(eng, qp, sol, rows, gx):
+def ab_lead_gradient(eng, qp, sol, rows, gx, solver=None):
     """Gradient of a scalar loss on the solution x of an ABMPC step with respect to the lead prediction s_tv_est: [B, N+1]
     (device tensor; row N_hor of s_tv_est is not read, its entry is 0).  qp: the AbQp of eng.ab_build_qp_est (or
     ab_build_qp), sol: the QpDualResult of eng.qp_solve_batched_dual on it, rows: eng.ab_qp_rows(), gx [B, nV]: dL/dx
     (x[0] is the applied acceleration EEPACC_OUT_AQP).  One adjoint solve (qp_vjp), then lead_gradient_from_uba.  Exactly 0
-    for a stage none of whose lead rows is in the working set; NaN where qp_vjp gives NaN."""
-    gr = qp_vjp(eng, sol, qp.H, qp.A, gx)
-    return lead_gradient_from_uba(gr["uba"], rows[0], rows[1], eng.N)
+    for a stage none of whose lead rows is in the working set; NaN where qp_vjp gives NaN.
+    On an engine of from_classes with ABMPC classes qp is the AbQp of eng.classes_build_qp and rows is not read (None will do):
+    every instance is summed over the lead rows of the catalogue of its own class (eng.classes_qp_rows), so the mix of a
+    launch is differentiated in one adjoint solve; padding rows have no type and contribute nothing.  solver: the engine
+    whose dense QP operator solved the problem and runs the adjoint solve (default eng); a class engine has no dense operator
+    of its own, so any ordinary Engine on the same device is named here."""
+    gr = qp_vjp(solver if solver is not None else eng, sol, qp.H, qp.A, gx)
+    class_of = getattr(eng, "class_of", None)
+    if class_of is None:
+        return lead_gradient_from_uba(gr["uba"], rows[0], rows[1], eng.N)
+    if qp.H.shape[1] != 5 * eng.N:
+        raise ValueError("ab_lead_gradient differentiates the ABMPC problem; the classes of this engine are baseline or target-vehicle settings")
+    g_uba = gr["uba"]
+    out = g_uba.new_zeros((g_uba.shape[0], eng.N + 1))
+    for c in np.unique(class_of):
+        idx = eng.torch.as_tensor(np.nonzero(class_of == c)[0], device=g_uba.device)
+        stage, typ = eng.classes_qp_rows(int(c))
+        out[idx] = lead_gradient_from_uba(g_uba[idx], stage, typ, eng.N)
+    return out
 
 
 _FUNCTION = None

@@ -619,8 +619,8 @@ int  eepacc_run_blmpc_preview(eepacc_handle* h, int B, int n_steps, int n_lead,
  * EEPACC_ENOTSUP, the message naming the entry and the cause: a handle without classes (the message points to the plain
  * entries of its mode); a class handle with bl_mode = 2 (no lead).  EEPACC_EINVAL: a call before eepacc_set_classes or with
  * another B than the map's, s_est without v_est or the reverse, n_lead < n_steps, B outside [0, max_batch], a NULL required
- * buffer.  B = 0 returns EEPACC_OK.  The six entries above keep refusing class handles, and the QP builders stay refused on
- * them.
+ * buffer.  B = 0 returns EEPACC_OK.  The six entries above keep refusing class handles, and so do the plain QP builder
+ * entries (eepacc_classes_build_qp, below, builds the problems of a class handle).
  * Cost against twelve launches on plain handles: tools/gpu_classes_est_bench.py, DESIGN.md section 3.4h. */
 int  eepacc_classes_step_est(eepacc_handle* h, int B,
                              const double* s, const double* v, const double* a_prev, const double* t0,
@@ -714,6 +714,41 @@ int  eepacc_bl_build_qp(eepacc_handle* h, int B,
                         const double* s, const double* v, const double* a_prev, const double* t0,
                         const double* s_tv, const double* v_tv, const double* a_tv_prev,
                         double* H, double* g, double* A, double* lba, double* uba, void* stream);
+
+/* The condensed QP of a step as data on a handle with settings classes: eepacc_ab_build_qp(_est) / eepacc_bl_build_qp(_est)
+ * for the mixed launch.  One launch writes the problem of every instance with the settings of its class in
+ * eepacc_set_classes' map: of a handle of eepacc_create_classes the ABMPC problem (nV = 5 N_hor), of one of
+ * eepacc_create_classes_bl the BLMPC or TVMPC problem (nV = 2 N_hor).  These three entries serve class handles only; the
+ * nine _qp_size, _qp_rows, _build_qp(_est) entries above keep refusing them.
+ *
+ * eepacc_classes_qp_size returns nV and nC of the handle.  ABMPC classes may differ in ab_route_rows and so in their row
+ * count (14 N_hor + 2 or 18 N_hor + 2; class handles have no Mb); nC is the count of the largest class and the leading row
+ * dimension of A, lba and uba for EVERY instance.  The classes of eepacc_create_classes_bl share bl_mode and so the count
+ * (13 N_hor + 2 or 11 N_hor).
+ * eepacc_classes_qp_rows fills two host arrays [nC] with the row catalogue of class cls: stage[i] and type[i] as
+ * eepacc_ab_qp_rows / eepacc_bl_qp_rows give them for a plain handle of that class's settings, in the same order, and behind
+ * the class's own rows -1 in both arrays: padding rows.
+ * eepacc_classes_build_qp: inputs as eepacc_ab_build_qp_est (device, [B]; s_est, v_est, s_tv_est device [N_hor+1][B] or NULL,
+ * s_est and v_est together or both NULL, NULL keeping the estimators of the instance's class).  Outputs, device,
+ * instance-major, in the layout eepacc_qp_solve_batched reads: H [B][nV*nV], g [B][nV], A [B][nV][nC] (column-major
+ * nC x nV), lba, uba [B][nC].  Over its class's own rows an instance holds, bit for bit, what the plain builder of a handle of
+ * that class's settings writes for it; its padding rows hold A exactly 0.0, lba = -inf, uba = +inf, so the dense QP operator
+ * takes the arrays as they are and returns padding rows with a zero multiplier and outside the working set.  Every byte of
+ * the five arrays is written by the one kernel (no memset, no second pass).  The handle's state is read (estimator mode 2:
+ * the carried predictions, as the plain builder), never written.  bl_mode = 2 classes take no lead inputs (s_tv, v_tv,
+ * a_tv_prev may be NULL).
+ * EEPACC_ENOTSUP, the message naming the entry and the cause: a handle without classes (the message names the plain builder
+ * to call); supplied arrays on bl_mode = 2 classes.  EEPACC_EINVAL: a call before eepacc_set_classes or with another B than
+ * the map's, B outside [0, max_batch], s_est without v_est or the reverse, a NULL required buffer, cls outside
+ * [0, eepacc_num_classes).  B = 0 returns EEPACC_OK.
+ * Cost against one plain launch per class and against a device fill: tools/gpu_classes_build_bench.py, DESIGN.md section 3.6d. */
+int  eepacc_classes_qp_size(const eepacc_handle* h, int* nV, int* nC);
+int  eepacc_classes_qp_rows(const eepacc_handle* h, int cls, int32_t* stage, int32_t* type);
+int  eepacc_classes_build_qp(eepacc_handle* h, int B,
+                             const double* s, const double* v, const double* a_prev, const double* t0,
+                             const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                             const double* s_est, const double* v_est, const double* s_tv_est,
+                             double* H, double* g, double* A, double* lba, double* uba, void* stream);
 
 /* Post-processing of a closed-loop trajectory (ABO/RunOpt_ABMPC.m:343-349): rpm, Tm,
  * fifth-order battery power P and cumulative energy E, all device [n_steps][B]. */
