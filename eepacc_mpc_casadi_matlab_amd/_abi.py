@@ -94,6 +94,14 @@ FB_BUILD_ARGTYPES = {
     "eepacc_fb_build_qp": [C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p] * 2 + [C.c_void_p] * 5 + [C.c_void_p] * 2 + [C.c_void_p],
 }
 
+# FBMPC with the horizon guesses supplied: the ten inputs of eepacc_fb_step, then s_est, v_est, s_tv_est (each may be None), then its
+# outputs; the build with the three guesses before the model; the closed loop with B, n_steps, n_lead
+FB_EST_ARGTYPES = {
+    "eepacc_fb_step_est": [C.c_void_p, C.c_int] + [C.c_void_p] * 10 + [C.c_void_p] * 3 + [C.c_void_p] * 4 + [C.c_void_p],
+    "eepacc_fb_build_qp_est": [C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p] * 3 + [C.c_void_p] * 2 + [C.c_void_p] * 5 + [C.c_void_p] * 2 + [C.c_void_p],
+    "eepacc_run_fbmpc_preview": list(AB_EST_ARGTYPES["eepacc_run_abmpc_preview"]),
+}
+
 # enum EEPACC_BL_ROW_*: the row types of eepacc_bl_qp_rows, ascending in the order of the rows within a stage (a handle created
 # with bl_mode = 2 has none of the two safe-distance types)
 BL_ROW_TYPES = ["s", "v", "xi_f", "a_min", "a_max", "j_min", "j_max", "v_lim", "v_curv", "v_stop", "v_tl", "safe1", "safe2"]

@@ -496,6 +496,21 @@ extern "C" int eepacc_classes_step_est(eepacc_handle* h, int B, const double* s,
     return step_est_impl(EstEntry::Classes, "eepacc_classes_step_est", h, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, s_est, v_est, s_tv_est, out, s_pred, v_pred, status, stream);
 }
 
+// The preview tables of the handle (eepacc::preview_tables), made at the first preview launch of any controller
+static int preview_tables_ready(eepacc_handle* h) {
+    if (h->d_pv_idx) return EEPACC_OK;
+    const int N = h->cfg.N;
+    std::vector<int32_t> idx((size_t)N);
+    std::vector<double> frac((size_t)N);
+    eepacc::preview_tables(h->cfg.Tvec, N, idx.data(), frac.data());        // (class handle: class 0's Tvec, which every class shares)
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(h->d_pv_frac.alloc((size_t)N));
+    HIPCHK(hipMemcpy(h->d_pv_frac, frac.data(), (size_t)N * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(h->d_pv_idx.alloc((size_t)N));
+    HIPCHK(hipMemcpy(h->d_pv_idx, idx.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice));
+    return EEPACC_OK;
+}
+
 static int run_preview_impl(EstEntry entry, const std::string& who, eepacc_handle* h, int B, int n_steps, int n_lead, const double* s0,
                             const double* v0, const double* a_minus1, const double* s_tv, const double* v_tv, double* traj,
                             int32_t* status, void* stream) {
@@ -505,17 +520,7 @@ static int run_preview_impl(EstEntry entry, const std::string& who, eepacc_handl
     if (n_lead < n_steps)
         return fail(EEPACC_EINVAL, who + ": n_lead = " + std::to_string(n_lead) + " is below n_steps = " + std::to_string(n_steps) + "; the lead traces hold at least the rows of the launch's steps");
     if (B == 0 || n_steps == 0) return EEPACC_OK;
-    if (!h->d_pv_idx) {
-        const int N = h->cfg.N;
-        std::vector<int32_t> idx((size_t)N);
-        std::vector<double> frac((size_t)N);
-        eepacc::preview_tables(h->cfg.Tvec, N, idx.data(), frac.data());        // (class handle: class 0's Tvec, which every class shares)
-        HIPCHK(hipSetDevice(h->device));
-        HIPCHK(h->d_pv_frac.alloc((size_t)N));
-        HIPCHK(hipMemcpy(h->d_pv_frac, frac.data(), (size_t)N * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(h->d_pv_idx.alloc((size_t)N));
-        HIPCHK(hipMemcpy(h->d_pv_idx, idx.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
+    if (const int rc = preview_tables_ready(h)) return rc;
     const eepacc::AbPreview pv{h->d_pv_idx, h->d_pv_frac, n_lead};
     return ab_run_impl(h, who.c_str(), (who + ": bad B / n_steps").c_str(), B, n_steps, s0, v0, a_minus1, s_tv, v_tv, traj, status, stream, &pv);
 }
@@ -611,8 +616,8 @@ static int qp_rows_impl(const QpFamily& F, const eepacc_handle* h, int32_t* stag
 struct QpBufs { const double *s, *v, *a_prev, *t0, *s_tv, *v_tv, *a_tv_prev, *H, *g, *A, *lba, *uba; };
 
 // Handle, B range, NULL buffers.  *launch: there is something to build (B > 0)
-static int build_args_check(const QpFamily& F, const eepacc_handle* h, int B, const QpBufs& b, bool* launch) {
-    const std::string who = std::string(F.stem) + "_build_qp";
+static int build_args_check(const QpFamily& F, const eepacc_handle* h, int B, const QpBufs& b, bool* launch, const char* entry = nullptr) {
+    const std::string who = entry ? std::string(entry) : std::string(F.stem) + "_build_qp";      // (entry: eepacc_fb_build_qp_est)
     *launch = false;
     if (const int rc = qp_handle(F, h, who)) return rc;
     if (B < 0 || B > h->max_batch)
@@ -1054,6 +1059,21 @@ static int fb_one_step(eepacc_handle* h, int B, int mode, const double* s, const
     return EEPACC_OK;
 }
 
+// One step of a structured handle: eepacc_fb_step (sup == NULL) and eepacc_fb_step_est, on the same handle state
+static int fbs_step_launch(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev, const double* t0,
+                           const double* s_tv, const double* v_tv, const double* a_tv_prev, double* out, double* s_pred,
+                           double* v_pred, int32_t* status, void* stream, const eepacc::AbSupplied* sup) {
+    eepacc::fbs_step_args a;
+    a.cfg = h->d_cfg; a.B = B; a.k_step = h->fb_k_done;
+    a.s = s; a.v = v; a.a_prev = a_prev; a.t0 = t0; a.s_tv = s_tv; a.v_tv = v_tv; a.a_tv_prev = a_tv_prev;
+    a.state = h->fbs_state; a.hb = h->fbs_hb; a.out = out; a.s_pred = s_pred; a.v_pred = v_pred;
+    a.status = status; a.iters = h->d_iters;
+    if (sup) HIPCHK(eepacc::launch_fbs_step_est(a, h->cfg.N, (hipStream_t)stream, sup->s_est, sup->v_est, sup->s_tv_est));
+    else HIPCHK(eepacc::launch_fbs_step(a, h->cfg.N, (hipStream_t)stream));
+    h->fb_k_done += 1; h->last_B = B; h->fb_by_step = true;
+    return EEPACC_OK;
+}
+
 extern "C" int eepacc_fb_step(eepacc_handle* h, int B, const double* s, const double* v, const double* v_prev,
                               const double* a_prev, const double* Fm_prev, const double* Fb_prev, const double* t0,
                               const double* s_tv, const double* v_tv, const double* a_tv_prev,
@@ -1066,16 +1086,8 @@ extern "C" int eepacc_fb_step(eepacc_handle* h, int B, const double* s, const do
     if (!s || !v || !a_prev || !t0 || !s_tv || !v_tv || !a_tv_prev || !out || !status)
         return fail(EEPACC_EINVAL, "eepacc_fb_step: NULL buffer");
     HIPCHK(hipSetDevice(h->device));
-    if (h->fbs) {
-        eepacc::fbs_step_args a;
-        a.cfg = h->d_cfg; a.B = B; a.k_step = h->fb_k_done;
-        a.s = s; a.v = v; a.a_prev = a_prev; a.t0 = t0; a.s_tv = s_tv; a.v_tv = v_tv; a.a_tv_prev = a_tv_prev;
-        a.state = h->fbs_state; a.hb = h->fbs_hb; a.out = out; a.s_pred = s_pred; a.v_pred = v_pred;
-        a.status = status; a.iters = h->d_iters;
-        HIPCHK(eepacc::launch_fbs_step(a, h->cfg.N, (hipStream_t)stream));
-        h->fb_k_done += 1; h->last_B = B; h->fb_by_step = true;
-        return EEPACC_OK;
-    }
+    if (h->fbs)
+        return fbs_step_launch(h, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, out, s_pred, v_pred, status, stream, nullptr);
     int rc = fb_prepare(h, B);
     if (rc != EEPACC_OK) return rc;
     h->fb_by_step = true;              // after fb_prepare: its first (re)allocation clears the flag
@@ -1087,18 +1099,20 @@ extern "C" int eepacc_fb_step(eepacc_handle* h, int B, const double* s, const do
 extern "C" int eepacc_fb_qp_size(const eepacc_handle* h, int* nV, int* nC) { return qp_size_impl(kQpFB, h, nV, nC); }
 extern "C" int eepacc_fb_qp_rows(const eepacc_handle* h, int32_t* stage, int32_t* type) { return qp_rows_impl(kQpFB, h, stage, type); }
 
-extern "C" int eepacc_fb_build_qp(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
-                                  const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
-                                  const double* A22, const double* D2, double* H, double* g, double* A, double* lba,
-                                  double* uba, double* A22_used, double* D2_used, void* stream) {
+// eepacc_fb_build_qp (sup == NULL) and eepacc_fb_build_qp_est: the same checks, carried state and launch arguments
+static int fb_build_impl(const std::string& who, eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
+                         const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                         const double* A22, const double* D2, double* H, double* g, double* A, double* lba,
+                         double* uba, double* A22_used, double* D2_used, void* stream, const eepacc::AbSupplied* sup) {
     bool launch;
-    if (const int rc = build_args_check(kQpFB, h, B, {s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, H, g, A, lba, uba}, &launch)) return rc;
+    if (const int rc = build_args_check(kQpFB, h, B, {s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, H, g, A, lba, uba}, &launch, who.c_str())) return rc;
     if (!launch) return EEPACC_OK;
+    if (sup) { if (const int rc = est_pair(who, sup->s_est, sup->v_est)) return rc; }
     if (!A22 != !D2)
-        return fail(EEPACC_EINVAL, std::string("eepacc_fb_build_qp: ") + (A22 ? "D2" : "A22") + " is NULL while " + (A22 ? "A22" : "D2") + " is given; pass both or neither");
+        return fail(EEPACC_EINVAL, who + ": " + (A22 ? "D2" : "A22") + " is NULL while " + (A22 ? "A22" : "D2") + " is given; pass both or neither");
     const DevCfg& C = h->cfg;
     if (A22 && !C.FBuseTaylor)
-        return fail(EEPACC_EINVAL, "eepacc_fb_build_qp: A22 and D2 are given, but with FBuseTaylor = 0 no model is carried (A22 = 1, D2 from the step's estimate); pass NULL");
+        return fail(EEPACC_EINVAL, who + ": A22 and D2 are given, but with FBuseTaylor = 0 no model is carried (A22 = 1, D2 from the step's estimate); pass NULL");
     const int N = C.N;
     eepacc::fb_qp_args a;
     a.cfg = h->d_cfg; a.B = B; a.nC = eepacc::fb_qp_num_rows(C);
@@ -1113,7 +1127,7 @@ extern "C" int eepacc_fb_build_qp(eepacc_handle* h, int B, const double* s, cons
     // The stride of the dense path's arrays is the B of the FBMPC steps that wrote them (fb.steps_B <= fb.B, what they are
     // allocated for); h->last_B will not do, since the ABMPC entry points write it too.
     if (!h->fbs && (carried_model || carried_pred) && (B != h->fb.steps_B || B > h->fb.B))
-        return fail(EEPACC_EINVAL, "eepacc_fb_build_qp: B = " + std::to_string(B) + " differs from the B = " + std::to_string(h->fb.steps_B) +
+        return fail(EEPACC_EINVAL, who + ": B = " + std::to_string(B) + " differs from the B = " + std::to_string(h->fb.steps_B) +
                                    " of the FBMPC steps whose carried state this handle holds");
     const size_t ks = eepacc::kFbsStateDoubles, lB = (size_t)h->fb.steps_B;
     if (A22) {
@@ -1133,24 +1147,71 @@ extern "C" int eepacc_fb_build_qp(eepacc_handle* h, int B, const double* s, cons
         a.sp = eepacc::FbCarried{h->fb.sp, lB, 1}; a.vp = eepacc::FbCarried{h->fb.vp, lB, 1};
     }
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(eepacc::launch_fb_qp(a, N, (hipStream_t)stream));
+    if (sup) HIPCHK(eepacc::launch_fb_qp_est(a, N, (hipStream_t)stream, sup->s_est, sup->v_est, sup->s_tv_est));
+    else HIPCHK(eepacc::launch_fb_qp(a, N, (hipStream_t)stream));
     return EEPACC_OK;
 }
 
-extern "C" int eepacc_run_fbmpc(eepacc_handle* h, int B, int n_steps, const double* s0, const double* v0,
-                                const double* a_minus1, const double* s_tv, const double* v_tv,
-                                double* traj, int32_t* status, void* stream) {
-    if (const int rc = not_classes(h, "eepacc_run_fbmpc")) return rc;      // (any class handle, a target-vehicle one included: not supported)
-    if (const int rc = not_tv(h, "eepacc_run_fbmpc")) return rc;
-    if (B < 0 || B > h->max_batch || n_steps < 0) return fail(EEPACC_EINVAL, "eepacc_run_fbmpc: bad B / n_steps");
-    if (B == 0 || n_steps == 0) return EEPACC_OK;
+extern "C" int eepacc_fb_build_qp(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
+                                  const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                                  const double* A22, const double* D2, double* H, double* g, double* A, double* lba,
+                                  double* uba, double* A22_used, double* D2_used, void* stream) {
+    return fb_build_impl("eepacc_fb_build_qp", h, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, A22, D2, H, g, A, lba, uba, A22_used, D2_used,
+                         stream, nullptr);
+}
+
+// ---- FBMPC with horizon guesses from the caller: eepacc_fb_step_est, eepacc_fb_build_qp_est, eepacc_run_fbmpc_preview.  The
+// refusals of a handle are eepacc::fb_est_refusal (eepacc_cfg.cpp); the step and the preview loop run the kernels of
+// eepacc_fbs_est.hip on the state of eepacc_fb_step / eepacc_run_fbmpc.
+static int fb_est_handle(const eepacc_handle* h, const std::string& who, bool needs_structured) {
+    if (!h) return fail(EEPACC_EINVAL, who + ": NULL handle");
+    return eepacc::fb_est_refusal(who, h->n_classes, h->cfg, h->fbs, needs_structured);
+}
+
+extern "C" int eepacc_fb_step_est(eepacc_handle* h, int B, const double* s, const double* v, const double* v_prev,
+                                  const double* a_prev, const double* Fm_prev, const double* Fb_prev, const double* t0,
+                                  const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                                  const double* s_est, const double* v_est, const double* s_tv_est,
+                                  double* out, double* s_pred, double* v_pred, int32_t* status, void* stream) {
+    (void)v_prev; (void)Fm_prev; (void)Fb_prev;   // accepted and unused, as in eepacc_fb_step
+    const std::string who = "eepacc_fb_step_est";
+    if (const int rc = fb_est_handle(h, who, true)) return rc;
+    if (B < 0 || B > h->max_batch)
+        return fail(EEPACC_EINVAL, who + ": B = " + std::to_string(B) + " is outside [0, max_batch = " + std::to_string(h->max_batch) + "]");
+    if (B == 0) return EEPACC_OK;
+    const struct { const void* p; const char* name; } bufs[] = {{s, "s"}, {v, "v"}, {a_prev, "a_prev"}, {t0, "t0"}, {s_tv, "s_tv"},
+        {v_tv, "v_tv"}, {a_tv_prev, "a_tv_prev"}, {out, "out"}, {status, "status"}};
+    for (const auto& bf : bufs)
+        if (!bf.p) return fail(EEPACC_EINVAL, who + ": " + bf.name + " is NULL");
+    if (const int rc = est_pair(who, s_est, v_est)) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    const eepacc::AbSupplied sup{s_est, v_est, s_tv_est};
+    return fbs_step_launch(h, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, out, s_pred, v_pred, status, stream, &sup);
+}
+
+extern "C" int eepacc_fb_build_qp_est(eepacc_handle* h, int B, const double* s, const double* v, const double* a_prev,
+                                      const double* t0, const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                                      const double* s_est, const double* v_est, const double* s_tv_est,
+                                      const double* A22, const double* D2, double* H, double* g, double* A, double* lba,
+                                      double* uba, double* A22_used, double* D2_used, void* stream) {
+    const std::string who = "eepacc_fb_build_qp_est";
+    if (const int rc = fb_est_handle(h, who, false)) return rc;
+    const eepacc::AbSupplied sup{s_est, v_est, s_tv_est};
+    return fb_build_impl(who, h, B, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, A22, D2, H, g, A, lba, uba, A22_used, D2_used, stream, &sup);
+}
+
+// The launch of eepacc_run_fbmpc (pv == NULL) and of eepacc_run_fbmpc_preview after their own checks of the handle and of B,
+// n_steps: buffers, the resume rules and, on a structured handle, the closed-loop kernel
+static int fb_run_impl(const std::string& who, eepacc_handle* h, int B, int n_steps, const double* s0, const double* v0,
+                       const double* a_minus1, const double* s_tv, const double* v_tv,
+                       double* traj, int32_t* status, void* stream, const eepacc::AbPreview* pv) {
     if (!s0 || !v0 || !a_minus1 || !s_tv || !v_tv || !traj || !status)
-        return fail(EEPACC_EINVAL, "eepacc_run_fbmpc: NULL buffer");
+        return fail(EEPACC_EINVAL, who + ": NULL buffer");
     HIPCHK(hipSetDevice(h->device));
     if (h->fb_k_done > 0 && B != h->last_B)
-        return fail(EEPACC_EINVAL, "eepacc_run_fbmpc: B changed while resuming; call eepacc_reset first");
+        return fail(EEPACC_EINVAL, who + ": B changed while resuming; call eepacc_reset first");
     if (h->fb_k_done > 0 && h->fb_by_step)
-        return fail(EEPACC_EINVAL, "eepacc_run_fbmpc after eepacc_fb_step: the per-step operator keeps no closed-loop state to resume from; call eepacc_reset first");
+        return fail(EEPACC_EINVAL, who + " after eepacc_fb_step: the per-step operator keeps no closed-loop state to resume from; call eepacc_reset first");
     if (h->fbs) {
         // work-unit length: 16 MPC steps, shorter for short launches so that every resident wave still gets several units
         int chunk_steps = eepacc::pick_chunk_steps(n_steps, B, eepacc::fbs_run_chunking_waves(h->cfg.N, h->num_cus));
@@ -1162,7 +1223,8 @@ extern "C" int eepacc_run_fbmpc(eepacc_handle* h, int B, int n_steps, const doub
         a.chunk_steps = chunk_steps;
         a.cold = 0;
         if (const char* ev = getenv("EEPACC_DEBUG_FBS_COLD")) a.cold = atoi(ev) != 0;
-        HIPCHK(eepacc::launch_fbs_run(a, h->cfg.N, h->num_cus, (hipStream_t)stream));
+        if (pv) HIPCHK(eepacc::launch_fbs_run_preview(a, h->cfg.N, h->num_cus, (hipStream_t)stream, pv->idx, pv->frac, pv->n_lead));
+        else HIPCHK(eepacc::launch_fbs_run(a, h->cfg.N, h->num_cus, (hipStream_t)stream));
         h->fb_k_done += n_steps; h->last_B = B;
         return EEPACC_OK;
     }
@@ -1175,6 +1237,31 @@ extern "C" int eepacc_run_fbmpc(eepacc_handle* h, int B, int n_steps, const doub
         if (rc != EEPACC_OK) return rc;
     }
     return EEPACC_OK;
+}
+
+extern "C" int eepacc_run_fbmpc(eepacc_handle* h, int B, int n_steps, const double* s0, const double* v0,
+                                const double* a_minus1, const double* s_tv, const double* v_tv,
+                                double* traj, int32_t* status, void* stream) {
+    if (const int rc = not_classes(h, "eepacc_run_fbmpc")) return rc;      // (any class handle, a target-vehicle one included: not supported)
+    if (const int rc = not_tv(h, "eepacc_run_fbmpc")) return rc;
+    if (B < 0 || B > h->max_batch || n_steps < 0) return fail(EEPACC_EINVAL, "eepacc_run_fbmpc: bad B / n_steps");
+    if (B == 0 || n_steps == 0) return EEPACC_OK;
+    return fb_run_impl("eepacc_run_fbmpc", h, B, n_steps, s0, v0, a_minus1, s_tv, v_tv, traj, status, stream, nullptr);
+}
+
+extern "C" int eepacc_run_fbmpc_preview(eepacc_handle* h, int B, int n_steps, int n_lead, const double* s0, const double* v0,
+                                        const double* a_minus1, const double* s_tv, const double* v_tv, double* traj,
+                                        int32_t* status, void* stream) {
+    const std::string who = "eepacc_run_fbmpc_preview";
+    if (const int rc = fb_est_handle(h, who, true)) return rc;
+    if (B < 0 || B > h->max_batch || n_steps < 0)
+        return fail(EEPACC_EINVAL, who + ": B = " + std::to_string(B) + " must be in [0, max_batch = " + std::to_string(h->max_batch) + "] and n_steps = " + std::to_string(n_steps) + " not negative");
+    if (n_lead < n_steps)
+        return fail(EEPACC_EINVAL, who + ": n_lead = " + std::to_string(n_lead) + " is below n_steps = " + std::to_string(n_steps) + "; the lead traces hold at least the rows of the launch's steps");
+    if (B == 0 || n_steps == 0) return EEPACC_OK;
+    if (const int rc = preview_tables_ready(h)) return rc;
+    const eepacc::AbPreview pv{h->d_pv_idx, h->d_pv_frac, n_lead};
+    return fb_run_impl(who, h, B, n_steps, s0, v0, a_minus1, s_tv, v_tv, traj, status, stream, &pv);
 }
 
 // Host-pointer wrappers (what the MEX gateways mex/RunOpt_*MPC.c call): copy in, reset, run, wait, copy out.  The device

@@ -218,6 +218,22 @@ void preview_tables(const double* Tvec, int N, int32_t* idx, double* frac) {
     }
 }
 
+// eepacc_fb_step_est, eepacc_fb_build_qp_est, eepacc_run_fbmpc_preview: what they refuse of a handle (header: EEPACC_ENOTSUP).
+int fb_est_refusal(const std::string& who, int n_classes, const DevCfg& C, bool structured, bool needs_structured) {
+    if (n_classes)
+        return set_error(EEPACC_ENOTSUP, who + ": a handle of eepacc_create_classes / eepacc_create_classes_bl has no FBMPC variant, with or without supplied horizon guesses");
+    if (C.bl_mode != 0)
+        return set_error(EEPACC_ENOTSUP, who + ": the handle was created with bl_mode = " + std::to_string(C.bl_mode) +
+                                         "; supplied horizon guesses for FBMPC are built for a handle with bl_mode = 0 (the baseline controller has eepacc_bl_step_est, eepacc_bl_build_qp_est and eepacc_run_blmpc_preview)");
+    if (!needs_structured || structured) return EEPACC_OK;
+    std::string cause = "EEPACC_FB_DENSE=1 was set when the handle was created, or its horizon does not fit the structured kernels";
+    for (int k = 0; k < C.N; ++k)
+        if (C.mb_mask[k]) { cause = "Mb[" + std::to_string(k) + "] != 0 (blocked moves)"; break; }
+    if (!C.mb_any && C.b_quadr[3] != 0.0) cause = "b_quadr(4) != 0 (the Fm^2 term of the power fit)";
+    return set_error(EEPACC_ENOTSUP, who + ": the FBMPC steps of this handle go through the dense path: " + cause +
+                                     "; supplied horizon guesses are built for the structured kernels only.  eepacc_fb_build_qp_est still builds the problem of such a handle");
+}
+
 // What eepacc_kpis reads of a class (validated by build_cfg before): the power fit and driveline of the energy, the fuel
 // map and coast-down terms of ABO/Custom_plots.m:73-107 and the speed-limit table of ABO/Main.m:133.
 KpiCfg build_kpi_cfg(const eepacc_settings* S, const eepacc_vehicle* V) {

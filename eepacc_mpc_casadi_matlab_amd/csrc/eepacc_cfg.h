@@ -29,6 +29,11 @@ int build_cfg(const eepacc_settings* S, const eepacc_vehicle* V, DevCfg& C, std:
 // step reads the lead trace idx[k] + frac[k] rows after the step's own, frac in [0, 1) and 0 where the stage falls on a sample.
 void preview_tables(const double* Tvec, int N, int32_t* idx, double* frac);
 
+// Whether a handle serves the FBMPC entries with supplied horizon guesses (who: the entry's name).  n_classes, C: the handle's;
+// structured: its FBMPC steps run through the structured kernels; needs_structured: the entry is the step or the preview loop
+// (the builder serves dense-path handles too).  EEPACC_OK, or EEPACC_ENOTSUP with the cause through set_error.
+int fb_est_refusal(const std::string& who, int n_classes, const DevCfg& C, bool structured, bool needs_structured);
+
 // Of settings that build_cfg has accepted.
 KpiCfg build_kpi_cfg(const eepacc_settings* S, const eepacc_vehicle* V);
 FollowCfg build_follow_cfg(const eepacc_settings* S, const eepacc_vehicle* V);

@@ -31,6 +31,10 @@ struct fb_qp_args {
 
 // B workgroups of 256 threads; every entry of the outputs is written.  Nothing else is.
 hipError_t launch_fb_qp(const fb_qp_args& a, int N, hipStream_t stream);
+// The same on the caller's horizon guesses (eepacc_fb_qp_est.hip): device arrays [N+1][B], s_est and v_est both or neither,
+// a null array keeps the estimator's guess.  All three null: the arrays of launch_fb_qp.
+hipError_t launch_fb_qp_est(const fb_qp_args& a, int N, hipStream_t stream, const double* s_est, const double* v_est,
+                            const double* s_tv_est);
 size_t fb_qp_smem_bytes(int N, int nC);     // static + dynamic LDS of a workgroup
 
 }  // namespace eepacc

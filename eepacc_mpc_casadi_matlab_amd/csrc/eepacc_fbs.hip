@@ -24,6 +24,12 @@
 //
 // The tables of the active-set method (the inverse He of the effective Hessian, the inverse Schur block P of the working
 // set) are maintained by eepacc_schur.h, shared with the ABMPC kernels.
+//
+// Two translation units instantiate their kernels from the templates below: this one (k_fbs_step, k_fbs_run with an empty
+// argument pack: the estimators' horizon guesses; the host-side launchers at the end) and eepacc_fbs_est.hip, which includes this
+// file with EEPACC_FBS_KERNELS_ONLY defined and instantiates the same two templates with further arguments (the guesses of the
+// caller: eepacc_fb_step_est, eepacc_run_fbmpc_preview).  Two units so that the kernels of the first
+// keep their code (profiles/fb_est_codegen.txt).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -1033,6 +1039,41 @@ __device__ __forceinline__ SolveStats solve_qp(Lane& L, const RC& c, FMem<MMAX, 
 
 struct StepIn { double s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, v_prev; int k_step, have_vprev; };
 
+// Horizon guesses of the caller for this lane's stage (eepacc_fbs_est.hip): ego = s_est and v_est are given, lead = s_tv_est is
+struct EstIn { bool ego, lead; double s_est, v_est, stv_est; };
+
+// What this lane's stage gets of the three supplied arrays ([N_hor+1][B], the layout of s_pred: one load per array, coalesced
+// over the instances of a block).  Row N_hor of s_tv_est is not read: the terminal rows use stage N - 1 (CreateQP_FB.m:478-489).
+__device__ __forceinline__ EstIn est_supplied(int lane, int N, int B, int b, const double* __restrict__ s_est,
+                                              const double* __restrict__ v_est, const double* __restrict__ s_tv_est) {
+    EstIn e{s_est != nullptr, s_tv_est != nullptr, 0.0, 0.0, 0.0};
+    const size_t ke = lane <= N ? lane : N, kl = lane < N ? lane : N - 1;
+    if (e.ego) { e.s_est = s_est[ke * B + b]; e.v_est = v_est[ke * B + b]; }
+    if (e.lead) e.stv_est = s_tv_est[kl * B + b];
+    return e;
+}
+// The lead's guess of the step at row kk of the launch's traces [n_lead][B], read from the traces themselves
+// (eepacc_run_fbmpc_preview).  The rule is that of the ABMPC preview kernels (est_preview of eepacc_ab_impl.inc, specification:
+// scenarios.lead_preview) on the same tables of the handle (eepacc::preview_tables): stage k looks tau_k ahead, at row
+// kk + idx[k] + frac[k]; the sample itself where frac is 0, else the two neighbours interpolated, and past the last row that
+// row carried on at its speed.  Products and sums are rounded one by one, as the specification's are; +inf stays +inf.
+__device__ __forceinline__ EstIn est_preview(const DevCfg& C, int lane, int B, int b, int kk, const double* __restrict__ s_tv,
+                                             const double* __restrict__ v_tv, const int32_t* __restrict__ idx,
+                                             const double* __restrict__ frac, int n_lead) {
+    EstIn e{false, true, 0.0, 0.0, 0.0};
+    const int k = lane < C.N ? lane : C.N - 1, last = n_lead - 1;
+    const int i = kk + idx[k];
+    const double f = frac[k];
+    if (i < last || (i == last && f == 0.0)) {
+        const double a = s_tv[(size_t)i * B + b];
+        e.stv_est = f == 0.0 ? a : __dadd_rn(__dmul_rn(1.0 - f, a), __dmul_rn(f, s_tv[(size_t)(i + 1) * B + b]));
+    } else {
+        const double dt = __dsub_rn(C.tau[k], __dmul_rn((double)(last - kk), C.Tvec[0]));
+        e.stv_est = __dadd_rn(s_tv[(size_t)last * B + b], __dmul_rn(v_tv[(size_t)last * B + b], dt));
+    }
+    return e;
+}
+
 // LDS layout of a block: per wave [FMem][He NS x NS]; the step's base inverse (needed again only by a cold restart)
 // is kept in a per-wave global scratch
 __host__ __device__ inline size_t wave_bytes(size_t wm, int ns) {
@@ -1041,10 +1082,13 @@ __host__ __device__ inline size_t wave_bytes(size_t wm, int ns) {
 
 // One FBMPC step of the wave's instance (ABO/RunOpt_FBMPC.m:204-320).  A22, D2: this lane's carried state-space
 // entries (the A(k)/D(k) index quirk :247-259 freezes stage k at MPC step k); code: warm working set.
-template <int MMAX, int NS>
+// est: nothing (the estimators' guesses) or one EstIn (the caller's guesses of this lane's stage stand where they are given).
+template <int MMAX, int NS, class... Est>
 __device__ __forceinline__ void fb_step(const DevCfg& C, FMem<MMAX, NS>& M, double* Hs, double* Hb, const StepIn& in,
                                         double& A22, double& D2, unsigned long long& code, StepOut& so,
-                                        double& s_pred, double& v_pred, double ps_prev, double pv_prev) {
+                                        double& s_pred, double& v_pred, double ps_prev, double pv_prev, Est... est) {
+    static_assert(sizeof...(Est) <= 1, "at most one EstIn");
+    constexpr bool kEst = sizeof...(Est) == 1;
     Lane L;
     L.lane = lane_id(); L.N = C.N;
     const int lane = L.lane, N = C.N;
@@ -1061,7 +1105,17 @@ __device__ __forceinline__ void fb_step(const DevCfg& C, FMem<MMAX, NS>& M, doub
     c.c5 = C.fb_w[0] * Kr * C.b_quadr[4]; c.c2 = C.fb_w[0] * C.b_quadr[1];
     // estimators (A2)
     double s_est, v_est, stv_est, vtv_est;
-    if (C.paramEstSetting == 2) {
+    // CreateQP_FB takes s_est, v_est and s_tv_est as inputs: a side that the caller supplied is taken as given (wave-uniform
+    // choice), the other one is estimated as ever
+    bool ego_given = false, lead_given = false;
+    if constexpr (kEst) {
+        const EstIn e[] = {est...};
+        ego_given = e[0].ego; lead_given = e[0].lead;
+        s_est = e[0].s_est; v_est = e[0].v_est; stv_est = e[0].stv_est;
+    }
+    if (ego_given) {
+        // (s_est, v_est: the caller's, row 0 included)
+    } else if (C.paramEstSetting == 2) {
         // EstimateVehicleTrajectory.m:81-88: [x_curr; prev(3:end); prev(end) + Ts v_prev(end)]; ps_prev/pv_prev hold
         // the previous prediction of stage lane+1 (stage N for the last two lanes)
         s_est = lane == 0 ? in.s : (lane < N ? ps_prev : ps_prev + C.Tvec[N - 1] * pv_prev);
@@ -1069,7 +1123,7 @@ __device__ __forceinline__ void fb_step(const DevCfg& C, FMem<MMAX, NS>& M, doub
     } else {
         estimate_traj(C, C.paramEstSetting, C.tConstACC_ego, in.s, in.v, in.a_prev, lane, s_est, v_est);
     }
-    estimate_traj(C, C.TVestSetting, C.tConstACC_tar, in.s_tv, in.v_tv, in.a_tv_prev, lane, stv_est, vtv_est);
+    if (!lead_given) estimate_traj(C, C.TVestSetting, C.tConstACC_tar, in.s_tv, in.v_tv, in.a_tv_prev, lane, stv_est, vtv_est);
     const double dist_hor = bcast(s_est, N) - in.s;                           // :208
     const double stv_Nm1 = bcast(stv_est, N - 1);
     double v_lim, v_curv, v_stop, v_TL, a_min, a_max, j_min, j_max;
@@ -1233,6 +1287,11 @@ __device__ __forceinline__ void fb_step(const DevCfg& C, FMem<MMAX, NS>& M, doub
                 exists = true;
                 if (t == F_SHI && !(C.s_goal < 1e300)) exists = false;
             } else exists = (lane == N) && (t == F_SAFE1 || t == F_SAFE2);
+            // A supplied lead guess may say "no lead" (+inf) at a stage where the carried working set, made on another guess,
+            // holds a headway row.  Such a row does not exist: its code is dropped below, so that no pivot or penalised xi_h
+            // is defined by an infinite right-hand side.  (On the estimators' guesses a lead is absent at every stage or at
+            // none, and an infinite row is never violated, so it never enters a working set: DESIGN.md section 3.5e.)
+            if constexpr (kEst) { if (lead_given && (t == F_SAFE1 || t == F_SAFE2 || t == F_HWP) && !(b[t] < kInf)) exists = false; }
             if (exists && lane == 0 && row_ga(t, c) == 0.0 && row_aw(t, c) == 0.0) {
                 // stage-0 rows on (s_0, v_0) only are constants: fold into slack bounds
                 exists = false;
@@ -1368,10 +1427,10 @@ __device__ __forceinline__ double* st_D2(double* s) { return s + 128; }
 __device__ __forceinline__ double* st_sp(double* s) { return s + 192; }
 __device__ __forceinline__ double* st_vp(double* s) { return s + 256; }
 
-// B2: one step for B instances
-template <int MMAX, int NS, int WPB>
+// B2: one step for B instances.  extra: nothing, or the three supplied arrays s_est, v_est, s_tv_est (eepacc_fbs_est.hip)
+template <int MMAX, int NS, int WPB, class... Extra>
 __global__ void __launch_bounds__(64 * WPB)
-k_fbs_step(fbs_step_args a) {
+k_fbs_step(fbs_step_args a, Extra... extra) {
     extern __shared__ __align__(16) unsigned char smem[];
     const DevCfg& C = *a.cfg;
     rc_table_init<MMAX>();
@@ -1389,6 +1448,9 @@ k_fbs_step(fbs_step_args a) {
     const double ps = st_sp(stt)[idx], pv = st_vp(stt)[idx];
     StepOut so;
     double sp, vp;
+    if constexpr (sizeof...(Extra) != 0)
+        fb_step<MMAX, NS>(C, M, Hs, Hb, in, A22, D2, code, so, sp, vp, ps, pv, est_supplied(lane, N, a.B, b, extra...));
+    else
     fb_step<MMAX, NS>(C, M, Hs, Hb, in, A22, D2, code, so, sp, vp, ps, pv);
     st_A22(stt)[lane] = A22; st_D2(stt)[lane] = D2;
     if (lane <= N) { st_sp(stt)[lane] = sp; st_vp(stt)[lane] = vp; }
@@ -1399,10 +1461,12 @@ k_fbs_step(fbs_step_args a) {
     if (lane == 0) { a.status[b] = so.status; if (a.iters) a.iters[b] = so.iters; }
 }
 
-// B1: closed loop over n_steps for B instances (ABO/RunOpt_FBMPC.m:161-331) in work units (run_units, eepacc_units.h)
-template <int MMAX, int NS, int WPB>
+// B1: closed loop over n_steps for B instances (ABO/RunOpt_FBMPC.m:161-331) in work units (run_units, eepacc_units.h).
+// extra: nothing, or the preview tables idx, frac and n_lead (eepacc_fbs_est.hip): the lead's guess of every step is read from
+// the launch's lead traces, a.s_tv / a.v_tv [n_lead][B]
+template <int MMAX, int NS, int WPB, class... Extra>
 __global__ void __launch_bounds__(64 * WPB, ((NS <= 32 && WPB <= 2) ? 2 : 1))
-k_fbs_run(fbs_run_args a) {
+k_fbs_run(fbs_run_args a, Extra... extra) {
     extern __shared__ __align__(16) unsigned char smem[];
     const DevCfg& C = *a.cfg;
     rc_table_init<MMAX>();
@@ -1434,6 +1498,10 @@ k_fbs_run(fbs_run_args a) {
             measure(C, Ts, in.k_step, kk, B, b, a.s0, a.v0, a.a_m1, a.s_tv, a.v_tv, cs, in);
             StepOut so;
             double sp, vp;
+            if constexpr (sizeof...(Extra) != 0)
+                fb_step<MMAX, NS>(C, M, Hs, Hb, in, A22, D2, code, so, sp, vp, ps, pv,
+                                  est_preview(C, lane, B, b, kk, a.s_tv, a.v_tv, extra...));
+            else
             fb_step<MMAX, NS>(C, M, Hs, Hb, in, A22, D2, code, so, sp, vp, ps, pv);
             if (C.paramEstSetting == 2) {
                 ps = __shfl(sp, idx, 64); pv = __shfl(vp, idx, 64);
@@ -1453,6 +1521,10 @@ k_fbs_run(fbs_run_args a) {
 }
 
 }  // namespace fbs
+}  // namespace eepacc
+
+#ifndef EEPACC_FBS_KERNELS_ONLY
+namespace eepacc {
 
 #ifdef EEPACC_FBS_TIMING
 extern "C" int eepacc_debug_fbs_prof(unsigned long long* out, int reset) {
@@ -1464,10 +1536,7 @@ extern "C" int eepacc_debug_fbs_prof(unsigned long long* out, int reset) {
 #endif
 
 // ----------------------------------------------------------------------------------------------
-// host-side launchers used by eepacc_capi.cpp
-constexpr int kFMMaxSmall = 32, kFNSSmall = 32, kFWpbSmall = 7;     // N <= 32: 21.7 KB of LDS per wave, one block of 7 waves per CU
-                                                                    // (working-set rows are independent in the N-dimensional u-space: m <= N)
-constexpr int kFMMaxLarge = 66, kFNSLarge = 64, kFWpbLarge = 1;     // N <= 63
+// host-side launchers used by eepacc_capi.cpp (size classes and LDS budget: eepacc_fbs.h)
 
 // settings the structured solver represents; everything else goes through the dense path (eepacc_fb.hip)
 bool fbs_supported(const DevCfg& C) {
@@ -1484,11 +1553,8 @@ size_t fbs_smem_bytes(int N) {
                           : fbs::wave_bytes(sizeof(fbs::FMem<kFMMaxLarge, kFNSLarge>), kFNSLarge) * kFWpbLarge;
 }
 
-// dynamic LDS a block may ask for: 160 KB per CU minus the kernels' static index table (one ushort per packed entry of P)
-constexpr size_t kFbsLdsBudget = 160 * 1024 - 4608;
-
 // blocks of a chip-filling closed-loop launch
-static int fbs_run_max_grid(int N, int num_cus) {
+int fbs_run_max_grid(int N, int num_cus) {
     const int per_cu = (int)(kFbsLdsBudget / fbs_smem_bytes(N));
     return num_cus * (per_cu < 1 ? 1 : per_cu);
 }
@@ -1511,7 +1577,7 @@ hipError_t fbs_set_max_smem() {
         hipError_t e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFbsLdsBudget);
         if (e != hipSuccess) return e;
     }
-    return hipSuccess;
+    return fbs_est_set_max_smem();      // the four kernels of eepacc_fbs_est.hip: a handle may launch either set
 }
 
 hipError_t launch_fbs_step(const fbs_step_args& a, int N, hipStream_t stream) {
@@ -1541,3 +1607,4 @@ hipError_t launch_fbs_run(fbs_run_args a, int N, int num_cus, hipStream_t stream
 }
 
 }  // namespace eepacc
+#endif  // EEPACC_FBS_KERNELS_ONLY

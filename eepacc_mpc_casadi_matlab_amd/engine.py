@@ -13,7 +13,7 @@ from typing import Any, Dict, NamedTuple, Optional
 
 import numpy as np
 
-from ._abi import (SettingsHolder, SettingsPOD, Vehicle, make_vehicle, pack_classes, OUT, OUT_N, OUT_FIELDS, KPI_N, FKPI_N, FKPI_WEIGHTS, RKPI_N, RLIM_N, ROUTE_KPIS_ARGTYPES, AB_BUILD_ARGTYPES, AB_EST_ARGTYPES, BL_EST_ARGTYPES, CLASSES_EST_ARGTYPES, CLASSES_BUILD_ARGTYPES,
+from ._abi import (SettingsHolder, SettingsPOD, Vehicle, make_vehicle, pack_classes, OUT, OUT_N, OUT_FIELDS, KPI_N, FKPI_N, FKPI_WEIGHTS, RKPI_N, RLIM_N, ROUTE_KPIS_ARGTYPES, AB_BUILD_ARGTYPES, AB_EST_ARGTYPES, BL_EST_ARGTYPES, FB_EST_ARGTYPES, CLASSES_EST_ARGTYPES, CLASSES_BUILD_ARGTYPES,
                    FB_BUILD_ARGTYPES, BL_BUILD_ARGTYPES,
                    c_double_p, as_dptr, as_iptr)
 
@@ -75,7 +75,7 @@ def load_library() -> C.CDLL:
     lib.eepacc_qp_solve_batched_dual.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [dp] * 8 + [dp, dp] + [dp] * 3 + [dp] * 5 + [vp]
     lib.eepacc_qp_kkt_solve_batched.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int] + [dp] * 2 + [dp] * 2 + [dp] * 3 + [dp] * 3 + [dp, vp]
     for name, argtypes in (list(AB_BUILD_ARGTYPES.items()) + list(FB_BUILD_ARGTYPES.items()) + list(BL_BUILD_ARGTYPES.items())
-                           + list(AB_EST_ARGTYPES.items()) + list(BL_EST_ARGTYPES.items()) + list(CLASSES_EST_ARGTYPES.items()) + list(CLASSES_BUILD_ARGTYPES.items())):
+                           + list(AB_EST_ARGTYPES.items()) + list(BL_EST_ARGTYPES.items()) + list(FB_EST_ARGTYPES.items()) + list(CLASSES_EST_ARGTYPES.items()) + list(CLASSES_BUILD_ARGTYPES.items())):
         getattr(lib, name).argtypes = argtypes
     lib.eepacc_synchronize.argtypes = [vp, vp]
     lib.eepacc_build_flags.restype = C.c_char_p
@@ -93,6 +93,7 @@ ABI_SYMBOLS = ["eepacc_last_error", "eepacc_version", "eepacc_sizeof_settings", 
                "eepacc_ab_qp_size", "eepacc_ab_qp_rows", "eepacc_ab_build_qp",
                "eepacc_ab_step_est", "eepacc_ab_build_qp_est", "eepacc_run_abmpc_preview",
                "eepacc_fb_qp_size", "eepacc_fb_qp_rows", "eepacc_fb_build_qp",
+               "eepacc_fb_step_est", "eepacc_fb_build_qp_est", "eepacc_run_fbmpc_preview",
                "eepacc_bl_qp_size", "eepacc_bl_qp_rows", "eepacc_bl_build_qp",
                "eepacc_bl_step_est", "eepacc_bl_build_qp_est", "eepacc_run_blmpc_preview",
                "eepacc_classes_step_est", "eepacc_run_classes_preview",
@@ -537,6 +538,42 @@ class Engine:
                                            _ptr(used[0]), _ptr(used[1]), self._stream()))
         return FbQpModel(*qp, used[0], used[1]) if want_model else FbQp(*qp)
 
+    # FBMPC with the horizon guesses supplied (structured kernels), and the closed loop with the lead's guess read from its trace
+    def fb_step_est(self, s, v, v_prev, a_prev, Fm_prev, Fb_prev, t0, s_tv, v_tv, a_tv_prev, s_est=None, v_est=None,
+                    s_tv_est=None, want_pred: bool = True):
+        """eepacc_fb_step_est: fb_step with the horizon guesses supplied, the contract of CreateQP_FB(..., s_est, v_est,
+        s_tv_est, ...).  s_est, v_est (together or both None) and s_tv_est are [N+1, B], the layout of the predictions
+        fb_step returns; None keeps the engine's estimator for that side.  The model entry of the step is made of the
+        supplied v_est[N-1].  Reads and writes the engine state fb_step does; results as fb_step."""
+        self._est_check(s, s_est, v_est, s_tv_est)
+        B = int(self.torch.as_tensor(s).numel())
+        est = self._est(B, s_est, v_est, s_tv_est)
+        fn = lambda h, B_, *rest: self.lib.eepacc_fb_step_est(h, B_, *rest[:10], *[_ptr(x) for x in est], *rest[10:])
+        return self._step(fn, (s, v, v_prev, a_prev, Fm_prev, Fb_prev, t0, s_tv, v_tv, a_tv_prev), want_pred)
+
+    def fb_build_qp_est(self, s, v, a_prev, t0, s_tv, v_tv, a_tv_prev, s_est=None, v_est=None, s_tv_est=None, A22=None, D2=None,
+                        want_model: bool = False):
+        """eepacc_fb_build_qp_est: the condensed QP of the step fb_step_est solves, CreateQP_FB on the supplied guesses and,
+        with A22 = D2 = None, the model whose entry of this step is made of the supplied v_est[N-1].  Everything else as
+        fb_build_qp (dense-path engines included); fb_qp_size and fb_qp_rows describe the result."""
+        self._est_check(s, s_est, v_est, s_tv_est)
+        t = self.torch
+        B = int(t.as_tensor(s).numel())
+        ins = [self._d(x, B) for x in (s, v, a_prev, t0, s_tv, v_tv, a_tv_prev)]
+        est = self._est(B, s_est, v_est, s_tv_est)
+        model = [None if x is None else self._d(x, self.N * B) for x in (A22, D2)]
+        ptrs, qp = self._qp_outputs(B, *self.fb_qp_size())
+        used = [t.empty((self.N, B), dtype=t.float64, device=self.device) if want_model else None for _ in range(2)]
+        _check(self.lib.eepacc_fb_build_qp_est(self.h, B, *[x.data_ptr() for x in ins], *[_ptr(x) for x in est], _ptr(model[0]),
+                                               _ptr(model[1]), *ptrs, _ptr(used[0]), _ptr(used[1]), self._stream()))
+        return FbQpModel(*qp, used[0], used[1]) if want_model else FbQp(*qp)
+
+    def run_fbmpc_preview(self, s0, v0, a_minus1, s_tv, v_tv, n_steps=None, resume: bool = False, out=None):
+        """eepacc_run_fbmpc_preview: run_fbmpc whose steps take the lead's horizon guess from the lead trace itself, by the
+        rule of run_abmpc_preview (scenarios.lead_preview); the ego estimator stays the engine's.  Arguments and results as
+        run_abmpc_preview."""
+        return self._run_preview(self.lib.eepacc_run_fbmpc_preview, s0, v0, a_minus1, s_tv, v_tv, n_steps, resume, out)
+
     def postprocess(self, traj):
         t = self.torch
         n_steps, _, B = traj.shape
@@ -833,13 +870,13 @@ def generate_lead_and_run(OPTsettings: Dict[str, Any], V: Optional[Dict[str, flo
     The two controllers share the sample grid, so TV_Ts must equal Tvec[0]: anything else is refused, not resampled.
     preview=True (kind "ab" or "bl"): the generated trace is also the controller's guess of the lead's future, through
     run_abmpc_preview / run_blmpc_preview with n_lead = n_steps, so that ABMPC and its yardstick can be given the same
-    information; FBMPC has no such entry and raises ValueError.
+    information; kind="fb" with preview raises ValueError here (Engine.run_fbmpc_preview is the FBMPC preview loop).
     Returns (traj, status, s_tv, v_tv): the ego closed loop and the [n_steps, batch] lead traces it was fed."""
     from .settings import SetVehicleParameters, Settings_TV, Settings_BL
     if kind not in ("ab", "fb", "bl"):
         raise ValueError("kind must be 'ab', 'fb' or 'bl'")
     if preview and kind == "fb":
-        raise ValueError("preview=True: FBMPC has no entry with supplied horizon guesses; kind must be 'ab' or 'bl'")
+        raise ValueError("preview=True: kind must be 'ab' or 'bl' here; the FBMPC preview loop is Engine.run_fbmpc_preview")
     Ts = float(np.asarray(OPTsettings["Tvec"]).ravel()[0])
     if float(OPTsettings["TV_Ts"]) != Ts:
         raise ValueError("TV_Ts = %g differs from Tvec[0] = %g: the lead trace would have to be resampled (ABO/Main.m:82-89 "

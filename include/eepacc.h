@@ -273,8 +273,9 @@ int  eepacc_ab_step(eepacc_handle* h, int B,
  * The baseline controller's counterparts are eepacc_bl_step_est, eepacc_bl_build_qp_est and eepacc_run_blmpc_preview, below; on a
  * bl_mode = 1 handle the message of these three entries points to them.
  * Class handles have entries of their own, eepacc_classes_step_est and eepacc_run_classes_preview, below.
- * Not built: supplied guesses for FBMPC, for the target-vehicle controller, for move blocking and the ICE map, and a preview
- * of the ego estimate.
+ * FBMPC's counterparts are eepacc_fb_step_est, eepacc_fb_build_qp_est and eepacc_run_fbmpc_preview, after eepacc_fb_build_qp.
+ * Not built: supplied guesses for FBMPC steps through the dense path (the builder entry serves such handles) and for FBMPC
+ * settings classes, for the target-vehicle controller, for move blocking and the ICE map, and a preview of the ego estimate.
  * Cost against eepacc_ab_step / eepacc_run_abmpc: tools/gpu_ab_est_bench.py, DESIGN.md section 3.4f. */
 int  eepacc_ab_step_est(eepacc_handle* h, int B,
                         const double* s, const double* v, const double* a_prev, const double* t0,
@@ -538,6 +539,66 @@ int  eepacc_fb_build_qp(eepacc_handle* h, int B,
                         const double* A22, const double* D2,
                         double* H, double* g, double* A, double* lba, double* uba,
                         double* A22_used, double* D2_used, void* stream);
+
+/* FBMPC with the horizon guesses supplied: the contract of CreateQP_FB(OPTsettings, ..., s_est, v_est, s_tv_est, ...)
+ * (ABO/RunOpt_FBMPC.m:215), which linearises about v_est (the drag terms of the objective, the acceleration and jerk rows, the
+ * headway row with FBuseTaylor = 1), reads the route bounds at s_est, and whose loop makes the model entry A(k), D(k) of MPC
+ * step k of v_est(N_hor) (:247-259).  The three entries are the counterparts of eepacc_ab_step_est, eepacc_ab_build_qp_est and
+ * eepacc_run_abmpc_preview, above, and the guess arrays follow the same contract:
+ *   s_est, v_est, s_tv_est: device arrays [N_hor+1][B], the layout of s_pred / v_pred.
+ *   s_est and v_est are given together or both NULL; NULL: the handle's paramEstSetting, mode 2 from the carried predictions
+ *   included.  s_tv_est may be NULL: the handle's TVestSetting.  Either side may be given without the other.
+ *   Row 0 of s_est and v_est is used as given.  Row N_hor of s_tv_est is not read: the terminal rows use stage N_hor-1
+ *   (s_tv_est(N) of CreateQP_FB.m:478-489).  +inf in s_tv_est: no lead at that stage (the three headway rows of the stage, and
+ *   the terminal rows if the stage is N_hor-1, then bind nothing).
+ *   All three NULL: bit for bit eepacc_fb_step / eepacc_fb_build_qp.
+ *   The slope.  The reference's CreateQP_FB sees slope(1) at every stage, whatever s_est says.  eepacc_fb_build_qp_est follows
+ *   it, as eepacc_fb_build_qp does.  eepacc_fb_step_est and eepacc_run_fbmpc_preview look the slope up at s_est, as eepacc_fb_step
+ *   and eepacc_run_fbmpc do.  On a slope table that is constant (one value along the route) the three agree.  On a table that is
+ *   not constant they differ: a supplied s_est then moves the slope of the step, and the step does not solve the problem that
+ *   the builder entry writes.  This is the behaviour of the structured FBMPC kernels before these entries and is not tested on
+ *   such a table (DESIGN.md sections 3.5e and 7).
+ *
+ * eepacc_fb_step_est reads and writes exactly the handle state eepacc_fb_step does (working-set codes, the model A22 / D2, the
+ * carried predictions, the step counter, the by-step flag): the two can alternate on one handle.  With FBuseTaylor = 1 the
+ * entry frozen at k == step is computed from the supplied v_est[N_hor-1]; with FBuseTaylor = 0 D2 comes from the supplied v_est
+ * at every stage: what the reference's loop does with those arrays.
+ *
+ * eepacc_fb_build_qp_est covers what eepacc_fb_build_qp covers (Mb, b_quadr(4) != 0, both FBuseTaylor, dense-path handles, the
+ * A22 / D2 rules); it reads no solver state and writes none.  The only difference is where the three guesses come from, and
+ * with them the k == step model entry when A22 == D2 == NULL.
+ *
+ * eepacc_run_fbmpc_preview: eepacc_run_fbmpc with the lead's horizon guess read from the lead trace itself, by exactly the
+ * rule of eepacc_run_abmpc_preview: s_tv, v_tv [n_lead][B], n_lead >= n_steps, idx / frac computed once per handle in long
+ * double with the same snapping (one table per handle, shared with the ABMPC preview), linear extrapolation past the last row,
+ * +inf stays +inf; scenarios.lead_preview states the rule.  The ego estimator stays the handle's.  Launches resume as
+ * eepacc_run_fbmpc's do, the caller passing the continued rows.
+ *
+ * EEPACC_ENOTSUP, the message naming the cause: a handle of eepacc_create_classes / _classes_bl and a handle with bl_mode != 0
+ * (all three entries); for the step and the preview entry also a handle whose FBMPC steps go through the dense path (Mb,
+ * b_quadr(4) != 0, EEPACC_FB_DENSE=1), where the message says that the builder entry still works.  EEPACC_EINVAL: a NULL
+ * required buffer, s_est without v_est or the reverse, B out of range, n_lead < n_steps, and the builder's A22 / D2 rules.
+ * B = 0 returns EEPACC_OK.
+ * Cost against eepacc_fb_step / eepacc_run_fbmpc: tools/gpu_fb_est_bench.py, DESIGN.md section 3.5e. */
+int  eepacc_fb_step_est(eepacc_handle* h, int B,
+                        const double* s, const double* v, const double* v_prev,
+                        const double* a_prev, const double* Fm_prev, const double* Fb_prev,
+                        const double* t0, const double* s_tv, const double* v_tv,
+                        const double* a_tv_prev,
+                        const double* s_est, const double* v_est, const double* s_tv_est,
+                        double* out, double* s_pred, double* v_pred, int32_t* status,
+                        void* stream);
+int  eepacc_fb_build_qp_est(eepacc_handle* h, int B,
+                            const double* s, const double* v, const double* a_prev, const double* t0,
+                            const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                            const double* s_est, const double* v_est, const double* s_tv_est,
+                            const double* A22, const double* D2,
+                            double* H, double* g, double* A, double* lba, double* uba,
+                            double* A22_used, double* D2_used, void* stream);
+int  eepacc_run_fbmpc_preview(eepacc_handle* h, int B, int n_steps, int n_lead,
+                              const double* s0, const double* v0, const double* a_minus1,
+                              const double* s_tv, const double* v_tv,
+                              double* traj, int32_t* status, void* stream);
 
 /* Host-pointer convenience wrappers (what a MEX gateway calls). */
 int  eepacc_run_abmpc_host(eepacc_handle* h, int B, int n_steps,
