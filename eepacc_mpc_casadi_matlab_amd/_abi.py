@@ -102,6 +102,13 @@ FB_EST_ARGTYPES = {
     "eepacc_run_fbmpc_preview": list(AB_EST_ARGTYPES["eepacc_run_abmpc_preview"]),
 }
 
+# FBMPC on a handle with settings classes (eepacc_create_classes): arguments and order are those of eepacc_fb_step (ten
+# inputs, four outputs) and eepacc_run_fbmpc (B, n_steps, five inputs, two outputs)
+CLASSES_FB_ARGTYPES = {
+    "eepacc_classes_fb_step": [C.c_void_p, C.c_int] + [C.c_void_p] * 10 + [C.c_void_p] * 4 + [C.c_void_p],
+    "eepacc_run_classes_fbmpc": [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_void_p] * 2 + [C.c_void_p],
+}
+
 # enum EEPACC_BL_ROW_*: the row types of eepacc_bl_qp_rows, ascending in the order of the rows within a stage (a handle created
 # with bl_mode = 2 has none of the two safe-distance types)
 BL_ROW_TYPES = ["s", "v", "xi_f", "a_min", "a_max", "j_min", "j_max", "v_lim", "v_curv", "v_stop", "v_tl", "safe1", "safe2"]

@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libeepacc.so")
 FLAGFILE = os.path.join(HERE, "libeepacc.flags")
-SOURCES = ["eepacc_kernels.hip", "eepacc_ab_build.hip", "eepacc_ab_build_est.hip", "eepacc_ab_build_cls.hip", "eepacc_bl_qp.hip", "eepacc_bl_qp_est.hip", "eepacc_bl_qp_cls.hip", "eepacc_qp_dense.hip", "eepacc_fb.hip", "eepacc_fb_qp.hip", "eepacc_fb_qp_est.hip", "eepacc_fbs.hip", "eepacc_fbs_est.hip", "eepacc_kpis.hip", "eepacc_follow.hip", "eepacc_route.hip", "eepacc_capi.cpp", "eepacc_cfg.cpp", "eepacc_casadi_c.cpp", "eepacc_nlp.hip", "eepacc_nlp_tables.cpp"]
+SOURCES = ["eepacc_kernels.hip", "eepacc_ab_build.hip", "eepacc_ab_build_est.hip", "eepacc_ab_build_cls.hip", "eepacc_bl_qp.hip", "eepacc_bl_qp_est.hip", "eepacc_bl_qp_cls.hip", "eepacc_qp_dense.hip", "eepacc_fb.hip", "eepacc_fb_qp.hip", "eepacc_fb_qp_est.hip", "eepacc_fbs.hip", "eepacc_fbs_est.hip", "eepacc_fbs_cls.hip", "eepacc_kpis.hip", "eepacc_follow.hip", "eepacc_route.hip", "eepacc_capi.cpp", "eepacc_cfg.cpp", "eepacc_casadi_c.cpp", "eepacc_nlp.hip", "eepacc_nlp_tables.cpp"]
 BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 
 
@@ -35,7 +35,7 @@ def built_flags() -> str | None:
 def headers() -> list[str]:
     """Everything a source can include: a change to any of them makes every object stale."""
     inc = os.path.join(HERE, os.pardir, "include")
-    # (eepacc_fbs.hip: eepacc_fbs_est.hip includes it for the kernel templates)
+    # (eepacc_fbs.hip: eepacc_fbs_est.hip and eepacc_fbs_cls.hip include it for the kernel templates)
     return (glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + glob.glob(os.path.join(inc, "*.h"))
             + [os.path.join(CSRC, "eepacc_fbs.hip")])
 

@@ -87,6 +87,10 @@ struct eepacc_handle {
     // structured FBMPC path (eepacc_fbs.hip): per-instance state, closed-loop carry, base-inverse scratch
     bool fbs = false;                        // settings are covered by the structured solver
     DevMem<double> fbs_state, fbs_carry, fbs_hb;
+    // The same on a handle of eepacc_create_classes (eepacc_fbs_cls.hip: eepacc_classes_fb_step, eepacc_run_classes_fbmpc), where
+    // every class is covered and the horizon fits: fbs stays false there, since eepacc_fb_step / eepacc_run_fbmpc refuse class handles
+    bool fbs_cls = false;
+    std::vector<const char*> fb_unsup;       // [n_classes] eepacc::fbs_unsupported_field of every class (bl_mode = 0 classes only)
     // Settings classes (eepacc_create_classes): d_cfg holds DevCfg[n_classes], d_Hinv one N x N block per class and cfg is
     // class 0, whose N and Tvec every class shares.  n_classes = 0 marks a handle of eepacc_create.
     int n_classes = 0;
@@ -181,7 +185,14 @@ static int create_on_device(eepacc_handle** out, std::vector<DevCfg>& Cs, const 
     // FBMPC: structured kernels unless the settings need the dense path (or EEPACC_FB_DENSE=1 asks for it)
     h->fbs = !classes && eepacc::fbs_supported(C) && eepacc::fbs_smem_bytes(C.N) <= 160 * 1024 - 4608;
     if (const char* e = getenv("EEPACC_FB_DENSE")) if (atoi(e) != 0) h->fbs = false;
-    if (h->fbs) {
+    if (classes && C.bl_mode == 0) {
+        h->fbs_cls = eepacc::fbs_smem_bytes(C.N) <= eepacc::kFbsLdsBudget;
+        for (const DevCfg& Ck : Cs) {
+            h->fb_unsup.push_back(eepacc::fbs_unsupported_field(Ck));
+            if (h->fb_unsup.back()) h->fbs_cls = false;
+        }
+    }
+    if (h->fbs || h->fbs_cls) {
         HIPCHK(eepacc::fbs_set_max_smem());
         HIPCHK(h->fbs_state.alloc_zero(nB * eepacc::kFbsStateDoubles));
         HIPCHK(h->fbs_carry.alloc_zero(nB * 6));
@@ -1247,6 +1258,65 @@ extern "C" int eepacc_run_fbmpc(eepacc_handle* h, int B, int n_steps, const doub
     if (B < 0 || B > h->max_batch || n_steps < 0) return fail(EEPACC_EINVAL, "eepacc_run_fbmpc: bad B / n_steps");
     if (B == 0 || n_steps == 0) return EEPACC_OK;
     return fb_run_impl("eepacc_run_fbmpc", h, B, n_steps, s0, v0, a_minus1, s_tv, v_tv, traj, status, stream, nullptr);
+}
+
+// ---- FBMPC on a handle with settings classes: eepacc_classes_fb_step, eepacc_run_classes_fbmpc.  Every refusal is
+// eepacc::classes_fb_refusal (eepacc_cfg.cpp); the kernels are those of eepacc_fbs_cls.hip, on FBMPC state of the handle's own
+// (fbs_state, fbs_carry, fbs_hb, fb_k_done) beside the ABMPC state, as on a structured handle of eepacc_create.
+static int classes_fb_call(const eepacc_handle* h, const std::string& who, int B, int n_steps, const char* null_buffer) {
+    if (!h) return fail(EEPACC_EINVAL, who + ": NULL handle");
+    const eepacc::ClassesFbCall c{h->n_classes, h->cfg.bl_mode, h->cfg.N, h->fb_unsup.data(), eepacc::fbs_smem_bytes(h->cfg.N),
+                                  eepacc::kFbsLdsBudget, h->max_batch, h->classes_B, B, n_steps, null_buffer};
+    return eepacc::classes_fb_refusal(who, c);
+}
+struct NamedBuf { const void* p; const char* name; };
+template <size_t n>
+static const char* first_null(const NamedBuf (&bufs)[n]) {
+    for (const NamedBuf& bf : bufs) if (!bf.p) return bf.name;
+    return nullptr;
+}
+
+extern "C" int eepacc_classes_fb_step(eepacc_handle* h, int B, const double* s, const double* v, const double* v_prev,
+                                      const double* a_prev, const double* Fm_prev, const double* Fb_prev, const double* t0,
+                                      const double* s_tv, const double* v_tv, const double* a_tv_prev,
+                                      double* out, double* s_pred, double* v_pred, int32_t* status, void* stream) {
+    (void)v_prev; (void)Fm_prev; (void)Fb_prev;   // accepted and unused, as in eepacc_fb_step
+    const NamedBuf bufs[] = {{s, "s"}, {v, "v"}, {a_prev, "a_prev"}, {t0, "t0"}, {s_tv, "s_tv"}, {v_tv, "v_tv"},
+                             {a_tv_prev, "a_tv_prev"}, {out, "out"}, {status, "status"}};
+    if (const int rc = classes_fb_call(h, "eepacc_classes_fb_step", B, 1, first_null(bufs))) return rc;
+    if (B == 0) return EEPACC_OK;
+    HIPCHK(hipSetDevice(h->device));
+    eepacc::fbs_step_args a;
+    a.cfg = h->d_cfg; a.B = B; a.k_step = h->fb_k_done;
+    a.s = s; a.v = v; a.a_prev = a_prev; a.t0 = t0; a.s_tv = s_tv; a.v_tv = v_tv; a.a_tv_prev = a_tv_prev;
+    a.state = h->fbs_state; a.hb = h->fbs_hb; a.out = out; a.s_pred = s_pred; a.v_pred = v_pred;
+    a.status = status; a.iters = h->d_iters;
+    HIPCHK(eepacc::launch_fbs_step_cls(a, h->cfg.N, (hipStream_t)stream, h->d_class_of));
+    h->fb_k_done += 1; h->last_B = B; h->fb_by_step = true;
+    return EEPACC_OK;
+}
+
+extern "C" int eepacc_run_classes_fbmpc(eepacc_handle* h, int B, int n_steps, const double* s0, const double* v0,
+                                        const double* a_minus1, const double* s_tv, const double* v_tv,
+                                        double* traj, int32_t* status, void* stream) {
+    const std::string who = "eepacc_run_classes_fbmpc";
+    const NamedBuf bufs[] = {{s0, "s0"}, {v0, "v0"}, {a_minus1, "a_minus1"}, {s_tv, "s_tv"}, {v_tv, "v_tv"}, {traj, "traj"}, {status, "status"}};
+    if (const int rc = classes_fb_call(h, who, B, n_steps, first_null(bufs))) return rc;
+    if (B == 0 || n_steps == 0) return EEPACC_OK;
+    HIPCHK(hipSetDevice(h->device));
+    // (B is that of the class map, so it cannot change while resuming)
+    if (h->fb_k_done > 0 && h->fb_by_step)
+        return fail(EEPACC_EINVAL, who + " after eepacc_classes_fb_step: the per-step operator keeps no closed-loop state to resume from; call eepacc_reset first");
+    eepacc::fbs_run_args a;
+    a.cfg = h->d_cfg; a.B = B; a.k_start = h->fb_k_done; a.n_steps = n_steps;
+    a.s0 = s0; a.v0 = v0; a.a_m1 = a_minus1; a.s_tv = s_tv; a.v_tv = v_tv;
+    a.carry = h->fbs_carry; a.state = h->fbs_state; a.hb = h->fbs_hb; a.traj = traj; a.status = status;
+    a.iters_total = h->d_iters; a.work_counter = h->d_counter; a.done = h->d_done; a.err_word = h->d_err;
+    a.chunk_steps = eepacc::pick_chunk_steps(n_steps, B, eepacc::fbs_run_chunking_waves(h->cfg.N, h->num_cus));      // as eepacc_run_fbmpc
+    a.cold = 0;
+    HIPCHK(eepacc::launch_fbs_run_cls(a, h->cfg.N, h->num_cus, (hipStream_t)stream, h->d_class_of));
+    h->fb_k_done += n_steps; h->last_B = B;
+    return EEPACC_OK;
 }
 
 extern "C" int eepacc_run_fbmpc_preview(eepacc_handle* h, int B, int n_steps, int n_lead, const double* s0, const double* v0,

@@ -234,6 +234,43 @@ int fb_est_refusal(const std::string& who, int n_classes, const DevCfg& C, bool 
                                      "; supplied horizon guesses are built for the structured kernels only.  eepacc_fb_build_qp_est still builds the problem of such a handle");
 }
 
+// What the structured FBMPC solver (eepacc_fbs.hip) does not represent of a DevCfg: the field, with the reason, or NULL.
+const char* fbs_unsupported_field(const DevCfg& C) {
+    if (C.mb_any) return "Mb != 0 (blocked moves keep their equality rows, CreateQP_FB.m:346-356)";
+    if (C.b_quadr[3] != 0.0) return "b_quadr(4) != 0 (the Fm^2 term of the power fit would give the friction-brake share its own curvature)";
+    const double Kr = (30.0 / 3.14159265358979323846) * C.phi;
+    if (!(C.fb_w[0] * Kr * C.b_quadr[4] > 0.0)) return "W_FB(1) * b_quadr(5) is not positive (the price of the friction-brake share must rise with speed)";
+    if (!(C.fb_w[4] > 0.0) || C.fb_w[3] < 0.0 || C.fb_w[5] < 0.0 || C.fb_w[6] < 0.0 || !(C.fb_w[1] > 0.0))
+        return "W_FB (W_FB(2) and W_FB(5) must be positive, W_FB(4), W_FB(6) and W_FB(7) not negative)";
+    return nullptr;
+}
+
+// eepacc_classes_fb_step, eepacc_run_classes_fbmpc: what they refuse of a handle and of a call (header: EEPACC_ENOTSUP for a handle
+// that has no FBMPC class kernels to run, EEPACC_EINVAL for the arguments of a call on one that has).
+int classes_fb_refusal(const std::string& who, const ClassesFbCall& c) {
+    if (!c.n_classes)
+        return set_error(EEPACC_ENOTSUP, who + ": this handle has no settings classes (it was created by eepacc_create); eepacc_fb_step / eepacc_run_fbmpc run FBMPC on such a handle");
+    if (c.bl_mode != 0)
+        return set_error(EEPACC_ENOTSUP, who + ": a handle of eepacc_create_classes_bl holds classes of the baseline or target-vehicle controller (bl_mode = " +
+                                         std::to_string(c.bl_mode) + "); FBMPC classes are those of eepacc_create_classes (bl_mode = 0)");
+    for (int k = 0; k < c.n_classes; ++k)
+        if (c.unsupported[k])
+            return set_error(EEPACC_ENOTSUP, who + ": class " + std::to_string(k) + ": " + c.unsupported[k] +
+                                             "; the structured FBMPC kernels do not represent it, and classes have no dense path");
+    if (c.smem_bytes > c.smem_budget)
+        return set_error(EEPACC_ENOTSUP, who + ": class 0: N_hor = " + std::to_string(c.N) + " needs " + std::to_string(c.smem_bytes) + " bytes of LDS per block, above the " +
+                                         std::to_string(c.smem_budget) + " of the structured FBMPC kernels; classes have no dense path");
+    if (c.B < 0 || c.B > c.max_batch)
+        return set_error(EEPACC_EINVAL, who + ": B = " + std::to_string(c.B) + " is outside [0, max_batch = " + std::to_string(c.max_batch) + "]");
+    if (c.n_steps < 0) return set_error(EEPACC_EINVAL, who + ": n_steps = " + std::to_string(c.n_steps) + " is negative");
+    if (c.B == 0 || c.n_steps == 0) return EEPACC_OK;
+    if (c.null_buffer) return set_error(EEPACC_EINVAL, who + ": " + c.null_buffer + " is NULL");
+    if (!c.classes_B) return set_error(EEPACC_EINVAL, who + ": eepacc_set_classes has not been called on this handle");
+    if (c.B != c.classes_B)
+        return set_error(EEPACC_EINVAL, who + ": B = " + std::to_string(c.B) + " differs from the B = " + std::to_string(c.classes_B) + " of the last eepacc_set_classes");
+    return EEPACC_OK;
+}
+
 // What eepacc_kpis reads of a class (validated by build_cfg before): the power fit and driveline of the energy, the fuel
 // map and coast-down terms of ABO/Custom_plots.m:73-107 and the speed-limit table of ABO/Main.m:133.
 KpiCfg build_kpi_cfg(const eepacc_settings* S, const eepacc_vehicle* V) {

@@ -34,6 +34,24 @@ void preview_tables(const double* Tvec, int N, int32_t* idx, double* frac);
 // (the builder serves dense-path handles too).  EEPACC_OK, or EEPACC_ENOTSUP with the cause through set_error.
 int fb_est_refusal(const std::string& who, int n_classes, const DevCfg& C, bool structured, bool needs_structured);
 
+// What the structured FBMPC solver does not represent of C: the settings field with the reason, or NULL where it runs C
+// (eepacc::fbs_supported is this test).
+const char* fbs_unsupported_field(const DevCfg& C);
+
+// Whether eepacc_classes_fb_step / eepacc_run_classes_fbmpc (who) serve a call.  Of the handle: n_classes (0: one of
+// eepacc_create), bl_mode and N of class 0, unsupported [n_classes] = fbs_unsupported_field of every class, the LDS a block of
+// the kernels needs at N and may have, max_batch and the B of the last eepacc_set_classes (0: none).  Of the call: B, n_steps
+// (the step entry passes 1) and the name of its first required buffer that is NULL (or NULL).  EEPACC_OK (also for B = 0 or
+// n_steps = 0, before the buffers are looked at), EEPACC_ENOTSUP for the handle, EEPACC_EINVAL for the call; text through set_error.
+struct ClassesFbCall {
+    int n_classes, bl_mode, N;
+    const char* const* unsupported;
+    size_t smem_bytes, smem_budget;
+    int max_batch, classes_B, B, n_steps;
+    const char* null_buffer;
+};
+int classes_fb_refusal(const std::string& who, const ClassesFbCall& c);
+
 // Of settings that build_cfg has accepted.
 KpiCfg build_kpi_cfg(const eepacc_settings* S, const eepacc_vehicle* V);
 FollowCfg build_follow_cfg(const eepacc_settings* S, const eepacc_vehicle* V);

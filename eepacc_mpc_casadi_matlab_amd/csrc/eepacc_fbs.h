@@ -44,6 +44,7 @@ constexpr int kFMMaxLarge = 66, kFNSLarge = 64, kFWpbLarge = 1;     // N <= 63
 // dynamic LDS a block may ask for: 160 KB per CU minus the kernels' static index table (one ushort per packed entry of P)
 constexpr size_t kFbsLdsBudget = 160 * 1024 - 4608;
 
+const char* fbs_unsupported_field(const DevCfg& C);     // eepacc_cfg.cpp (declared in eepacc_cfg.h too): NULL, or what the solver lacks
 bool fbs_supported(const DevCfg& C);
 size_t fbs_smem_bytes(int N);
 int fbs_run_max_grid(int N, int num_cus);           // blocks of a chip-filling closed-loop launch
@@ -66,6 +67,12 @@ hipError_t launch_fbs_step_est(const fbs_step_args& a, int N, hipStream_t stream
                                const double* s_tv_est);
 hipError_t launch_fbs_run_preview(fbs_run_args a, int N, int num_cus, hipStream_t stream, const int32_t* idx, const double* frac,
                                   int n_lead);
+
+// The kernels of a handle with settings classes (eepacc_fbs_cls.hip), on the same scratch and grids.  a.cfg is the handle's
+// class array DevCfg[n_classes] (N and Tvec are those of its head) and class_of [a.B] the class of every instance, on the device.
+hipError_t fbs_cls_set_max_smem();
+hipError_t launch_fbs_step_cls(const fbs_step_args& a, int N, hipStream_t stream, const int32_t* class_of);
+hipError_t launch_fbs_run_cls(fbs_run_args a, int N, int num_cus, hipStream_t stream, const int32_t* class_of);
 
 }  // namespace eepacc
 #endif

@@ -29,7 +29,8 @@
 // argument pack: the estimators' horizon guesses; the host-side launchers at the end) and eepacc_fbs_est.hip, which includes this
 // file with EEPACC_FBS_KERNELS_ONLY defined and instantiates the same two templates with further arguments (the guesses of the
 // caller: eepacc_fb_step_est, eepacc_run_fbmpc_preview).  Two units so that the kernels of the first
-// keep their code (profiles/fb_est_codegen.txt).
+// keep their code (profiles/fb_est_codegen.txt).  A third, eepacc_fbs_cls.hip, does the same with the class map of a handle of
+// eepacc_create_classes as the one further argument (eepacc_classes_fb_step, eepacc_run_classes_fbmpc).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -1427,15 +1428,31 @@ __device__ __forceinline__ double* st_D2(double* s) { return s + 128; }
 __device__ __forceinline__ double* st_sp(double* s) { return s + 192; }
 __device__ __forceinline__ double* st_vp(double* s) { return s + 256; }
 
-// B2: one step for B instances.  extra: nothing, or the three supplied arrays s_est, v_est, s_tv_est (eepacc_fbs_est.hip)
+// The settings of instance b.  The kernels of eepacc_fbs_cls.hip (a handle of eepacc_create_classes) have one further argument,
+// the class map of the launch (class_of [B], values checked by eepacc_set_classes), and their a.cfg is the handle's class
+// array: C0 is its head, whose N and Tvec every class shares.  One wave serves one instance, and the index is made wave-uniform
+// by construction, so that every read of the instance's DevCfg stays a scalar load.  A pack of one argument is the class map;
+// the packs of eepacc_fbs_est.hip hold three.  Every other kernel gets C0 back: the same reference as before.
+template <class... Extra> constexpr bool kClassPack = sizeof...(Extra) == 1;
+template <class... Extra>
+__device__ __forceinline__ const DevCfg& cfg_of(const DevCfg& C0, int b, Extra... extra) {
+    if constexpr (kClassPack<Extra...>) {
+        const int32_t* map = (extra, ...);
+        return (&C0)[__builtin_amdgcn_readfirstlane(map[b])];
+    } else return C0;
+}
+
+// B2: one step for B instances.  extra: nothing, the three supplied arrays s_est, v_est, s_tv_est (eepacc_fbs_est.hip), or the
+// class map (eepacc_fbs_cls.hip).  A block of the N <= 32 kernel holds WPB instances of possibly as many classes: C is bound per wave.
 template <int MMAX, int NS, int WPB, class... Extra>
 __global__ void __launch_bounds__(64 * WPB)
 k_fbs_step(fbs_step_args a, Extra... extra) {
     extern __shared__ __align__(16) unsigned char smem[];
-    const DevCfg& C = *a.cfg;
+    const DevCfg& C0 = *a.cfg;
     rc_table_init<MMAX>();
     const int b = blockIdx.x * WPB + (threadIdx.x >> 6);
     if (b >= a.B) return;
+    const DevCfg& C = cfg_of(C0, b, extra...);
     double* Hs;
     FMem<MMAX, NS>& M = *wave_mem<MMAX, NS>(smem, Hs);
     double* Hb = a.hb + ((size_t)blockIdx.x * WPB + (threadIdx.x >> 6)) * (NS * NS);
@@ -1448,7 +1465,7 @@ k_fbs_step(fbs_step_args a, Extra... extra) {
     const double ps = st_sp(stt)[idx], pv = st_vp(stt)[idx];
     StepOut so;
     double sp, vp;
-    if constexpr (sizeof...(Extra) != 0)
+    if constexpr (sizeof...(Extra) != 0 && !kClassPack<Extra...>)
         fb_step<MMAX, NS>(C, M, Hs, Hb, in, A22, D2, code, so, sp, vp, ps, pv, est_supplied(lane, N, a.B, b, extra...));
     else
     fb_step<MMAX, NS>(C, M, Hs, Hb, in, A22, D2, code, so, sp, vp, ps, pv);
@@ -1463,10 +1480,25 @@ k_fbs_step(fbs_step_args a, Extra... extra) {
 
 // B1: closed loop over n_steps for B instances (ABO/RunOpt_FBMPC.m:161-331) in work units (run_units, eepacc_units.h).
 // extra: nothing, or the preview tables idx, frac and n_lead (eepacc_fbs_est.hip): the lead's guess of every step is read from
-// the launch's lead traces, a.s_tv / a.v_tv [n_lead][B]
+// the launch's lead traces, a.s_tv / a.v_tv [n_lead][B]; or the class map (eepacc_fbs_cls.hip): a wave serves another instance in
+// every work unit, so C is bound once more inside the unit's body (it hides the kernel's C, class 0, of which only N and Ts, which
+// the classes share, are read outside the body).  That line is a macro and empty in the other units: bound through cfg_of there
+// too, k_fbs_step comes out with the same machine code but k_fbs_run does not (a few instructions of the N <= 32 kernel's spill
+// code move), and those kernels are to stay what they were (profiles/classes_fb_codegen.txt).
+#undef EEPACC_FBS_UNIT_CFG
+#ifdef EEPACC_FBS_CLASS_MAP
+#define EEPACC_FBS_UNIT_CFG const DevCfg& C = cfg_of(*a.cfg, b, extra...);
+#else
+#define EEPACC_FBS_UNIT_CFG
+#endif
 template <int MMAX, int NS, int WPB, class... Extra>
 __global__ void __launch_bounds__(64 * WPB, ((NS <= 32 && WPB <= 2) ? 2 : 1))
 k_fbs_run(fbs_run_args a, Extra... extra) {
+#ifdef EEPACC_FBS_CLASS_MAP
+    static_assert(kClassPack<Extra...>, "EEPACC_FBS_CLASS_MAP is defined by eepacc_fbs_cls.hip, whose kernels have the class map as their one further argument");
+#else
+    static_assert(!kClassPack<Extra...>, "the class kernels are instantiated by eepacc_fbs_cls.hip, which defines EEPACC_FBS_CLASS_MAP");
+#endif
     extern __shared__ __align__(16) unsigned char smem[];
     const DevCfg& C = *a.cfg;
     rc_table_init<MMAX>();
@@ -1477,6 +1509,7 @@ k_fbs_run(fbs_run_args a, Extra... extra) {
     const double Ts = C.Tvec[0];
     run_units(B, a.n_steps, a.chunk_steps, a.work_counter, a.done, a.err_word, a.spin_limit, a.status, a.iters_total,
               [&](int b, int kk0, int kk1) {
+        EEPACC_FBS_UNIT_CFG
         double* stt = a.state + (size_t)b * kFbsStateDoubles;
         unsigned long long code = 0ull;
         double A22 = 1.0, D2 = 0.0;
@@ -1498,7 +1531,7 @@ k_fbs_run(fbs_run_args a, Extra... extra) {
             measure(C, Ts, in.k_step, kk, B, b, a.s0, a.v0, a.a_m1, a.s_tv, a.v_tv, cs, in);
             StepOut so;
             double sp, vp;
-            if constexpr (sizeof...(Extra) != 0)
+            if constexpr (sizeof...(Extra) != 0 && !kClassPack<Extra...>)
                 fb_step<MMAX, NS>(C, M, Hs, Hb, in, A22, D2, code, so, sp, vp, ps, pv,
                                   est_preview(C, lane, B, b, kk, a.s_tv, a.v_tv, extra...));
             else
@@ -1539,14 +1572,8 @@ extern "C" int eepacc_debug_fbs_prof(unsigned long long* out, int reset) {
 // host-side launchers used by eepacc_capi.cpp (size classes and LDS budget: eepacc_fbs.h)
 
 // settings the structured solver represents; everything else goes through the dense path (eepacc_fb.hip)
-bool fbs_supported(const DevCfg& C) {
-    if (C.mb_any) return false;                 // blocked moves (CreateQP_FB.m:346-356) keep their equality rows
-    if (C.b_quadr[3] != 0.0) return false;      // Fm^2 term of the power fit would give w its own curvature
-    const double Kr = (30.0 / 3.14159265358979323846) * C.phi;
-    if (!(C.fb_w[0] * Kr * C.b_quadr[4] > 0.0)) return false;   // price of the friction-brake share must rise with speed
-    if (!(C.fb_w[4] > 0.0) || C.fb_w[3] < 0.0 || C.fb_w[5] < 0.0 || C.fb_w[6] < 0.0 || !(C.fb_w[1] > 0.0)) return false;
-    return true;
-}
+// (the conditions, each with the field it names in a refusal: eepacc::fbs_unsupported_field, eepacc_cfg.cpp, host only)
+bool fbs_supported(const DevCfg& C) { return fbs_unsupported_field(C) == nullptr; }
 
 size_t fbs_smem_bytes(int N) {
     return N <= kFNSSmall ? fbs::wave_bytes(sizeof(fbs::FMem<kFMMaxSmall, kFNSSmall>), kFNSSmall) * kFWpbSmall
@@ -1577,7 +1604,8 @@ hipError_t fbs_set_max_smem() {
         hipError_t e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFbsLdsBudget);
         if (e != hipSuccess) return e;
     }
-    return fbs_est_set_max_smem();      // the four kernels of eepacc_fbs_est.hip: a handle may launch either set
+    if (const hipError_t e = fbs_est_set_max_smem()) return e;      // the four kernels of eepacc_fbs_est.hip: a handle may launch either set
+    return fbs_cls_set_max_smem();      // and the four of eepacc_fbs_cls.hip, for a handle of eepacc_create_classes
 }
 
 hipError_t launch_fbs_step(const fbs_step_args& a, int N, hipStream_t stream) {

@@ -13,7 +13,7 @@ from typing import Any, Dict, NamedTuple, Optional
 
 import numpy as np
 
-from ._abi import (SettingsHolder, SettingsPOD, Vehicle, make_vehicle, pack_classes, OUT, OUT_N, OUT_FIELDS, KPI_N, FKPI_N, FKPI_WEIGHTS, RKPI_N, RLIM_N, ROUTE_KPIS_ARGTYPES, AB_BUILD_ARGTYPES, AB_EST_ARGTYPES, BL_EST_ARGTYPES, FB_EST_ARGTYPES, CLASSES_EST_ARGTYPES, CLASSES_BUILD_ARGTYPES,
+from ._abi import (SettingsHolder, SettingsPOD, Vehicle, make_vehicle, pack_classes, OUT, OUT_N, OUT_FIELDS, KPI_N, FKPI_N, FKPI_WEIGHTS, RKPI_N, RLIM_N, ROUTE_KPIS_ARGTYPES, AB_BUILD_ARGTYPES, AB_EST_ARGTYPES, BL_EST_ARGTYPES, FB_EST_ARGTYPES, CLASSES_EST_ARGTYPES, CLASSES_BUILD_ARGTYPES, CLASSES_FB_ARGTYPES,
                    FB_BUILD_ARGTYPES, BL_BUILD_ARGTYPES,
                    c_double_p, as_dptr, as_iptr)
 
@@ -75,7 +75,7 @@ def load_library() -> C.CDLL:
     lib.eepacc_qp_solve_batched_dual.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [dp] * 8 + [dp, dp] + [dp] * 3 + [dp] * 5 + [vp]
     lib.eepacc_qp_kkt_solve_batched.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int] + [dp] * 2 + [dp] * 2 + [dp] * 3 + [dp] * 3 + [dp, vp]
     for name, argtypes in (list(AB_BUILD_ARGTYPES.items()) + list(FB_BUILD_ARGTYPES.items()) + list(BL_BUILD_ARGTYPES.items())
-                           + list(AB_EST_ARGTYPES.items()) + list(BL_EST_ARGTYPES.items()) + list(FB_EST_ARGTYPES.items()) + list(CLASSES_EST_ARGTYPES.items()) + list(CLASSES_BUILD_ARGTYPES.items())):
+                           + list(AB_EST_ARGTYPES.items()) + list(BL_EST_ARGTYPES.items()) + list(FB_EST_ARGTYPES.items()) + list(CLASSES_EST_ARGTYPES.items()) + list(CLASSES_BUILD_ARGTYPES.items()) + list(CLASSES_FB_ARGTYPES.items())):
         getattr(lib, name).argtypes = argtypes
     lib.eepacc_synchronize.argtypes = [vp, vp]
     lib.eepacc_build_flags.restype = C.c_char_p
@@ -98,6 +98,7 @@ ABI_SYMBOLS = ["eepacc_last_error", "eepacc_version", "eepacc_sizeof_settings", 
                "eepacc_bl_step_est", "eepacc_bl_build_qp_est", "eepacc_run_blmpc_preview",
                "eepacc_classes_step_est", "eepacc_run_classes_preview",
                "eepacc_classes_qp_size", "eepacc_classes_qp_rows", "eepacc_classes_build_qp",
+               "eepacc_classes_fb_step", "eepacc_run_classes_fbmpc",
                "eepacc_synchronize", "eepacc_build_flags"]
 
 
@@ -186,8 +187,9 @@ class Engine:
         """eepacc_create_classes / eepacc_create_classes_bl: one engine for instances of several settings classes.
         OPT_list[k], V_list[k] are the settings and the vehicle of class k; N_hor and Tvec must agree.  With ABMPC settings
         (bl_mode 0 or absent) set_classes() says which class every instance of the next launches belongs to; ab_step,
-        run_abmpc, run_abmpc_host, postprocess and the key figures then work as on an ordinary engine, every other controller
-        is refused.  Where every class has the same bl_mode 1 (settings.Settings_BL) or 2 (Settings_TV) the engine is one of
+        run_abmpc, run_abmpc_host, postprocess and the key figures then work as on an ordinary engine, and classes_fb_step /
+        run_classes_fbmpc run FBMPC on the same classes (W_FB, FBuseTaylor and b_quadr of every class) with state of their
+        own; fb_step / run_fbmpc and every other controller are refused.  Where every class has the same bl_mode 1 (settings.Settings_BL) or 2 (Settings_TV) the engine is one of
         eepacc_create_classes_bl and serves run_blmpc / ab_step / run_blmpc_host, or tv_step / run_tvmpc / run_tvmpc_host,
         in the same way; classes that disagree in bl_mode raise ValueError."""
         if len(OPT_list) != len(V_list) or len(OPT_list) < 1:
@@ -573,6 +575,18 @@ class Engine:
         rule of run_abmpc_preview (scenarios.lead_preview); the ego estimator stays the engine's.  Arguments and results as
         run_abmpc_preview."""
         return self._run_preview(self.lib.eepacc_run_fbmpc_preview, s0, v0, a_minus1, s_tv, v_tv, n_steps, resume, out)
+
+    # FBMPC on an engine of from_classes (ABMPC settings classes): one mixed launch
+    def classes_fb_step(self, s, v, v_prev, a_prev, Fm_prev, Fb_prev, t0, s_tv, v_tv, a_tv_prev, want_pred: bool = True):
+        """eepacc_classes_fb_step: fb_step on an engine of from_classes, every instance with the settings of its class in
+        set_classes' map.  Arguments and results as fb_step; bit for bit what a plain engine of the instance's class computes.
+        Reads and writes FBMPC state of the engine's own, which ab_step / run_abmpc leave alone."""
+        return self._step(self.lib.eepacc_classes_fb_step, (s, v, v_prev, a_prev, Fm_prev, Fb_prev, t0, s_tv, v_tv, a_tv_prev), want_pred)
+
+    def run_classes_fbmpc(self, s0, v0, a_minus1, s_tv, v_tv, resume: bool = False, out=None):
+        """eepacc_run_classes_fbmpc: closed-loop FBMPC on an engine of from_classes, e.g. the twelve use cases of
+        scenarios.make_use_case_mix(..., controller="ab") in one launch.  Arguments and results as run_fbmpc."""
+        return self._run(self.lib.eepacc_run_classes_fbmpc, (s0, v0, a_minus1), (s_tv, v_tv), None, resume, out)
 
     def postprocess(self, traj):
         t = self.torch

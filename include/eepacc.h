@@ -183,7 +183,9 @@ void eepacc_destroy(eepacc_handle* h);
  *
  * Such a handle runs eepacc_ab_step, eepacc_run_abmpc (also resumed in chunks), eepacc_run_abmpc_host and
  * eepacc_postprocess (each instance with the settings of its class) and eepacc_reset, eepacc_synchronize,
- * eepacc_last_iterations; the FBMPC, BLMPC, TVMPC and dense-QP entry points return EEPACC_ENOTSUP on it.  It runs the
+ * eepacc_last_iterations; the FBMPC, BLMPC, TVMPC and dense-QP entry points return EEPACC_ENOTSUP on it.  FBMPC on its
+ * classes (each settings struct carries W_FB, FBuseTaylor and b_quadr) has entries of its own, eepacc_classes_fb_step and
+ * eepacc_run_classes_fbmpc, after eepacc_run_fbmpc; eepacc_fb_step / eepacc_run_fbmpc keep refusing the handle.  It runs the
  * class kernels also with n_classes = 1; the results of an instance are bit for bit those of a handle created by
  * eepacc_create from the settings of its class. */
 #define EEPACC_MAX_CLASSES 4096
@@ -458,6 +460,41 @@ int  eepacc_run_fbmpc(eepacc_handle* h, int B, int n_steps,
                       const double* s0, const double* v0, const double* a_minus1,
                       const double* s_tv, const double* v_tv,
                       double* traj, int32_t* status, void* stream);
+
+/* The same two operators on a handle of eepacc_create_classes: the reference's use cases (GetUseCase.m) or a Settings.m sweep
+ * under FBMPC in one launch.  Arguments, layouts and results are those of eepacc_fb_step and eepacc_run_fbmpc (resumption in
+ * chunks included); every instance runs with the settings of its class in eepacc_set_classes' map: route tables, W_FB,
+ * FBuseTaylor, b_quadr, the estimator modes and time constants, tau_min, h_min, s_goal, N_integratePlant and the whole
+ * vehicle.  N_hor and Tvec are class 0's, as for every class handle.  The results of an instance are bit for bit those of
+ * eepacc_fb_step / eepacc_run_fbmpc on a handle of eepacc_create from the settings of its class, launched with the same B and
+ * n_steps (the kernels are the structured ones, eepacc_fbs.hip, with the class of the instance bound per wave).
+ * State.  The entries read and write FBMPC state of the handle's own (warm working set, carried A22 / D2 and predictions,
+ * closed-loop carry, step counter) beside the ABMPC state, as on a handle of eepacc_create: eepacc_ab_step / eepacc_run_abmpc
+ * and the other ABMPC entries between two of these calls change nothing of their results, and the reverse.  eepacc_reset and
+ * eepacc_set_classes reset it.  As with eepacc_run_fbmpc, a closed loop after a step needs eepacc_reset first.
+ * eepacc_last_iterations, eepacc_postprocess, eepacc_kpis, eepacc_follow_kpis (EEPACC_FKPI_W_FB) and eepacc_route_kpis work
+ * on the result, per class.
+ * EEPACC_ENOTSUP, the message naming the entry and the cause: a handle of eepacc_create (use eepacc_fb_step /
+ * eepacc_run_fbmpc); a handle of eepacc_create_classes_bl; a class that the structured kernels do not represent (b_quadr(4)
+ * != 0, W_FB(1) * b_quadr(5) <= 0, a W_FB outside their signs: the message names the first such class and the field) or a
+ * horizon above their LDS budget.  There is no dense path for classes.  EEPACC_EINVAL: a NULL required buffer (s_pred and
+ * v_pred may be NULL), B outside [0, max_batch] or different from the last eepacc_set_classes, no map set, n_steps < 0.
+ * B = 0 (and n_steps = 0) returns EEPACC_OK.
+ * Not built: supplied horizon guesses for FBMPC classes, the condensed QP of an FBMPC step of a class as data
+ * (eepacc_classes_build_qp builds the ABMPC problem of such a handle), FBMPC classes through the dense path, and _host and MEX
+ * forms of these two entries.
+ * Design, code listing and what is measured: DESIGN.md section 3.5f. */
+int  eepacc_classes_fb_step(eepacc_handle* h, int B,
+                            const double* s, const double* v, const double* v_prev,
+                            const double* a_prev, const double* Fm_prev, const double* Fb_prev,
+                            const double* t0, const double* s_tv, const double* v_tv,
+                            const double* a_tv_prev,
+                            double* out, double* s_pred, double* v_pred, int32_t* status,
+                            void* stream);
+int  eepacc_run_classes_fbmpc(eepacc_handle* h, int B, int n_steps,
+                              const double* s0, const double* v0, const double* a_minus1,
+                              const double* s_tv, const double* v_tv,
+                              double* traj, int32_t* status, void* stream);
 
 /* The condensed QP of one FBMPC step as data, the counterpart of eepacc_ab_build_qp: what a user of the reference holds as H,
  * c, G, g_lb, g_ub after ABO/RunOpt_FBMPC.m:215-264 and finds saved as optSol.H, optSol.G.  The structured FBMPC kernels never
